@@ -16,9 +16,12 @@ gathers the per-frame keypoint/descriptor records with one RCCL all_gather per s
 Started without a launcher (`WORLD_SIZE` unset) it spawns the N ranks itself before touching the GPU; under
 `python -m torch.distributed.run` it uses the ranks it is given.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` (dominant kernel, HIP events on the
-launching stream), at N=1 `cpu_baseline` (the CPU oracle on a bounded sample) and `e2e_frames_per_s` (host images in,
-host keypoints / descriptors / matches out, double-buffered over PCIe) -- `value` itself is HBM-resident.
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times `--steps` steps and
+prints the headline (`value`, `ms_per_step`) and nothing else.  `--full` adds the side measurements and checks: `roofline`
+(dominant kernel, HIP events on the launching stream), `config.self_check`, the C-ABI pipeline handle, at N=1 `cpu_baseline`
+(the CPU oracle on a bounded sample), `e2e_frames_per_s` (host images in, host keypoints / descriptors / matches out,
+double-buffered over PCIe), `content` and `per_frame` -- `value` itself is HBM-resident either way.
+`--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy (see write_outputs).
 """
 from __future__ import annotations
 
@@ -59,6 +62,9 @@ W, H, NFEAT = CONFIGS["kitti_stereo"]["w"], CONFIGS["kitti_stereo"]["h"], CONFIG
 MBF, FX, TH_STEREO = CONFIGS["kitti_stereo"]["bf"], CONFIGS["kitti_stereo"]["fx"], CONFIGS["kitti_stereo"]["th"]   # th = 7: Tracking.cc:793-798
 SHIFT_X = -2.0                             # synth.sequence: the image content moves 2 px per frame
 MONO_DEPTH = 10.0                          # kitti_mono: depth at which the previous frame's keypoints are un-projected
+DUMP_FRAMES = 32                           # --dump-outputs: per-keypoint rows of at most this many frames (fixed, seeded sample)
+DUMP_LIMIT = 64 << 20                      # --dump-outputs: bytes in all
+SEED_DUMP = 20240611                       # --dump-outputs: seed of the frame sample
 
 
 def camera_records(n, sf, cfg=None):
@@ -300,11 +306,12 @@ def per_frame_latency(cfg, n_frames: int):
                     "ORBmatcher::SearchByProjection(cur,last), host images in, host keypoints / matches out, one pair at a time"}
 
 
-def cabi_driver(rig, steps: int, output_mask: int, slots: int = 3):
+def cabi_driver(rig, steps: int, output_mask: int, slots: int = 3, check: bool = True):
     """The step driven through the C ABI's pipeline handle (orbfe_pipeline_*: what a C / C++ host calls; no torch in the loop): the rig's
     frames uploaded once into the slots' device blocks, then `steps` chunks by orbfe_pipeline_submit_resident in a ring of `slots`
-    slots.  Returns the rate and a self-check: a second handle that copies every block out must reproduce, byte for byte, what the
-    torch-driven step left in the rig's buffers (which tests/test_bench_layout_gpu.py compares with the oracle)."""
+    slots.  Returns the rate, what the last chunk returned (`last_output`) and, with `check`, a self-check: a second handle that copies every
+    block out must reproduce, byte for byte, what the torch-driven step left in the rig's buffers (which tests/test_bench_layout_gpu.py
+    compares with the oracle)."""
     import torch
     from refactored_orb_slam2_amd._lib import KP_DTYPE
     from refactored_orb_slam2_amd.pipeline import StereoPipeline
@@ -337,6 +344,11 @@ def cabi_driver(rig, steps: int, output_mask: int, slots: int = 3):
             p.wait(s)
         dt = time.perf_counter() - t0
         n_tr = int(np.asarray(p.output(0)["n_tracked"]).sum())
+        last = {k: np.array(v) for k, v in p.output((steps - 1) % slots).items() if k != "cap"} if steps > 0 else None
+    res = {"frames_per_s": round(F * steps / dt, 1), "ms_per_step": round(dt / steps * 1e3, 4), "steps": steps, "slots": slots,
+           "output_mask": output_mask, "tracked_per_frame": round(n_tr / F, 1), "last_output": last}
+    if not check:
+        return res
     # ---- self-check against the torch-driven step (one chunk per slot through a handle that copies everything out)
     rig.step(); rig.barrier()
     B = rig.B0
@@ -355,10 +367,9 @@ def cabi_driver(rig, steps: int, output_mask: int, slots: int = 3):
             ok = ok and o["kps_left"][:, :cap][m].tobytes() == rk[:, :cap][m].tobytes() and o["desc_left"][:, :cap][m].tobytes() == ref["dl"][:, :cap][m].tobytes()
             ok = ok and o["u_right"][:, :cap][m].tobytes() == ref["ur"][:, :cap][m].tobytes() and o["depth"][:, :cap][m].tobytes() == ref["depth"][:, :cap][m].tobytes()
             ok = ok and o["assigned"][:, :cap][m].tobytes() == ref["assigned"][:, :cap][m].tobytes()
-    return {"frames_per_s": round(F * steps / dt, 1), "ms_per_step": round(dt / steps * 1e3, 4), "steps": steps, "slots": slots,
-            "output_mask": output_mask, "tracked_per_frame": round(n_tr / F, 1), "equals_torch_driven_step": bool(ok),
+    return dict(res, **{"equals_torch_driven_step": bool(ok),
             "path": "orbfe_pipeline_submit_resident / orbfe_pipeline_wait in a ring of slots (ctypes; frames resident in the slots' device blocks); "
-                    "output_mask 8 = tracked assignments + counts copied to the host per chunk, 16 = counts only, 0 = every block (37 MB)"}
+                    "output_mask 8 = tracked assignments + counts copied to the host per chunk, 16 = counts only, 0 = every block (37 MB)"})
 
 
 def spawn_ranks(n: int) -> int:
@@ -459,6 +470,7 @@ class StepRig:
         self.gatherer = None
         self.world = 1
         self._dist = None
+        self.last_B = self.B0   # the buffer set the last step wrote (--dump-outputs)
 
     def Buffers(self):
         return _Buffers(self)
@@ -520,6 +532,7 @@ class StepRig:
         cfg, W, H, sM, sL, sR = self.cfg, self.W, self.H, self.sM, self.sL, self.sR
         xl, xr, m, B, eL, eR, eT = self.pipe_sets[self.pipe_k % self.n_sets]
         self.pipe_k += 1
+        self.last_B = B
         sL.wait_event(eT); sR.wait_event(eT)
         xl.extract_batch_device(B.dL, B.kl, B.dl, B.nl, stream=sL)
         xr.extract_batch_device(B.dR, B.kr, B.dr, B.nr, stream=sR)
@@ -544,6 +557,7 @@ class StepRig:
                 if self.two_sets:
                     sM.wait_stream(self.sL); sM.wait_stream(self.sR)   # (a one-stream pass behind pipelined steps ...
                 self._step(sM, self.B0)
+                self.last_B = self.B0
                 if self.two_sets:
                     self.pipe_sets[0][6].record(sM)               #  ... and in front of the next ones: set 0 is free when this step has ended)
 
@@ -625,6 +639,86 @@ class _Buffers:
         self.grp = z(F, cap, dt=torch.int32)
 
 
+def dump_frames(F):
+    """Frames whose per-keypoint rows --dump-outputs writes: all of them up to DUMP_FRAMES, else a fixed, seeded sample."""
+    if F <= DUMP_FRAMES:
+        return np.arange(F)
+    return np.sort(np.random.default_rng(SEED_DUMP).choice(F, DUMP_FRAMES, replace=False))
+
+
+def kp_columns(kp):
+    """KP_DTYPE records (..., ) -> (..., 7) float64: x, y, size, angle, response, octave, class_id (exact for every field)."""
+    return np.stack([kp[f].astype(np.float64) for f in kp.dtype.names], axis=-1)
+
+
+def write_outputs(path, frames, counts, rows):
+    """--dump-outputs: `counts` = name -> per-frame array (F,), written whole; `rows` = name -> (array over the sampled `frames`
+    (S, cap, ...), how many leading rows of each of those frames are results (S,)), written as those rows concatenated in frame order.
+    Rows behind a frame's count are whatever earlier steps left and are never written.  float64 for integers and records, float32 for
+    what the step computes in float32 and for descriptor bytes."""
+    out = {"frames": np.asarray(frames, np.float64)}
+    for k, v in counts.items():
+        out[k] = np.asarray(v).astype(np.float64)
+    for k, (a, n) in rows.items():
+        a = np.asarray(a)
+        dt = np.float32 if a.dtype in (np.float32, np.uint8) else np.float64
+        out[k] = np.concatenate([a[i, :max(int(n[i]), 0)] for i in range(len(frames))]).astype(dt)
+    total = sum(v.nbytes for v in out.values())
+    if total > DUMP_LIMIT:
+        raise SystemExit(f"--dump-outputs: {total} bytes, more than {DUMP_LIMIT}")
+    os.makedirs(path, exist_ok=True)
+    for k, v in out.items():
+        np.save(os.path.join(path, k + ".npy"), v)
+
+
+def step_outputs(rig, B):
+    """What a caller of the timed step receives in the buffer set `B` the last step wrote: the per-frame counts, and per keypoint of the
+    sampled frames the left (and right) keypoints and descriptors, mvuRight / mvDepth, the tracked assignment or the brute-force match."""
+    import torch
+    from refactored_orb_slam2_amd._lib import BF_DTYPE, KP_DTYPE
+    cfg, F, STEREO = rig.cfg, rig.F, rig.STEREO
+    frames = dump_frames(F)
+    sel = torch.as_tensor(frames, device=B.nl.device)
+    host = lambda t: t.index_select(0, sel).cpu().numpy()
+    nl = B.nl.cpu().numpy()
+    counts, rows = {"n_left": nl}, {}
+    n = nl[frames]
+    rows["left_keypoints"] = (kp_columns(host(B.kl).view(KP_DTYPE)[..., 0]), n)
+    rows["left_descriptors"] = (host(B.dl), n)
+    if STEREO:
+        nr = B.nr.cpu().numpy()
+        counts["n_right"], counts["n_stereo"] = nr, B.n_stereo.cpu().numpy()
+        rows["right_keypoints"] = (kp_columns(host(B.kr).view(KP_DTYPE)[..., 0]), nr[frames])
+        rows["right_descriptors"] = (host(B.dr), nr[frames])
+        rows["u_right"], rows["depth"] = (host(B.ur), n), (host(B.depth), n)
+    if cfg["match"] == "projection":
+        counts["n_tracked"] = B.n_track.cpu().numpy()
+        rows["assigned"] = (host(B.assigned), n)
+    else:   # frame f against frame f - 1: frame 0 has no match records
+        bf = host(B.bf).view(BF_DTYPE)[..., 0]
+        rows["bow_matches"] = (np.stack([bf[f].astype(np.int64) for f in BF_DTYPE.names], axis=-1), np.where(frames > 0, n, 0))
+    return frames, counts, rows
+
+
+def pipeline_outputs(o, output_mask):
+    """The same for the C-ABI pipeline handle's last chunk (`o` = StereoPipeline.output(slot), copied): the blocks its output_mask
+    selects (include/orbfe.h ORBFE_PIPE_OUT_*; the counts always)."""
+    F = len(o["n_left"])
+    frames = dump_frames(F)
+    counts = {"n_left": o["n_left"], "n_right": o["n_right"], "n_stereo": o["n_stereo"], "n_tracked": o["n_tracked"]}
+    n = np.asarray(o["n_left"])[frames]
+    every = output_mask == 0
+    rows = {}
+    if every or output_mask & 1:
+        rows["left_keypoints"] = (kp_columns(o["kps_left"][frames]), n)
+    if every or output_mask & 2:
+        rows["left_descriptors"] = (o["desc_left"][frames], n)
+    if every or output_mask & 4:
+        rows["u_right"], rows["depth"] = (o["u_right"][frames], n), (o["depth"][frames], n)
+    if every or output_mask & 8:
+        rows["assigned"] = (o["assigned"][frames], n)
+    return frames, counts, rows
+
 
 def main():
     if os.environ.get("ORBFE_BENCH_WATCHDOG"):  # debugging aid: dump all stacks and exit if the run exceeds N seconds
@@ -636,13 +730,20 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--frames", type=int, default=256, help="frames per GPU per step")
     ap.add_argument("--config", choices=sorted(CONFIGS), default="kitti_stereo")
-    ap.add_argument("--cpu-sample", type=int, default=160, help="frames timed on the CPU oracle (0 = skip)")
-    ap.add_argument("--e2e-steps", type=int, default=12, help="steps of the PCIe-inclusive measurement (0 = skip)")
-    ap.add_argument("--per-frame", type=int, default=192, help="stereo pairs pushed one at a time through the C++ drop-in classes for per_frame_ms (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, every side measurement and check (off by default: a plain run sets up, warms up, times --steps "
+                         "steps and prints the line): roofline and per-stage times, config.self_check, the C-ABI pipeline handle, the "
+                         "PCIe-inclusive rate, content sensitivity, per-frame latency, the CPU baseline, the standalone collective at N > 1")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32 / float64): per-frame counts, "
+                         f"and the per-keypoint results of at most {DUMP_FRAMES} frames (frames.npy: which)")
+    ap.add_argument("--cpu-sample", type=int, default=160, help="--full: frames timed on the CPU oracle (0 = skip)")
+    ap.add_argument("--e2e-steps", type=int, default=12, help="--full: steps of the PCIe-inclusive measurement (0 = skip)")
+    ap.add_argument("--per-frame", type=int, default=192, help="--full: stereo pairs pushed one at a time through the C++ drop-in classes for per_frame_ms (0 = skip)")
     ap.add_argument("--c-abi-gather", type=int, default=0, help="N > 1: after the line, run the record gather through the C ABI (orbfe_gather_*, RCCL inside "
                                                                 "liborbfe) in both modes, compare with the local records, report on stderr (default off: "
                                                                 "the path has never run with peers and must not be able to cost the line)")
-    ap.add_argument("--content-steps", type=int, default=30, help="steps per image content of the content-sensitivity key (0 = skip)")
+    ap.add_argument("--content-steps", type=int, default=30, help="--full: steps per image content of the content-sensitivity key (0 = skip)")
     ap.add_argument("--gather-impl", choices=("auto", "torch", "cabi"), default="auto",
                     help="which implementation of the record gather is the timed collective: `cabi` = the C ABI's (orbfe_gather_*: RCCL called by "
                          "liborbfe, what a C++ host of the batched mode uses; with it the gather also runs at N = 1, a one-rank communicator), "
@@ -656,11 +757,11 @@ def main():
                          "2 resize chain + one LDS blur launch (rounds 1-4)")
     ap.add_argument("--driver", choices=("torch", "cabi"), default="torch",
                     help="what drives the timed step: torch streams / events around the C ABI's device entry points (default), or the C ABI's "
-                         "own pipeline handle (orbfe_pipeline_submit_resident: no torch in the loop, what a C++ host runs).  At N = 1 the line "
-                         "carries both (config.cabi_driver); with `cabi`, `value` is the handle's rate")
+                         "own pipeline handle (orbfe_pipeline_submit_resident: no torch in the loop, what a C++ host runs).  With --full at N = 1 "
+                         "the line carries both (config.cabi_driver); with `cabi`, `value` is the handle's rate")
     ap.add_argument("--cabi-outputs", type=int, default=8, help="orbfe_pipeline_config.output_mask of the C-ABI driver (8: tracked assignments + counts, "
                                                                  "16: counts only, 0: every block)")
-    ap.add_argument("--cabi-steps", type=int, default=120, help="chunks timed through the C-ABI driver (0 = skip)")
+    ap.add_argument("--cabi-steps", type=int, default=120, help="--full: chunks timed through the C-ABI driver (0 = skip)")
     ap.add_argument("--queries", choices=("fused", "two_pass"), default="fused",
                     help="fused (default): UnprojectStereo + the projection of SearchByProjection(cur, last) in one pass "
                          "(orbfe_track_queries_stereo_device); two_pass: orbfe_unproject_stereo_device -> 60-byte point records -> "
@@ -749,8 +850,6 @@ def main():
     n_kp = int(B0.nl.sum().item()) + (int(B0.nr.sum().item()) if STEREO else 0)
     n_st = int(B0.n_stereo.sum().item())
     n_tr = int(B0.n_track.sum().item()) if cfg["match"] == "projection" else int((B0.bf.view(torch.int32)[..., 0] >= 0).sum().item())
-    # measured FAST candidates per image (for the algorithmic byte count of the FAST kernel)
-    cand_per_img = float(np.mean([sum(len(exL.debug_candidates(i, l)[0]) for l in range(NLEVELS)) for i in range(min(F, 4))]))
 
     # all-stage event timing costs ~2 % of the step: a short untimed pass yields the stage breakdown (and names the
     # dominant kernel); inside the timed region only that kernel is bracketed by HIP events on its launch stream
@@ -762,53 +861,66 @@ def main():
                 tot[k] = (a[0] + v[0], a[1] + v[1])
         return tot
 
-    lr["n"] = 1
-    for e in extractors:
-        e.profile(True); e.stage_times(reset=True)
-    for _ in range(3):
-        step()
-    barrier()
-    lr["n"] = args.lr_streams
-    stage_ms_all = {k: (v[0] / max(v[1] // 2 if k == "pyramid" else v[1], 1)) for k, v in stage_sums().items()}
-    # the dominant KERNEL: the level chain ("pyramid") is eight launches, none of them as long as FAST's one
-    dom = max((k for k in stage_ms_all if k != "pyramid"), key=lambda k: stage_ms_all[k])
-    # the dominant kernel is bracketed by HIP events on every DOM_EVERY-th step of the timed region: an event record in front of and
-    # behind a launch leaves ~6 us of idle GPU each (kernel trace), 24 us per stereo step if every launch were timed (0.8 %)
-    DOM_EVERY = 8
-    # the dominant kernel alone on the chip, timed without event records around the other stages (those leave idle gaps in front of
-    # it: FAST then finds less of the pyramid in the Infinity Cache): sixteen one-stream steps -- the `roofline` figure
-    lr["n"] = 1
-    for e in extractors:
-        e.profile(True, [dom]); e.stage_times(reset=True)
-    for _ in range(16):
-        step()
-    barrier()
-    lr["n"] = args.lr_streams
-    _sd = stage_sums()[dom]
-    dom_alone_launches = max(_sd[1] // 2 if dom == "pyramid" else _sd[1], 1)
-    stage_ms_all[dom] = _sd[0] / dom_alone_launches
-    for e in extractors:
-        e.profile(False); e.stage_times(reset=True)
-    for _ in range(max(n_sets, 2)):
-        step()           # back on the timed region's stream layout
-    barrier()
-    ref_ev = torch.cuda.Event(enable_timing=True)   # the clock of the dominant kernel's launch intervals (orbfe_stage_intervals)
-    ref_ev.record(sM)
+    # ---- --full: the untimed passes behind `roofline` (every stage, then the dominant kernel, alone on the chip), in front of the
+    #      timed region; a plain run goes straight to it
+    if args.full:
+        # measured FAST candidates per image (for the algorithmic byte count of the FAST kernel)
+        cand_per_img = float(np.mean([sum(len(exL.debug_candidates(i, l)[0]) for l in range(NLEVELS)) for i in range(min(F, 4))]))
+
+        lr["n"] = 1
+        for e in extractors:
+            e.profile(True); e.stage_times(reset=True)
+        for _ in range(3):
+            step()
+        barrier()
+        lr["n"] = args.lr_streams
+        stage_ms_all = {k: (v[0] / max(v[1] // 2 if k == "pyramid" else v[1], 1)) for k, v in stage_sums().items()}
+        # the dominant KERNEL: the level chain ("pyramid") is eight launches, none of them as long as FAST's one
+        dom = max((k for k in stage_ms_all if k != "pyramid"), key=lambda k: stage_ms_all[k])
+        # the dominant kernel is bracketed by HIP events on every DOM_EVERY-th step of the timed region: an event record in front of and
+        # behind a launch leaves ~6 us of idle GPU each (kernel trace), 24 us per stereo step if every launch were timed (0.8 %)
+        DOM_EVERY = 8
+        # the dominant kernel alone on the chip, timed without event records around the other stages (those leave idle gaps in front of
+        # it: FAST then finds less of the pyramid in the Infinity Cache): sixteen one-stream steps -- the `roofline` figure
+        lr["n"] = 1
+        for e in extractors:
+            e.profile(True, [dom]); e.stage_times(reset=True)
+        for _ in range(16):
+            step()
+        barrier()
+        lr["n"] = args.lr_streams
+        _sd = stage_sums()[dom]
+        dom_alone_launches = max(_sd[1] // 2 if dom == "pyramid" else _sd[1], 1)
+        stage_ms_all[dom] = _sd[0] / dom_alone_launches
+        for e in extractors:
+            e.profile(False); e.stage_times(reset=True)
+        for _ in range(max(n_sets, 2)):
+            step()           # back on the timed region's stream layout
+        barrier()
+        ref_ev = torch.cuda.Event(enable_timing=True)   # the clock of the dominant kernel's launch intervals (orbfe_stage_intervals)
+        ref_ev.record(sM)
+    else:
+        # as many untimed steps in front of the clock as the passes above run (3 + 16 + the return to the layout), on the timed layout:
+        # the timed region finds the chip and every set of handles as warm as in a --full run
+        for _ in range(3 + 16 + max(n_sets, 2)):
+            step()
     barrier()
     t0 = time.perf_counter()
     for i in range(args.steps):
-        if i % DOM_EVERY == 0:
+        if args.full and i % DOM_EVERY == 0:
             for e in extractors:
                 e.profile(True, [dom])
-        elif i % DOM_EVERY == 1:
+        elif args.full and i % DOM_EVERY == 1:
             for e in extractors:
                 e.profile(False)
         step()
     barrier()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0 and args.driver != "cabi":   # what the timed step computed last, before anything else runs
+        write_outputs(args.dump_outputs, *step_outputs(rig, rig.last_B))
     rank_rates, coll_ms = None, None
     gather_check = None
-    if gatherer is not None:
+    if args.full and gatherer is not None:
         # the gathered records of the last timed step == this rank's own records at its slot (the collective moved the right bytes)
         res = gatherer.result()
         if res is not None:
@@ -821,56 +933,62 @@ def main():
         dist.all_gather(every, mine)
         rank_rates = [round(F * args.steps / float(x.item()), 1) for x in every]
         dt = max(float(x.item()) for x in every)
-        # the collective on its own (not overlapped with a step): HIP events around three blocking gathers
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        with torch.cuda.stream(sM):
-            gatherer.launch(B0.nl, B0.kl, B0.dl); gatherer.wait()
-            torch.cuda.synchronize(); dist.barrier()
-            ev0.record(sM)
-            for _ in range(3):
+        if args.full:
+            # the collective on its own (not overlapped with a step): HIP events around three blocking gathers
+            ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            with torch.cuda.stream(sM):
                 gatherer.launch(B0.nl, B0.kl, B0.dl); gatherer.wait()
-            ev1.record(sM)
-        torch.cuda.synchronize()
-        coll_ms = ev0.elapsed_time(ev1) / 3
-    # the dominant kernel's timed launches as intervals on one clock: with the two extractors on two streams a launch's own
-    # first-to-last-event time contains the other launch's share of the chip; the UNION of the intervals is the time the chip spent on
-    # the kernel, and the bytes of all those launches over that time its achieved rate
-    dom_iv = []
-    for e in extractors:
-        dom_iv += [(a, b) for (st, a, b) in e.stage_intervals(ref_ev) if st == dom]
-    dom_iv.sort()
-    dom_union, cur_a, cur_b = 0.0, None, None
-    for a, b in dom_iv:
-        if cur_b is None or a > cur_b:
-            if cur_b is not None:
-                dom_union += cur_b - cur_a
-            cur_a, cur_b = a, b
-        else:
-            cur_b = max(cur_b, b)
-    if cur_b is not None:
-        dom_union += cur_b - cur_a
-    dom_own = sum(b - a for a, b in dom_iv)
-    st_dom = stage_sums()[dom]
-    for e in extractors:
-        e.profile(False)
+                torch.cuda.synchronize(); dist.barrier()
+                ev0.record(sM)
+                for _ in range(3):
+                    gatherer.launch(B0.nl, B0.kl, B0.dl); gatherer.wait()
+                ev1.record(sM)
+            torch.cuda.synchronize()
+            coll_ms = ev0.elapsed_time(ev1) / 3
+    if args.full:
+        # the dominant kernel's timed launches as intervals on one clock: with the two extractors on two streams a launch's own
+        # first-to-last-event time contains the other launch's share of the chip; the UNION of the intervals is the time the chip spent on
+        # the kernel, and the bytes of all those launches over that time its achieved rate
+        dom_iv = []
+        for e in extractors:
+            dom_iv += [(a, b) for (st, a, b) in e.stage_intervals(ref_ev) if st == dom]
+        dom_iv.sort()
+        dom_union, cur_a, cur_b = 0.0, None, None
+        for a, b in dom_iv:
+            if cur_b is None or a > cur_b:
+                if cur_b is not None:
+                    dom_union += cur_b - cur_a
+                cur_a, cur_b = a, b
+            else:
+                cur_b = max(cur_b, b)
+        if cur_b is not None:
+            dom_union += cur_b - cur_a
+        dom_own = sum(b - a for a, b in dom_iv)
+        st_dom = stage_sums()[dom]
+        for e in extractors:
+            e.profile(False)
     # ---- self-check of the layout that was just timed (after the clock stopped): what the last steps left in every set's buffers
     #      is identical across the sets and identical to a one-stream, one-set step (the layout the stage parity tests cover);
     #      tests/test_bench_layout_gpu.py compares the same object's outputs with the oracle
-    self_check = rig.self_check()
+    self_check = rig.self_check() if args.full else None
     # ---- the same step driven through the C ABI's pipeline handle (N = 1, STEREO + projection only: what the handle implements)
     cabi = None
-    if world == 1 and STEREO and cfg["match"] == "projection" and (args.cabi_steps > 0 or args.driver == "cabi"):
+    if world == 1 and STEREO and cfg["match"] == "projection" and ((args.full and args.cabi_steps > 0) or args.driver == "cabi"):
         try:
-            cabi = cabi_driver(rig, args.steps if args.driver == "cabi" else args.cabi_steps, args.cabi_outputs, slots=max(n_sets, 2))
+            cabi = cabi_driver(rig, args.steps if args.driver == "cabi" else args.cabi_steps, args.cabi_outputs, slots=max(n_sets, 2),
+                               check=args.full)
         except Exception as ex:
             if args.driver == "cabi":
                 raise
             cabi = {"error": str(ex)[:300]}
+        if args.dump_outputs and args.driver == "cabi":   # the handle's last timed chunk
+            write_outputs(args.dump_outputs, *pipeline_outputs(cabi["last_output"], args.cabi_outputs))
+        cabi.pop("last_output", None)
 
     # ---- PCIe-inclusive rate (N = 1): pinned host images in, host keypoints / descriptors / match results out, two buffer
     #      sets: the H2D copy of step i+1 and the D2H copy of step i-1 run beside the kernels of step i
     e2e = None
-    if world == 1 and args.e2e_steps > 0:
+    if args.full and world == 1 and args.e2e_steps > 0:
         Bs = [B0, Buffers()]
         sH, sD = torch.cuda.Stream(dev), torch.cuda.Stream(dev)
         host_out = [[torch.empty_like(t, device="cpu").pin_memory() for t in
@@ -910,7 +1028,7 @@ def main():
     #      synthetic generator of SURVEY.md 8(d); FAST's cost drivers (fallback cells, quick-test early-outs) differ 2-3 x between
     #      it and real texture (DESIGN lesson 18), dense noise sends the quadtree's keys to HBM, a flat frame has no corner at all.
     content = None
-    if world == 1 and args.content_steps > 0 and STEREO and cfg["match"] == "projection":
+    if args.full and world == 1 and args.content_steps > 0 and STEREO and cfg["match"] == "projection":
         def content_images(kind):
             rng = np.random.default_rng(1234)
             L = np.zeros((F, H, PITCH), np.uint8)
@@ -1005,50 +1123,68 @@ def main():
         barrier()
 
     if rank == 0:
-        px = [exL.level_size(l, W, H) for l in range(NLEVELS)]
-        sumP = sum(w * h for w, h in px)
-        P0, P7 = px[0][0] * px[0][1], px[-1][0] * px[-1][1]
-        # algorithmic bytes per image and per kernel; one launch processes F images
-        alg = {
-            # level chain: fused (launch l reads level l once, writes level l + 1 and the blurred level l), or the resize chain alone
-            "pyramid": (3 * sumP - P0) if args.blur_kind == 0 else (sumP - P7) + (sumP - P0),
-            "fast": sumP + 8 * cand_per_img,
-            "octree": 8 * cand_per_img + 4 * NFEAT,
-            "blur": 0 if args.blur_kind == 0 else 2 * sumP,
-            "describe": NFEAT * (749 + 512 + 60),
-        }
-        per_launch_ms = dict(stage_ms_all)   # untimed 3-step pass on ONE stream (every stage, every kernel alone on the chip)
-        cnt = st_dom[1] // 2 if dom == "pyramid" else st_dom[1]   # pyramid: two timed groups (level-0 copy, resize chain) per batch
-        own_ms = st_dom[0] / max(cnt, 1)                          # the dominant kernel: live, over the timed region, first to last event of a launch
-        n_iv = max(len(dom_iv), 1)
-        chip_ms = (dom_union / n_iv) if dom_iv else own_ms        # the chip's time per launch: union of the launches' intervals / launches
-        achieved = alg[dom] * F / (max(chip_ms, 1e-9) * 1e-3) / 1e9
-        achieved_alone = alg[dom] * F / (max(per_launch_ms[dom], 1e-9) * 1e-3) / 1e9
-        # HBM-side traffic of the dominant kernel: FETCH_SIZE (x2 for 16-byte-per-lane streams on gfx950) + WRITE_SIZE from the
-        # committed PMC pass of THIS kernel build (profiles/rNN_pmc_dominant.json, latest round), scaled to this launch's image count;
-        # null when the pass covers another kernel or configuration
-        traffic, traffic_src, issue = None, None, None
-        try:
-            import glob
-            pmc_path = sorted(glob.glob(os.path.join(ROOT, "profiles", "r[0-9][0-9]_pmc_dominant.json")))[-1]   # the latest round's pass
-            pmc = json.load(open(pmc_path))
-            if pmc["stage"] == dom and pmc["config"] == args.config:
-                if pmc.get("read_kb_by_request_size") is not None:   # fabric requests split by size (TCC_EA0_RDREQ / WRREQ passes): no correction factor
-                    kb = pmc["read_kb_by_request_size"] + pmc["write_kb_by_request_size"]
-                else:
-                    kb = pmc["fetch_kb"] * pmc.get("fetch_correction", 1.0) + pmc["write_kb"]
-                traffic = int(kb * 1024 * F / pmc["images_per_launch"])
-                traffic_src = f"committed rocprofv3 --pmc pass ({pmc['kernel']}, {os.path.basename(pmc_path)}), not measured in this run"
-                if pmc.get("issue"):
-                    # what the kernel is bound by when it is not HBM (profiles/r06_fast.md): the instruction stream of its waves.  Lane-
-                    # instructions per pixel = 64 lanes x vector instructions per wave x waves / the pixels one launch tests
-                    issue = dict(pmc["issue"])
-                    if dom == "fast":
-                        issue["lane_instructions_per_pixel"] = round(64.0 * issue["valu_per_wave"] * issue["waves_per_launch"] /
-                                                                     max(sumP * pmc["images_per_launch"], 1), 2)
-                    issue["source"] = traffic_src
-        except Exception:
-            pass
+        roofline = None
+        if args.full:
+            px = [exL.level_size(l, W, H) for l in range(NLEVELS)]
+            sumP = sum(w * h for w, h in px)
+            P0, P7 = px[0][0] * px[0][1], px[-1][0] * px[-1][1]
+            # algorithmic bytes per image and per kernel; one launch processes F images
+            alg = {
+                # level chain: fused (launch l reads level l once, writes level l + 1 and the blurred level l), or the resize chain alone
+                "pyramid": (3 * sumP - P0) if args.blur_kind == 0 else (sumP - P7) + (sumP - P0),
+                "fast": sumP + 8 * cand_per_img,
+                "octree": 8 * cand_per_img + 4 * NFEAT,
+                "blur": 0 if args.blur_kind == 0 else 2 * sumP,
+                "describe": NFEAT * (749 + 512 + 60),
+            }
+            per_launch_ms = dict(stage_ms_all)   # untimed 3-step pass on ONE stream (every stage, every kernel alone on the chip)
+            cnt = st_dom[1] // 2 if dom == "pyramid" else st_dom[1]   # pyramid: two timed groups (level-0 copy, resize chain) per batch
+            own_ms = st_dom[0] / max(cnt, 1)                          # the dominant kernel: live, over the timed region, first to last event of a launch
+            n_iv = max(len(dom_iv), 1)
+            chip_ms = (dom_union / n_iv) if dom_iv else own_ms        # the chip's time per launch: union of the launches' intervals / launches
+            achieved = alg[dom] * F / (max(chip_ms, 1e-9) * 1e-3) / 1e9
+            achieved_alone = alg[dom] * F / (max(per_launch_ms[dom], 1e-9) * 1e-3) / 1e9
+            # HBM-side traffic of the dominant kernel: FETCH_SIZE (x2 for 16-byte-per-lane streams on gfx950) + WRITE_SIZE from the
+            # committed PMC pass of THIS kernel build (profiles/rNN_pmc_dominant.json, latest round), scaled to this launch's image count;
+            # null when the pass covers another kernel or configuration
+            traffic, traffic_src, issue = None, None, None
+            try:
+                import glob
+                pmc_path = sorted(glob.glob(os.path.join(ROOT, "profiles", "r[0-9][0-9]_pmc_dominant.json")))[-1]   # the latest round's pass
+                pmc = json.load(open(pmc_path))
+                if pmc["stage"] == dom and pmc["config"] == args.config:
+                    if pmc.get("read_kb_by_request_size") is not None:   # fabric requests split by size (TCC_EA0_RDREQ / WRREQ passes): no correction factor
+                        kb = pmc["read_kb_by_request_size"] + pmc["write_kb_by_request_size"]
+                    else:
+                        kb = pmc["fetch_kb"] * pmc.get("fetch_correction", 1.0) + pmc["write_kb"]
+                    traffic = int(kb * 1024 * F / pmc["images_per_launch"])
+                    traffic_src = f"committed rocprofv3 --pmc pass ({pmc['kernel']}, {os.path.basename(pmc_path)}), not measured in this run"
+                    if pmc.get("issue"):
+                        # what the kernel is bound by when it is not HBM (profiles/r06_fast.md): the instruction stream of its waves.  Lane-
+                        # instructions per pixel = 64 lanes x vector instructions per wave x waves / the pixels one launch tests
+                        issue = dict(pmc["issue"])
+                        if dom == "fast":
+                            issue["lane_instructions_per_pixel"] = round(64.0 * issue["valu_per_wave"] * issue["waves_per_launch"] /
+                                                                         max(sumP * pmc["images_per_launch"], 1), 2)
+                        issue["source"] = traffic_src
+            except Exception:
+                pass
+            roofline = {"bound": "hbm", "kernel": dom, "achieved": round(achieved_alone, 2), "peak": HBM_PEAK_GBS,
+                        "unit": "GB/s", "frac": round(achieved_alone / HBM_PEAK_GBS, 5), "traffic": traffic, "traffic_source": traffic_src, "issue": issue,
+                        "algorithmic_bytes_per_launch": int(alg[dom] * F), "avg_launch_ms": round(per_launch_ms[dom], 4),
+                        "measured": (f"HIP events on the launch stream around {dom_alone_launches} launches of the kernel in a one-stream pass of this run (every "
+                                     "kernel alone on the chip: the figure rocprofv3 --stats and the serialised --pmc passes can be compared with -- "
+                                     "profiles/rNN_kernel_stats.md, one-stream table).  In the TIMED region launches overlap by design (left | right "
+                                     "extractor on two streams, the matching half of the step before on a third), a launch's own duration there contains "
+                                     "the others' share of the chip: see timed_region"),
+                        "timed_region": {"avg_launch_ms": round(own_ms, 4), "chip_ms_per_launch": round(chip_ms, 4),
+                                         "launches_overlapping": round(dom_own / max(dom_union, 1e-9), 2) if dom_iv else 1.0,
+                                         "timed_launches": len(dom_iv), "achieved": round(achieved, 2), "frac": round(achieved / HBM_PEAK_GBS, 5),
+                                         "lr_streams": lr["n"] if STEREO else 1, "handle_sets": n_sets,
+                                         "note": "HIP events around the kernel's launches on every 8th step of the timed region (orbfe_stage_intervals): "
+                                                 "avg_launch_ms = a launch's own first-to-last-event time; chip_ms_per_launch = union of the launches' "
+                                                 "intervals / launches; achieved = their algorithmic bytes / that union"},
+                        "stage_ms_per_batch": {k: round(v, 4) for k, v in per_launch_ms.items()}}
         value = world * F * args.steps / dt
         ms_step = dt / args.steps * 1e3
         if args.driver == "cabi":   # the C ABI's handle is the measured step; the torch-driven figure stays in config.torch_driver
@@ -1068,24 +1204,11 @@ def main():
                        "collective": ((f"{'RCCL through the C ABI (orbfe_gather_records)' if gather_impl == 'cabi' else backend} "
                                        f"{'all_gather' if args.gather == 'all' else 'gather to rank 0'} of padded per-frame records, world size {world}") if gatherer is not None else "none"),
                        "keypoints_per_image": round(n_kp / n_img, 1), "stereo_matches_per_frame": round(n_st / F, 1),
-                       "matches_per_frame": round(n_tr / F, 1), "timed_region_s": round(dt, 3), "self_check": self_check},
-            "roofline": {"bound": "hbm", "kernel": dom, "achieved": round(achieved_alone, 2), "peak": HBM_PEAK_GBS,
-                         "unit": "GB/s", "frac": round(achieved_alone / HBM_PEAK_GBS, 5), "traffic": traffic, "traffic_source": traffic_src, "issue": issue,
-                         "algorithmic_bytes_per_launch": int(alg[dom] * F), "avg_launch_ms": round(per_launch_ms[dom], 4),
-                         "measured": (f"HIP events on the launch stream around {dom_alone_launches} launches of the kernel in a one-stream pass of this run (every "
-                                      "kernel alone on the chip: the figure rocprofv3 --stats and the serialised --pmc passes can be compared with -- "
-                                      "profiles/rNN_kernel_stats.md, one-stream table).  In the TIMED region launches overlap by design (left | right "
-                                      "extractor on two streams, the matching half of the step before on a third), a launch's own duration there contains "
-                                      "the others' share of the chip: see timed_region"),
-                         "timed_region": {"avg_launch_ms": round(own_ms, 4), "chip_ms_per_launch": round(chip_ms, 4),
-                                          "launches_overlapping": round(dom_own / max(dom_union, 1e-9), 2) if dom_iv else 1.0,
-                                          "timed_launches": len(dom_iv), "achieved": round(achieved, 2), "frac": round(achieved / HBM_PEAK_GBS, 5),
-                                          "lr_streams": lr["n"] if STEREO else 1, "handle_sets": n_sets,
-                                          "note": "HIP events around the kernel's launches on every 8th step of the timed region (orbfe_stage_intervals): "
-                                                  "avg_launch_ms = a launch's own first-to-last-event time; chip_ms_per_launch = union of the launches' "
-                                                  "intervals / launches; achieved = their algorithmic bytes / that union"},
-                         "stage_ms_per_batch": {k: round(v, 4) for k, v in per_launch_ms.items()}},
+                       "matches_per_frame": round(n_tr / F, 1), "timed_region_s": round(dt, 3)},
         }
+        if args.full:
+            out["config"]["self_check"] = self_check
+            out["roofline"] = roofline
         out["config"]["driver"] = args.driver
         if cfg["match"] == "projection":
             out["config"]["queries"] = ("one pass: orbfe_track_queries_stereo_device" if rig.fused_queries
@@ -1111,20 +1234,20 @@ def main():
                                    f"to {W}x{H}, the same at twice the contrast with +-6 grey levels of noise (a stand-in for foliage), the synthetic sequence with +-8 grey levels "
                                    f"of pixel noise (the quadtree's keys of level 0 leave LDS: 1 664 per level), "
                                    f"uniform noise (every level's keys in HBM), a flat frame; `value` is the synthetic sequence of SURVEY.md 8(d)")
-        if world == 1 and args.per_frame > 0 and STEREO:
+        if args.full and world == 1 and args.per_frame > 0 and STEREO:
             pf = per_frame_latency(cfg, args.per_frame)
             out["per_frame_ms"] = pf.get("median_ms")
             out["per_frame"] = pf
-        if world == 1 and args.cpu_sample > 0:
+        if args.full and world == 1 and args.cpu_sample > 0:
             out["cpu_baseline"] = cpu_baseline(args.config, args.cpu_sample)
         print(json.dumps(out), flush=True)
     if cabi is not None and cabi.get("equals_torch_driven_step") is False:
         raise SystemExit(f"rank {rank}: the C-ABI pipeline handle's results differ from the torch-driven step's")
-    if not (self_check["sets_equal"] and self_check["equals_one_stream"]):
+    if args.full and not (self_check["sets_equal"] and self_check["equals_one_stream"]):
         raise SystemExit(f"rank {rank}: the timed layout's outputs differ between the handle sets or from the one-stream step: {self_check}")
     if world > 1:
         # the gathered records of the last step == every rank's own records at its slot (the collective moved the right bytes)
-        res = gatherer.result()
+        res = gatherer.result() if args.full else None
         if res is not None:   # mode "root": rank 0 alone holds the records; it checks its own slot
             n_all, k_all, d_all = res
             mine = slice(rank * F, (rank + 1) * F)

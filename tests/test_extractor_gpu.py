@@ -590,7 +590,7 @@ def test_bench_spawns_its_ranks_and_checks_the_gather():
     env = dict(os.environ, ORBFE_BENCH_SHARE_DEVICE="1")
     env.pop("WORLD_SIZE", None); env.pop("RANK", None)
     for mode, name in (("all", "all_gather"), ("root", "gather to rank 0")):
-        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--frames", "8", "--cpu-sample", "0",
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--gpus", "2", "--steps", "3", "--frames", "8", "--cpu-sample", "0",
                             "--e2e-steps", "0", "--gather", mode], env=env, capture_output=True, text=True, timeout=600)
         assert r.returncode == 0, r.stderr[-2000:]
         line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]
@@ -611,10 +611,48 @@ def test_bench_times_the_c_abi_gather_when_asked():
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     for mode in ("all", "root"):
-        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--frames", "8", "--cpu-sample", "0", "--e2e-steps", "0",
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--steps", "3", "--frames", "8", "--cpu-sample", "0", "--e2e-steps", "0",
                             "--per-frame", "0", "--content-steps", "0", "--gather-impl", "cabi", "--gather", mode], capture_output=True, text=True, timeout=300)
         assert r.returncode == 0, r.stderr[-2000:]
         out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
         g = out["config"]["gather"]
         assert g["impl"] == "cabi" and g["mode"] == mode and g["own_slot_equal_rank0"] is True, g
         assert "orbfe_gather_records" in out["config"]["collective"] and out["value"] > 0
+
+
+def test_bench_plain_run_is_lean_and_dumps_its_last_step(tmp_path):
+    """`bench.py` without --full: the headline line and no side measurement; `--steps` timed steps; `--dump-outputs` writes the last
+    timed step's results, equal to a fresh extraction of the same synthetic frames (inputs identical from run to run)."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, root)
+    import bench
+    out_dir = tmp_path / "out"
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "1", "--frames", "8",
+                        "--dump-outputs", str(out_dir)], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    assert out["steps"] == 4 and out["warmup"] == 1 and out["value"] > 0 and out["ms_per_step"] > 0
+    assert abs(out["ms_per_step"] * 4 - out["config"]["timed_region_s"] * 1e3) <= 0.5 + 1e-3   # timed_region_s: whole ms
+    for k in ("metric", "unit", "higher_is_better", "dtype"):
+        assert k in out
+    for k in ("roofline", "cpu_baseline", "e2e_frames_per_s", "content", "per_frame"):
+        assert k not in out, k
+    assert "self_check" not in out["config"] and "cabi_driver" not in out["config"]
+    got = {p.stem: np.load(p) for p in out_dir.glob("*.npy")}
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    assert sum(a.nbytes for a in got.values()) <= bench.DUMP_LIMIT
+    np.testing.assert_array_equal(got["frames"], np.arange(8))
+    cfg = bench.CONFIGS["kitti_stereo"]
+    pairs = synth.sequence(cfg["w"], cfg["h"], 8, seq=0, stereo=True)
+    ex = ORBextractor(cfg["nfeat"], 1.2, 8, 20, 7)
+    for f in (0, 5):
+        k, d = ex(pairs[f][0])
+        o = int(got["n_left"][:f].sum())
+        assert got["n_left"][f] == len(k)
+        np.testing.assert_array_equal(got["left_keypoints"][o:o + len(k)], bench.kp_columns(k))
+        np.testing.assert_array_equal(got["left_descriptors"][o:o + len(k)], d.astype(np.float32))
+    assert got["n_tracked"].sum() > 0 and len(got["assigned"]) == got["n_left"].sum()
+    ex.close()

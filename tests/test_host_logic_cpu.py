@@ -270,3 +270,50 @@ def test_png_reader_16bit_depth_maps_and_hostile_headers(tmp_path):
     ihdr = struct.pack(">IIBBBBB", 8, 8, 8, 0, 0, 0, 0)
     (tmp_path / "short.png").write_bytes(b"\x89PNG\r\n\x1a\n" + chunk(b"IHDR", ihdr) + chunk(b"IDAT", zlib.compress(b"\0" * 20)) + chunk(b"IEND", b""))
     assert L.orbfe_png_read_gray(str(tmp_path / "short.png").encode(), dst.ctypes.data_as(C.c_void_p), 16, 16, C.byref(w), C.byref(h)) == -1
+
+
+def test_bench_dump_outputs_writes_the_valid_rows_exactly(tmp_path):
+    """bench.py --dump-outputs: per-frame counts whole, per-keypoint rows of a fixed, seeded frame sample (only the first n rows of a
+    frame: the rest is what earlier steps left), float32 / float64 holding every value exactly, and a refusal above the size limit."""
+    import types
+    sys.path.insert(0, ROOT)
+    import bench
+    F, cap = bench.DUMP_FRAMES + 8, 50
+    rng = np.random.default_rng(7)
+    kp = np.zeros((F, cap), KP_DTYPE)
+    for f in ("x", "y", "size", "angle", "response"):
+        kp[f] = rng.random((F, cap), dtype=np.float32) * 1000
+    kp["octave"], kp["class_id"] = rng.integers(0, 8, (F, cap)), -1
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a))
+    B = types.SimpleNamespace(kl=t(kp.view(np.uint8).reshape(F, cap, 28)), dl=t(rng.integers(0, 256, (F, cap, 32), dtype=np.uint8)),
+                              kr=t(kp[::-1].copy().view(np.uint8).reshape(F, cap, 28)), dr=t(rng.integers(0, 256, (F, cap, 32), dtype=np.uint8)),
+                              nl=t(rng.integers(0, cap + 1, F).astype(np.int32)), nr=t(rng.integers(0, cap + 1, F).astype(np.int32)),
+                              ur=t(rng.random((F, cap), dtype=np.float32)), depth=t(rng.random((F, cap), dtype=np.float32)),
+                              n_stereo=t(rng.integers(0, cap, F).astype(np.int32)), n_track=t(rng.integers(0, cap, F).astype(np.int32)),
+                              assigned=t(rng.integers(-1, cap, (F, cap)).astype(np.int32)))
+    rig = types.SimpleNamespace(cfg=bench.CONFIGS["kitti_stereo"], F=F, STEREO=True)
+    bench.write_outputs(str(tmp_path / "a"), *bench.step_outputs(rig, B))
+    bench.write_outputs(str(tmp_path / "b"), *bench.step_outputs(rig, B))
+    got = {p.stem: np.load(p) for p in (tmp_path / "a").glob("*.npy")}
+    for p in (tmp_path / "b").glob("*.npy"):
+        np.testing.assert_array_equal(np.load(p), got[p.stem])
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    frames = got["frames"].astype(int)
+    assert len(frames) == bench.DUMP_FRAMES and np.all(np.diff(frames) > 0)
+    nl = B.nl.numpy()
+    np.testing.assert_array_equal(got["n_left"], nl)
+    np.testing.assert_array_equal(got["n_tracked"], B.n_track.numpy())
+    o = 0
+    for f in frames:
+        n = nl[f]
+        for i, name in enumerate(KP_DTYPE.names):
+            np.testing.assert_array_equal(got["left_keypoints"][o:o + n, i], kp[name][f, :n])
+        np.testing.assert_array_equal(got["left_descriptors"][o:o + n], B.dl.numpy()[f, :n])
+        np.testing.assert_array_equal(got["assigned"][o:o + n], B.assigned.numpy()[f, :n])
+        np.testing.assert_array_equal(got["depth"][o:o + n], B.depth.numpy()[f, :n])
+        o += n
+    assert o == len(got["left_keypoints"]) == len(got["u_right"])
+    assert len(got["right_keypoints"]) == B.nr.numpy()[frames].sum()
+    with pytest.raises(SystemExit):
+        bench.write_outputs(str(tmp_path / "c"), np.arange(1), {}, {"big": (np.zeros((1, bench.DUMP_LIMIT // 8 + 1)), [bench.DUMP_LIMIT])})
+    assert not (tmp_path / "c").exists()

@@ -77,7 +77,7 @@ def main(tag_dir, out_prefix, config="kitti_stereo"):
     foot = ("\n`__amd_rocclr_copyBuffer` / `fillBufferAligned` and the `at::native` kernels belong to bench.py's set-up (uploading the synthetic "
             "frames, one copy per image, before the first step) and result read-back; the kernel trace of a steady-state step holds none of "
             "them (two `at::native` fills of the match buffers excepted).  Percentages are of the whole profiled process.\n")
-    cmd = "`rocprofv3 --kernel-trace --stats -- python3 bench.py --steps 10 --warmup 2 --cpu-sample 0 --e2e-steps 0 --per-frame 0 --content-steps 0"
+    cmd = "`rocprofv3 --kernel-trace --stats -- python3 bench.py --full --steps 10 --warmup 2 --cpu-sample 0 --e2e-steps 0 --per-frame 0 --content-steps 0"
     avg_us = {short(r["Name"]): float(r["AverageNs"]) / 1e3 for r in rows}
     one = glob.glob(os.path.join(tag_dir, "**", "stats1_kernel_stats.csv"), recursive=True)
     with open(out_prefix + "_kernel_stats.md", "w") as f:
@@ -108,7 +108,7 @@ def main(tag_dir, out_prefix, config="kitti_stereo"):
     cs = counters(tag_dir)
     with open(out_prefix + "_pmc_counters.md", "w") as f:
         f.write(f"# {os.path.basename(out_prefix)}: PMC counters per kernel launch (256 KITTI images / stereo frames per launch)\n\n"
-                "Separate `rocprofv3 --kernel-trace --pmc <set>` passes of `python3 bench.py --steps 3 --warmup 1 --cpu-sample 0 --e2e-steps 0 --per-frame 0 --content-steps 0` "
+                "Separate `rocprofv3 --kernel-trace --pmc <set>` passes of `python3 bench.py --full --steps 3 --warmup 1 --cpu-sample 0 --e2e-steps 0 --per-frame 0 --content-steps 0` "
                 "(tools/profile_round.sh: two SQ sets, FETCH_SIZE, WRITE_SIZE, TCC hit/miss, GRBM_GUI_ACTIVE), averaged over the later launches of "
                 "each kernel (rocprofv3 serialises kernels in counter passes); durations from the one-stream `--stats` pass of the same build.  FETCH / WRITE are KB as rocprofv3 reports them; FETCH is doubled "
                 "(x2) for kernels whose bulk reads are coalesced 16-byte-per-lane loads, which gfx950 tallies at half their bytes "
@@ -178,7 +178,7 @@ def main(tag_dir, out_prefix, config="kitti_stereo"):
     json.dump({"stage": st, "config": config, "kernel": dom, "images_per_launch": 256, "issue": issue, "fetch_kb": cs[dom].get("FETCH_SIZE", 0),
                "fetch_correction": 2.0 if wide else 1.0, "write_kb": cs[dom].get("WRITE_SIZE", 0), "avg_us_stats_pass": avg_us[dom],
                "read_kb_by_request_size": rk, "write_kb_by_request_size": wk,
-               "source": "tools/profile_round.sh: rocprofv3 --kernel-trace --pmc FETCH_SIZE / WRITE_SIZE (separate passes) -- python3 bench.py --steps 3 "
+               "source": "tools/profile_round.sh: rocprofv3 --kernel-trace --pmc FETCH_SIZE / WRITE_SIZE (separate passes) -- python3 bench.py --full --steps 3 "
                          "--warmup 1 --cpu-sample 0 --e2e-steps 0 --per-frame 0 --content-steps 0; FETCH_SIZE x 2 for 16-byte-per-lane coalesced loads on gfx950 (MI355X_MICROARCH.md, HBM section); "
                          "read / write_kb_by_request_size: TCC_EA0_RDREQ / WRREQ split by request size (passes of their own)"},
               open(out_prefix + "_pmc_dominant.json", "w"), indent=1)
