@@ -85,8 +85,19 @@ int orbfe_device_download(void* h_dst, const void* d_src, size_t bytes);
  *   projection searches at most 9 500 keypoints per frame (orbfe_search_by_projection_*, orbfe_search_local_points*,
  *                       orbfe_proj_match_batch_device, orbfe_kf_search in its LOOP / RELOC modes: the ordered resolver keeps
  *                       nine bytes per keypoint in LDS); orbfe_proj_candidates / orbfe_proj_best alone take 65 535
- *   stereo matching     (image rows / 8, rounded up) x n_levels <= 8 192 row-bucket keys, rows <= 4 095
+ *   stereo matching     (image rows / 8, rounded up) x n_levels <= 8 192 row-bucket keys, rows <= 4 095, and pyramid scale
+ *                       factors mvScaleFactor[level] <= 13 (2 x scale + 2 <= 28 rows: a keypoint's row band spans at most
+ *                       8 buckets), e.g. 16 levels at a scale factor of 1.18648 or less
  *   inv_level_sigma2    orbfe_proj_best / orbfe_kf_search read n_levels floats (the caller states n_levels)
+ *   octree node table   max(N + 3, 4 x nIni) + 1, rounded up to 64, for every level's feature quota N: at most 2 752 nodes,
+ *                       56 bytes each in the 160 KiB of LDS of the octree kernel (the table itself is sized for 8 192), so
+ *                       nFeatures <= 12 655 at 8 levels and scale factor 1.2
+ *   aspect ratio        nIni = round(width / height) of every level with FAST cells (width, height: the level less its
+ *                       16-pixel borders) in 1..256: images much taller than wide are refused (a 4095-row image at 16 levels
+ *                       and scale factor 1.18648 needs about 2 100 columns)
+ *   SearchByBoW         at most 60 000 frame features under one vocabulary node (orbfe_search_by_bow, orbfe_search_by_bow_kf)
+ * Each limit is pinned at its largest accepted and its first refused value by tests/test_limits_gpu.py (levels: also
+ * tests/test_cabi_cpu.py).
  * Threads: a handle serialises its own calls (internal mutex); different handles may be used from different threads at the same
  * time (Frame.cc:91-94 runs the two extractors on two threads).  The library holds no other mutable global state and reads no
  * environment variables.  The matcher entry points that take no handle (orbfe_search_*, orbfe_stereo_match, orbfe_kf_search,
@@ -371,7 +382,8 @@ int orbfe_track_queries_device(int n_frames, const orbfe_track_pose* d_pose, con
  * point record per keypoint going through memory.  Byte-equal to orbfe_unproject_stereo_device + orbfe_track_queries_device.
  * Frames in front of the batch (f < frame_shift): the carry frame when the five d_carry_* arrays are given (one frame: [cap]
  * keypoints / descriptors / depth, one count, one camera -- the last frame of the batch before), otherwise the batch's own tail
- * (index mod n_frames, as orbfe_track_queries_device).  d_nq[f] = keypoint count of the source frame. */
+ * (index mod n_frames, as orbfe_track_queries_device).  The carry holds one frame, so it takes frame_shift 0 or 1 only: a carry
+ * with frame_shift > 1 is ORBFE_ERR_INVALID.  d_nq[f] = keypoint count of the source frame. */
 int orbfe_track_queries_stereo_device(int n_frames, const orbfe_keypoint* d_kps, const uint8_t* d_desc, const int32_t* d_n,
                                       const float* d_depth, int cap, const orbfe_unproject_cam* d_cam, int observed,
                                       const orbfe_keypoint* d_carry_kps, const uint8_t* d_carry_desc, const int32_t* d_carry_n,

@@ -308,6 +308,10 @@ static int stage_host(orbfe_matcher* m, const orbfe_frame_view* f, const orbfe_q
 }
 
 static bool frame_ok(const orbfe_frame_view* f) {
+  if (f && f->n > 65535) {   // keypoint indices travel as 16-bit fields next to the distance
+    orbfe_set_error("frame of %d keypoints: at most 65535", f->n);
+    return false;
+  }
   return f && f->n >= 0 && (f->n == 0 || (f->keys_un && f->desc)) && f->max_x > f->min_x && f->max_y > f->min_y;
 }
 
@@ -433,6 +437,10 @@ extern "C" int orbfe_track_queries_stereo_device(int n_frames, const orbfe_keypo
   const bool carry = d_carry_kps || d_carry_desc || d_carry_n || d_carry_depth || d_carry_cam;
   if (carry && !(d_carry_kps && d_carry_desc && d_carry_n && d_carry_depth && d_carry_cam)) {
     orbfe_set_error("the carry frame needs all five arrays (keypoints, descriptors, count, depth, camera) or none");
+    return ORBFE_ERR_INVALID;
+  }
+  if (carry && frame_shift > 1) {   // the carry holds one frame: frames 0 .. frame_shift-2 would read it in place of their own source
+    orbfe_set_error("a carry frame holds one frame: frame_shift %d > 1 needs the batch's own tail (no carry)", frame_shift);
     return ORBFE_ERR_INVALID;
   }
   if (((uintptr_t)d_desc & 15) || ((uintptr_t)d_carry_desc & 15) || ((uintptr_t)d_kps & 3) || ((uintptr_t)d_carry_kps & 3) ||
@@ -563,7 +571,10 @@ static int bow_impl(const uint8_t* descA, const float* angleA, const uint8_t* va
   for (int i = 0; i < n_nodesA; i++) totA = std::max(totA, nodesA[i].start + nodesA[i].count);
   for (int i = 0; i < n_nodesB; i++) totB = std::max(totB, nodesB[i].start + nodesB[i].count);
   if (pairs.empty()) return ORBFE_OK;
-  if (maxB >= 65536 || maxB > 60000) return ORBFE_ERR_INVALID;
+  if (maxB > 60000) {
+    orbfe_set_error("a vocabulary node lists %d frame features (at most 60000)", maxB);
+    return ORBFE_ERR_INVALID;
+  }
   // nodes are independent only if no frame feature is listed under two of them (always true for DBoW2 output)
   int sequential = 0;
   {
@@ -966,7 +977,10 @@ static int stereo_enqueue(orbfe_matcher* m, orbfe_extractor* left, orbfe_extract
   p.n_buckets = (p.pyrL.h[0] + 7) / 8;
   p.n_levels = nl;
   p.n_keys = p.n_buckets * nl;
-  if (p.n_buckets > STEREO_MAX_BUCKETS || p.n_keys > STEREO_MAX_KEYS) return ORBFE_ERR_INVALID;
+  if (p.n_buckets > STEREO_MAX_BUCKETS || p.n_keys > STEREO_MAX_KEYS) {
+    orbfe_set_error("stereo match: %d row buckets x %d levels exceed %d keys", p.n_buckets, nl, STEREO_MAX_KEYS);
+    return ORBFE_ERR_INVALID;
+  }
   if ((rc = mb_alloc(m->bucket_start, sizeof(int32_t) * (size_t)n_pairs * (p.n_keys + 1)))) return rc;
   if ((rc = mb_alloc(m->bucket_idx, 16 * (size_t)n_pairs * cap * STEREO_BUCKET_SPAN))) return rc;  // int4 records
   p.bucket_start = (int32_t*)m->bucket_start.p;

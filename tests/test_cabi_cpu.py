@@ -84,6 +84,17 @@ def test_argument_validation_without_compute(L):
     assert L.orbfe_stage_intervals(None, None, None, None, None, 0, C.byref(n)) == _lib.ERR_INVALID and n.value == 7
 
 
+def test_extractor_level_limit(L):
+    """ORBFE_MAX_LEVELS: 16 levels pass validation (then need a device), 17 are refused before any device is looked for"""
+    h = C.c_void_p(None)
+    rc = L.orbfe_extractor_create(C.byref(_lib.Params(2000, 1.08, 16, 20, 7)), -1, C.byref(h))
+    assert rc == (_lib.OK if _gpu_present(L) else _lib.ERR_NO_DEVICE)
+    assert L.orbfe_extractor_destroy(h) == 0
+    h = C.c_void_p(None)
+    assert L.orbfe_extractor_create(C.byref(_lib.Params(2000, 1.08, 17, 20, 7)), -1, C.byref(h)) == _lib.ERR_INVALID and not h.value
+    assert b"invalid extractor parameters" in L.orbfe_last_error()
+
+
 def test_pipeline_handle_validates_and_has_no_cpu_fallback(L):
     """orbfe_pipeline_* (the batched stereo step behind one handle, for hosts without the HIP runtime): the config struct has the
     header's layout, a bad configuration is refused before anything touches a device, and without a device creation is an error."""

@@ -145,7 +145,7 @@ def test_proj_candidates_order_and_distances(geom):
     assert tot > len(q)  # the test exercises real windows
 
 
-@pytest.mark.parametrize("n", [1500, 9000, 20500])
+@pytest.mark.parametrize("n", [1500, 9000, 20500, 65535])
 def test_grid_of_crowded_and_large_frames(n):
     """The Frame grid (Frame.cc:250-263) from random keypoints instead of extracted ones: a quarter of them piled into two cells
     (long cell lists: the rank-based placement), some outside the image bounds (no cell), 20 500 keypoints (beyond the LDS-resident
@@ -159,6 +159,7 @@ def test_grid_of_crowded_and_large_frames(n):
     k["x"][pile] = (np.where(rng.random(pile.sum()) < 0.5, 300.0, 911.5) + rng.uniform(-6, 6, pile.sum())).astype(np.float32)
     k["y"][pile] = (150.0 + rng.uniform(-3, 3, pile.sum())).astype(np.float32)
     k["octave"] = rng.integers(0, 8, n); k["angle"] = rng.uniform(0, 360, n).astype(np.float32); k["size"] = 31; k["class_id"] = -1
+    k["x"][n - 1], k["y"][n - 1] = 620.25, 190.5
     d = _rand_desc(rng, n)
     sf = np.array([np.float32(1.2) ** i for i in range(8)], np.float32)
     fv = FrameView(k, d, 0, w, 0, h); of = ol.OracleFrame(k, d, sf, 0, w, 0, h)
@@ -170,6 +171,7 @@ def test_grid_of_crowded_and_large_frames(n):
     q["min_level"] = -1; q["max_level"] = -1
     q["min_level"][::3] = 2; q["max_level"][::3] = 5
     q["valid"] = 1; q["blocks"] = 1; q["desc"] = _rand_desc(rng, nq)
+    q["u"][1], q["v"][1], q["min_level"][1], q["max_level"][1] = k["x"][n - 1], k["y"][n - 1], -1, -1   # the last keypoint's window
     cand, cnt = ORBmatcher().ProjCandidates(fv, q, max_cand=4096)
     for i in range(nq):
         idx = of.features_in_area(float(q["u"][i]), float(q["v"][i]), float(q["radius"][i]), int(q["min_level"][i]), int(q["max_level"][i]))
@@ -177,6 +179,7 @@ def test_grid_of_crowded_and_large_frames(n):
         m_ = min(len(idx), 4096)
         np.testing.assert_array_equal(cand[i, :m_]["idx"], np.asarray(idx[:m_], np.int32), err_msg=f"query {i}")
     assert cnt.max() > 100
+    assert n - 1 in cand[1, :cnt[1]]["idx"]   # the top index (0xfffe at 65 535 keypoints) travels through the grid lists
 
 
 @pytest.mark.parametrize("geom,th", [((1241, 376, 2000), 7.0), ((640, 480, 1000), 15.0), ((640, 480, 1000), 40.0)])
