@@ -96,8 +96,11 @@ int orbfe_device_download(void* h_dst, const void* d_src, size_t bytes);
  *                       16-pixel borders) in 1..256: images much taller than wide are refused (a 4095-row image at 16 levels
  *                       and scale factor 1.18648 needs about 2 100 columns)
  *   SearchByBoW         at most 60 000 frame features under one vocabulary node (orbfe_search_by_bow, orbfe_search_by_bow_kf)
+ *   RGB-D depth maps    at most 4095 x 4095 samples (orbfe_undistort_frames_device); a keypoint whose truncated coordinates fall
+ *                       outside its frame's depth map gets no depth (mvDepth = mvuRight = -1) and nothing outside the map is read
+ *                       -- the reference would read out of bounds there; the extractor never produces such a keypoint
  * Each limit is pinned at its largest accepted and its first refused value by tests/test_limits_gpu.py (levels: also
- * tests/test_cabi_cpu.py).
+ * tests/test_cabi_cpu.py; depth maps: tests/test_frames_cpu.py and tests/test_frames_gpu.py).
  * Threads: a handle serialises its own calls (internal mutex); different handles may be used from different threads at the same
  * time (Frame.cc:91-94 runs the two extractors on two threads).  The library holds no other mutable global state and reads no
  * environment variables.  The matcher entry points that take no handle (orbfe_search_*, orbfe_stereo_match, orbfe_kf_search,
@@ -390,6 +393,54 @@ int orbfe_track_queries_stereo_device(int n_frames, const orbfe_keypoint* d_kps,
                                       const float* d_carry_depth, const orbfe_unproject_cam* d_carry_cam,
                                       const orbfe_track_pose* d_pose, int frame_shift, orbfe_query* d_queries, int32_t* d_nq,
                                       void* stream);
+
+/* ---- lens distortion, image bounds and RGB-D depth: the per-keypoint tail of Frame::Frame ------------------------------------
+ * Monocular (L/src/Frame.cc:216) and RGB-D (:157-159) frames: UndistortKeyPoints (:419-445, cv::undistortPoints with the default five
+ * iterations, R = I, P = K, in double), ComputeImageBounds (:447-476) and ComputeStereoFromRGBD (:648-666) on the depth map as
+ * Tracking::GrabImageRGBD scales it (L/src/Tracking.cc:210-211).  k1 == 0 means no undistortion at all (mvKeysUn = mvKeys, bounds
+ * (0, cols, 0, rows)), whatever k2 .. k3 hold (:420-423, :469-474).
+ * Bounds: the four floats of orbfe_image_bounds are mnMinX .. mnMaxY -- they go into EVERY min_x ... max_y the library takes
+ * (orbfe_frame_view, orbfe_proj_match_batch_device, orbfe_search_local_points_batch_device, orbfe_track_pose, orbfe_frustum,
+ * orbfe_kf_camera) for frames of that camera; with distortion they are not (0, w, 0, h), and undistorted keypoints may lie outside
+ * them (the grid then leaves them out, Frame::PosInGrid :399-410).
+ * The RGB-D motion-model step reuses two entry points unchanged: orbfe_track_queries_stereo_device fed keys_un and the depth out of
+ * orbfe_undistort_frames_device (UnprojectStereo reads mvKeysUn, :668-679; octave and angle are those of mvKeys), its
+ * orbfe_track_pose records with the undistorted bounds and th = 15 (L/src/Tracking.cc:793-798); then orbfe_proj_match_batch_device
+ * (mode 1) fed keys_un, u_right and the undistorted bounds. */
+typedef struct orbfe_calibration {
+  float fx, fy, cx, cy;          /* mK */
+  float k1, k2, p1, p2, k3;      /* mDistCoef; k3 = 0 when the settings file has none (L/src/Tracking.cc:67-77) */
+  float mbf;                     /* Camera.bf */
+  float depth_factor;            /* mDepthMapFactor: 1.0f / DepthMapFactor, or 1 when |DepthMapFactor| < 1e-5 (L/src/Tracking.cc:141-147) */
+  int32_t reserved;              /* 0 */
+} orbfe_calibration;             /* 48 bytes */
+
+/* ComputeImageBounds (L/src/Frame.cc:447-476) of a width x height image: undistorts the float corners (0,0), (cols,0), (0,rows),
+ * (cols,rows); min_x = min(c0.x, c2.x), max_x = max(c1.x, c3.x), min_y = min(c0.y, c1.y), max_y = max(c2.y, c3.y).  HOST,
+ * synchronous, needs no device.  width / height 1 .. 4095, fx and fy != 0. */
+int orbfe_image_bounds(const orbfe_calibration* cal, int width, int height, float* min_x, float* max_x, float* min_y, float* max_y);
+/* cv::undistortPoints as Frame calls it, for n host points (x, y interleaved); xy_un may equal xy.  HOST, synchronous: a
+ * calibration-time utility (bounds, a handful of points), not a fallback of the device entry below.  The same arithmetic, bit for bit. */
+int orbfe_undistort_points(const orbfe_calibration* cal, const float* xy, int n, float* xy_un);
+
+#define ORBFE_DEPTH_NONE 0   /* monocular Frame: keys_un only (d_u_right / d_depth_out / d_n_depth optional: -1, -1, 0, :219-220) */
+#define ORBFE_DEPTH_U16 1    /* raw sensor map, e.g. TUM depth PNGs: mvDepth = (float)raw * depth_factor */
+#define ORBFE_DEPTH_F32 2    /* float map: scaled by depth_factor only when fabsf(depth_factor - 1.0f) > 1e-5 */
+/* The per-keypoint tail of Frame::Frame for n_frames frames in one launch.  DEVICE pointers, asynchronous on `stream` (NULL: the
+ * NULL stream).  Frame f: keypoint rows [f*cap, f*cap + d_n[f]) of d_kps (mvKeys) -> the same rows of d_kps_un (mvKeysUn: pt
+ * undistorted, size / angle / response / octave / class_id copied), d_u_right (mvuRight) and d_depth_out (mvDepth);
+ * d_n_depth[f] = keypoints with depth (d > 0).  Frame f's depth map is at d_depth + f*depth_image_bytes, width x height samples
+ * (uint16 or float), rows depth_pitch bytes apart; ComputeStereoFromRGBD reads the sample at the TRUNCATED coordinates of the
+ * distorted keypoint, imDepth.at<float>((int)y, (int)x).  A keypoint whose truncated coordinates fall outside the map gets no depth
+ * (-1, -1) and nothing outside the map is read; the extractor never produces one.  d_kps_un may equal d_kps (in place).  Rows at and
+ * behind d_n[f] are not written; d_n[f] is clamped to [0, cap].
+ * Limits (ORBFE_ERR_INVALID): n_frames >= 0 (0: nothing is launched), cap >= 1, fx and fy != 0, a known depth_format; with depth:
+ * width / height 1 .. 4095, depth_pitch >= width samples, depth_image_bytes >= (height - 1) * depth_pitch + width samples, the map
+ * pointer, pitch and image stride multiples of the sample size.  Without a device: ORBFE_ERR_NO_DEVICE (there is no CPU path). */
+int orbfe_undistort_frames_device(int n_frames, const orbfe_keypoint* d_kps, const int32_t* d_n, int cap,
+                                  const orbfe_calibration* cal, int depth_format, const void* d_depth, int width, int height,
+                                  int depth_pitch, size_t depth_image_bytes, orbfe_keypoint* d_kps_un, float* d_u_right,
+                                  float* d_depth_out, int32_t* d_n_depth, void* stream);
 
 /* SearchByBoW(KeyFrame*, Frame&, vector<MapPoint*>&) (L/src/ORBmatcher.cc:161-273), entirely on the device.
  * A DBoW2::FeatureVector is passed as its nodes sorted by id, each {node_id, start, count} into an index array

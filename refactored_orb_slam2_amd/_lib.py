@@ -78,6 +78,16 @@ class FeatVecNode(C.Structure):
     _fields_ = [("node_id", C.c_int32), ("start", C.c_int32), ("count", C.c_int32)]
 
 
+class Calibration(C.Structure):
+    """orbfe_calibration (include/orbfe.h): mK, mDistCoef, mbf, mDepthMapFactor; 48 bytes"""
+    _fields_ = [("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float), ("k1", C.c_float), ("k2", C.c_float),
+                ("p1", C.c_float), ("p2", C.c_float), ("k3", C.c_float), ("mbf", C.c_float), ("depth_factor", C.c_float),
+                ("reserved", C.c_int32)]
+
+
+DEPTH_NONE, DEPTH_U16, DEPTH_F32 = 0, 1, 2
+
+
 class FrameView(C.Structure):
     _fields_ = [("n", C.c_int32), ("keys_un", C.c_void_p), ("desc", C.c_void_p), ("u_right", C.c_void_p),
                 ("min_x", C.c_float), ("max_x", C.c_float), ("min_y", C.c_float), ("max_y", C.c_float)]
@@ -105,6 +115,7 @@ EXPORTS = [
     "orbfe_pipeline_create", "orbfe_pipeline_destroy", "orbfe_pipeline_input", "orbfe_pipeline_submit", "orbfe_pipeline_wait",
     "orbfe_pipeline_output", "orbfe_pipeline_device_records", "orbfe_pipeline_stream", "orbfe_pipeline_gather", "orbfe_pipeline_gather_wait",
     "orbfe_pipeline_device_input", "orbfe_pipeline_submit_resident", "orbfe_debug_pipeline_streams",
+    "orbfe_image_bounds", "orbfe_undistort_points", "orbfe_undistort_frames_device",
 ]
 
 
@@ -197,6 +208,10 @@ def lib():
     L.orbfe_search_for_initialization.argtypes = [C.POINTER(FrameView), C.POINTER(FrameView), vp, ci, cf, ci, vp, pi]
     L.orbfe_stereo_match_device.argtypes = [vp, vp, vp, ci, vp, vp, vp, vp, vp, vp, ci, cf, cf, vp, vp, vp, vp]
     L.orbfe_stereo_match.argtypes = [vp, vp, vp, vp, ci, vp, vp, ci, cf, cf, vp, vp, pi]
+    pcal, pf = C.POINTER(Calibration), C.POINTER(cf)
+    L.orbfe_image_bounds.argtypes = [pcal, ci, ci, pf, pf, pf, pf]
+    L.orbfe_undistort_points.argtypes = [pcal, vp, ci, vp]
+    L.orbfe_undistort_frames_device.argtypes = [ci, vp, vp, ci, pcal, ci, vp, ci, ci, ci, sz, vp, vp, vp, vp, vp]
     for name in EXPORTS:
         if name != "orbfe_last_error":
             getattr(L, name).restype = ci
