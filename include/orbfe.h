@@ -99,8 +99,12 @@ int orbfe_device_download(void* h_dst, const void* d_src, size_t bytes);
  *   RGB-D depth maps    at most 4095 x 4095 samples (orbfe_undistort_frames_device); a keypoint whose truncated coordinates fall
  *                       outside its frame's depth map gets no depth (mvDepth = mvuRight = -1) and nothing outside the map is read
  *                       -- the reference would read out of bounds there; the extractor never produces such a keypoint
+ *   rectification       source and destination images of 1 .. 4095 pixels per side (orbfe_rectifier_create: the fixed-point map keeps
+ *                       X + 1 and Y + 1 in 13 bits each); pitches at least the widths, image strides at least (height - 1) x pitch
+ *                       + width, source and destination must not overlap (orbfe_rectify_batch_device)
  * Each limit is pinned at its largest accepted and its first refused value by tests/test_limits_gpu.py (levels: also
- * tests/test_cabi_cpu.py; depth maps: tests/test_frames_cpu.py and tests/test_frames_gpu.py).
+ * tests/test_cabi_cpu.py; depth maps: tests/test_frames_cpu.py and tests/test_frames_gpu.py; rectification:
+ * tests/test_rectify_cpu.py and tests/test_rectify_gpu.py).
  * Threads: a handle serialises its own calls (internal mutex); different handles may be used from different threads at the same
  * time (Frame.cc:91-94 runs the two extractors on two threads).  The library holds no other mutable global state and reads no
  * environment variables.  The matcher entry points that take no handle (orbfe_search_*, orbfe_stereo_match, orbfe_kf_search,
@@ -442,6 +446,52 @@ int orbfe_undistort_frames_device(int n_frames, const orbfe_keypoint* d_kps, con
                                   int depth_pitch, size_t depth_image_bytes, orbfe_keypoint* d_kps_un, float* d_u_right,
                                   float* d_depth_out, int32_t* d_n_depth, void* stream);
 
+/* ---- stereo rectification: cv::initUndistortRectifyMap + cv::remap of the EuRoC stereo driver ---------------------------------
+ * Source/Examples/Stereo/stereo_euroc.cc reads LEFT. / RIGHT. K, D, R, P from the settings file, builds two float maps per eye with
+ * cv::initUndistortRectifyMap(K, D, R, P(0:3, 0:3), size, CV_32F) (:108-111) and runs cv::remap(..., cv::INTER_LINEAR) on both images
+ * of every frame (:159-160) before TrackStereo; Frame::ComputeStereoMatches is only valid on such pairs.  A rectifier is that pair of
+ * maps for one camera, built once; orbfe_rectify_batch_device is the remap of a batch of images in HBM (csrc/rectify_kernels.hip).
+ * No OpenCV exists where this library is built and tested: the arithmetic below is this project's reading of OpenCV 4.5's scalar
+ * paths, as unpinned as the other OpenCV primitives.
+ * Maps (host, double, once per camera): A = P(0:3, 0:3) x R, each element summed over k = 0, 1, 2; ir = adjugate(A) x (1.0 / det),
+ * det expanded along the first row (det == 0: ORBFE_ERR_INVALID).  Row i starts with _x = i*ir[1] + ir[2], _y = i*ir[4] + ir[5],
+ * _w = i*ir[7] + ir[8]; column j: w = 1./_w, x = _x*w, y = _y*w, x2 = x*x, y2 = y*y, r2 = x2 + y2, _2xy = 2*x*y,
+ * kr = 1 + ((k3*r2 + k2)*r2 + k1)*r2, xd = x*kr + p1*_2xy + p2*(r2 + 2*x2), yd = y*kr + p1*(r2 + 2*y2) + p2*_2xy,
+ * map_x = (float)(fx*xd + u0), map_y = (float)(fy*yd + v0), then _x += ir[0], _y += ir[3], _w += ir[6] (running sums).
+ * D holds k1 k2 p1 p2 k3; more coefficients cannot be expressed and a skew K[0][1] != 0 is refused.
+ * Pixels (8-bit, one channel, INTER_LINEAR, BORDER_CONSTANT 0): sx = rint(map_x * 32.0f) (float product, half to even), X = sx >> 5,
+ * ax = sx & 31, likewise sy, Y, ay; a product that is not finite or not an int32 puts the pixel outside.  Taps (Y, X) (Y, X+1)
+ * (Y+1, X) (Y+1, X+1) with the weights (32-ax)(32-ay), ax(32-ay), (32-ax)ay, ax ay; a tap outside the source reads 0;
+ * out = (sum + 512) >> 10 -- OpenCV's 15-bit weight table is exactly 32 x these products, so this equals its (sum + 16384) >> 15. */
+typedef struct orbfe_rectify_camera {
+  double K[9], D[5], R[9], P[12];          /* row-major, as the settings file holds them */
+  int32_t src_width, src_height;           /* the raw image */
+  int32_t dst_width, dst_height;           /* the map / the rectified image (the reference uses the same size) */
+} orbfe_rectify_camera;
+typedef struct orbfe_rectifier orbfe_rectifier;
+/* device >= 0: the fixed-point map is uploaded to that device (orbfe_rectify_batch_device); device = -1: a host-only handle for
+ * orbfe_rectifier_maps / _coverage / orbfe_rectify_image, which needs no GPU.  Sizes 1 .. 4095 per side. */
+int orbfe_rectifier_create(const orbfe_rectify_camera* cam, int device, orbfe_rectifier** out);
+int orbfe_rectifier_destroy(orbfe_rectifier* r);
+int orbfe_rectifier_info(const orbfe_rectifier* r, orbfe_rectify_camera* cam, int* device);   /* either output may be NULL */
+/* The float maps, dst_height x dst_width each, to HOST buffers */
+int orbfe_rectifier_maps(const orbfe_rectifier* r, float* map_x, float* map_y);
+/* Destination pixels by class: inner = all four taps inside the source; outside = no tap inside (the pixel is 0); edge = the rest */
+int orbfe_rectifier_coverage(const orbfe_rectifier* r, int32_t* inner, int32_t* edge, int32_t* outside);
+/* cv::remap of ONE host image (src_height rows of src_width bytes, src_stride apart -> dst_height x dst_width, dst_stride apart).
+ * HOST, synchronous: a calibration-time and test utility, not a fallback of the device entry below.  The same arithmetic, byte for
+ * byte.  Strides at least the widths. */
+int orbfe_rectify_image(const orbfe_rectifier* r, const uint8_t* src, int src_stride, uint8_t* dst, int dst_stride);
+/* cv::remap of n_images images in one launch.  DEVICE pointers on the rectifier's device (the caller's current device),
+ * asynchronous on `stream` (NULL: the NULL stream).  Image f is read at d_src + f*src_image_bytes (rows src_pitch apart) and written
+ * at d_dst + f*dst_image_bytes (rows dst_pitch apart).  Nothing outside src_width x src_height of an image is read; only dst_width
+ * bytes of each destination row are written (padding stays untouched).  Any alignment; a destination whose pointer, pitch and image
+ * stride are multiples of 4 is written in dwords.
+ * Limits (ORBFE_ERR_INVALID): n_images >= 0 (0: nothing is launched), each pitch >= its width, each image stride >=
+ * (height - 1) * pitch + width, source and destination must not overlap.  A host-only rectifier: ORBFE_ERR_NO_DEVICE. */
+int orbfe_rectify_batch_device(orbfe_rectifier* r, const uint8_t* d_src, int n_images, int src_pitch, size_t src_image_bytes,
+                               uint8_t* d_dst, int dst_pitch, size_t dst_image_bytes, void* stream);
+
 /* SearchByBoW(KeyFrame*, Frame&, vector<MapPoint*>&) (L/src/ORBmatcher.cc:161-273), entirely on the device.
  * A DBoW2::FeatureVector is passed as its nodes sorted by id, each {node_id, start, count} into an index array
  * (nodesA/idxA = pKF->mFeatVec, nodesB/idxB = F.mFeatVec).  validA[i] != 0 <=> keyframe feature i has a map point
@@ -721,6 +771,13 @@ int orbfe_pipeline_output(orbfe_pipeline* p, int slot, orbfe_pipeline_output_vie
  * camera / pose records go host to device.  Also what a host uses to run the handle at its kernels' rate on frames uploaded once. */
 int orbfe_pipeline_device_input(orbfe_pipeline* p, int slot, uint8_t** d_left, uint8_t** d_right, int* pitch, size_t* image_bytes);
 int orbfe_pipeline_submit_resident(orbfe_pipeline* p, int slot, int n_frames, int has_predecessor);
+/* Raw (unrectified) stereo input, e.g. EuRoC: an optional rectification stage in front of the extractors.  Called after
+ * orbfe_pipeline_create and before the first submit (afterwards: ORBFE_ERR_INVALID); both rectifiers live on the handle's device and
+ * their source AND destination sizes equal the pipeline's width x height (the input slots keep their geometry).  From then on the
+ * images of orbfe_pipeline_input / orbfe_pipeline_device_input are RAW: each eye's chunk is rectified on that eye's extractor stream
+ * into a device block of its own (one more per slot and eye), which the extractor reads.  The rectifiers stay the caller's and must
+ * outlive the handle.  Without this call the handle allocates and does exactly what it does without it. */
+int orbfe_pipeline_set_rectifiers(orbfe_pipeline* p, orbfe_rectifier* left, orbfe_rectifier* right);
 /* DEVICE pointers of slot s's left records ([batch] counts -- rows behind n_frames are zero --, [batch][cap] keypoints and
  * descriptors), valid from the slot's submit until its next submit, ordered on orbfe_pipeline_stream */
 int orbfe_pipeline_device_records(orbfe_pipeline* p, int slot, const int32_t** d_n, const orbfe_keypoint** d_kps,

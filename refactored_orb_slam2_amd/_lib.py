@@ -88,6 +88,15 @@ class Calibration(C.Structure):
 DEPTH_NONE, DEPTH_U16, DEPTH_F32 = 0, 1, 2
 
 
+class RectifyCamera(C.Structure):
+    """orbfe_rectify_camera (include/orbfe.h): LEFT. / RIGHT. K, D, R, P of a stereo settings file, row-major doubles; 296 bytes"""
+    _fields_ = [("K", C.c_double * 9), ("D", C.c_double * 5), ("R", C.c_double * 9), ("P", C.c_double * 12),
+                ("src_width", C.c_int32), ("src_height", C.c_int32), ("dst_width", C.c_int32), ("dst_height", C.c_int32)]
+
+
+assert C.sizeof(RectifyCamera) == 296
+
+
 class FrameView(C.Structure):
     _fields_ = [("n", C.c_int32), ("keys_un", C.c_void_p), ("desc", C.c_void_p), ("u_right", C.c_void_p),
                 ("min_x", C.c_float), ("max_x", C.c_float), ("min_y", C.c_float), ("max_y", C.c_float)]
@@ -116,6 +125,8 @@ EXPORTS = [
     "orbfe_pipeline_output", "orbfe_pipeline_device_records", "orbfe_pipeline_stream", "orbfe_pipeline_gather", "orbfe_pipeline_gather_wait",
     "orbfe_pipeline_device_input", "orbfe_pipeline_submit_resident", "orbfe_debug_pipeline_streams",
     "orbfe_image_bounds", "orbfe_undistort_points", "orbfe_undistort_frames_device",
+    "orbfe_rectifier_create", "orbfe_rectifier_destroy", "orbfe_rectifier_info", "orbfe_rectifier_maps", "orbfe_rectifier_coverage",
+    "orbfe_rectify_image", "orbfe_rectify_batch_device", "orbfe_pipeline_set_rectifiers",
 ]
 
 
@@ -212,6 +223,15 @@ def lib():
     L.orbfe_image_bounds.argtypes = [pcal, ci, ci, pf, pf, pf, pf]
     L.orbfe_undistort_points.argtypes = [pcal, vp, ci, vp]
     L.orbfe_undistort_frames_device.argtypes = [ci, vp, vp, ci, pcal, ci, vp, ci, ci, ci, sz, vp, vp, vp, vp, vp]
+    prc, pi32 = C.POINTER(RectifyCamera), C.POINTER(C.c_int32)
+    L.orbfe_rectifier_create.argtypes = [prc, ci, C.POINTER(vp)]
+    L.orbfe_rectifier_destroy.argtypes = [vp]
+    L.orbfe_rectifier_info.argtypes = [vp, prc, pi]
+    L.orbfe_rectifier_maps.argtypes = [vp, vp, vp]
+    L.orbfe_rectifier_coverage.argtypes = [vp, pi32, pi32, pi32]
+    L.orbfe_rectify_image.argtypes = [vp, vp, ci, vp, ci]
+    L.orbfe_rectify_batch_device.argtypes = [vp, vp, ci, ci, sz, vp, ci, sz, vp]
+    L.orbfe_pipeline_set_rectifiers.argtypes = [vp, vp, vp]
     for name in EXPORTS:
         if name != "orbfe_last_error":
             getattr(L, name).restype = ci

@@ -17,7 +17,7 @@ from . import _lib
 from ._lib import DEPTH_F32, DEPTH_NONE, DEPTH_U16, Calibration
 
 __all__ = ["Calibration", "DEPTH_NONE", "DEPTH_U16", "DEPTH_F32", "calibration", "depth_factor", "image_bounds", "undistort_points",
-           "undistort_frames_batch", "read_settings"]
+           "undistort_frames_batch", "read_settings", "read_stereo_rectification"]
 
 
 def depth_factor(depth_map_factor) -> np.float32:
@@ -112,3 +112,47 @@ def read_settings(path: str) -> dict:
                       "min_th_fast": i32("ORBextractor.minThFAST")},
         "values": vals,
     }
+
+
+_MATRIX = re.compile(r"^[ \t]*([A-Za-z_][A-Za-z0-9_.]*)[ \t]*:[ \t]*!!opencv-matrix[ \t]*\n[ \t]*rows[ \t]*:[ \t]*(\d+)[ \t]*\n"
+                     r"[ \t]*cols[ \t]*:[ \t]*(\d+)[ \t]*\n[ \t]*dt[ \t]*:[ \t]*(\w+)[ \t]*\n[ \t]*data[ \t]*:[ \t]*\[([^\]]*)\]", re.M)
+_RECT_SHAPES = {"K": (3, 3), "D": (1, 5), "R": (3, 3), "P": (3, 4)}
+
+
+def read_stereo_rectification(path: str) -> dict:
+    """The rectification entries of a stereo settings file (Source/Examples/Stereo/EuRoC.yaml) without OpenCV: LEFT. / RIGHT. K, D, R,
+    P -- `!!opencv-matrix` blocks of rows, cols, dt and data (`data:[` or `data: [`, possibly over several lines) -- and LEFT. /
+    RIGHT. height / width.  Raises ValueError where the reference's driver stops with "Calibration parameters to rectify stereo are
+    missing" (Source/Examples/Stereo/stereo_euroc.cc:98-104): a matrix that is absent or empty, or a size of 0; and for a matrix of
+    another shape than 3 x 3 (K, R), 1 x 5 (D: k1 k2 p1 p2 k3, no further coefficients) and 3 x 4 (P).
+    Returns {"LEFT": {"K", "D", "R", "P": float64 arrays, "width", "height"}, "RIGHT": {...}}."""
+    with open(path) as f:
+        text = "\n".join(line.split("#", 1)[0].rstrip() for line in f.read().splitlines())
+    mats = {}
+    for m in _MATRIX.finditer(text):
+        rows, cols = int(m.group(2)), int(m.group(3))
+        data = [float(v) for v in m.group(5).replace("\n", " ").split(",") if v.strip()]
+        if len(data) != rows * cols:
+            raise ValueError(f"{path}: {m.group(1)} holds {len(data)} values for {rows} x {cols}")
+        mats[m.group(1)] = np.array(data, np.float64).reshape(rows, cols)
+    sizes = {}
+    for line in text.splitlines():
+        e = _ENTRY.match(line)
+        if e and e.group(1) in ("LEFT.height", "LEFT.width", "RIGHT.height", "RIGHT.width") and e.group(2):
+            sizes[e.group(1)] = int(round(float(e.group(2))))
+    out = {}
+    for eye in ("LEFT", "RIGHT"):
+        cam = {}
+        for name, shape in _RECT_SHAPES.items():
+            a = mats.get(f"{eye}.{name}")
+            if a is None or a.size == 0:
+                raise ValueError(f"{path}: calibration parameters to rectify stereo are missing ({eye}.{name})")
+            if a.shape != shape and not (name == "D" and a.shape == (5, 1)):
+                raise ValueError(f"{path}: {eye}.{name} is {a.shape[0]} x {a.shape[1]}, expected {shape[0]} x {shape[1]}")
+            cam[name] = a.reshape(shape)
+        for side in ("width", "height"):
+            cam[side] = sizes.get(f"{eye}.{side}", 0)
+            if cam[side] == 0:
+                raise ValueError(f"{path}: calibration parameters to rectify stereo are missing ({eye}.{side})")
+        out[eye] = cam
+    return out

@@ -87,6 +87,7 @@ struct Slot {
   orbfe_keypoint* d_kps_r = nullptr;
   uint8_t* d_desc_r = nullptr;
   uint8_t* d_blocked = nullptr;
+  uint8_t* d_rect = nullptr;   // with rectifiers: [left images | right images] rectified, what the extractors read (d_in then holds raw images)
   hipEvent_t ev_in = nullptr, ev_done = nullptr, ev_out = nullptr, ev_gather = nullptr, ev_l = nullptr, ev_r = nullptr;
   // the slot's own extractors and matcher: the matching half of a chunk reads the pyramids its extractors left in HBM (the stereo SAD
   // windows), so the NEXT chunk's extraction can only run beside it on other handles (DESIGN lesson 47)
@@ -122,6 +123,10 @@ struct orbfe_pipeline {
   size_t cy_kps = 0, cy_depth = 0, cy_cam = 0, cy_n = 0, cy_bytes = 0;
   orbfe_query* d_q = nullptr;          // [batch][cap]
   int32_t* d_nq = nullptr;             // [batch]
+  // optional rectification stage (orbfe_pipeline_set_rectifiers); the caller's handles
+  orbfe_rectifier* rect_l = nullptr;
+  orbfe_rectifier* rect_r = nullptr;
+  bool submitted = false;              // a chunk has been submitted by the caller
   std::mutex mu;
 };
 
@@ -136,7 +141,7 @@ static void pipeline_free(orbfe_pipeline* p) {
     if (s.ex_r) (void)orbfe_extractor_destroy(s.ex_r);
     if (s.h_in) (void)hipHostFree(s.h_in);
     if (s.h_out) (void)hipHostFree(s.h_out);
-    for (void* d : {(void*)s.d_in, (void*)s.d_out, (void*)s.d_kps_r, (void*)s.d_desc_r, (void*)s.d_blocked})
+    for (void* d : {(void*)s.d_in, (void*)s.d_out, (void*)s.d_kps_r, (void*)s.d_desc_r, (void*)s.d_blocked, (void*)s.d_rect})
       if (d) (void)hipFree(d);
     for (hipEvent_t e : {s.ev_in, s.ev_done, s.ev_out, s.ev_gather, s.ev_l, s.ev_r})
       if (e) (void)hipEventDestroy(e);
@@ -331,6 +336,7 @@ static int pipeline_build(orbfe_pipeline* p) {
       memset(sk.h_in + p->in_right, 0, p->image_bytes * F);
     }
     PCHK(hipMemset(p->d_carry + p->cy_n, 0, sizeof(int32_t)));   // the warm-up chunk is nobody's predecessor
+    p->submitted = false;
   }
   return ORBFE_OK;
 }
@@ -431,6 +437,7 @@ static int submit_chunk(orbfe_pipeline* p, int slot, int n, int has_predecessor,
   if (s.pending) PCHK(hipEventSynchronize(s.ev_out));   // the caller did not wait: the host block is about to be overwritten
   s.pending = true;
   s.frames = n;
+  p->submitted = true;
   // ---- copy in: behind the kernels that still read this slot's images (level 0 of their pyramids in place) and its pyramids
   PCHK(hipStreamWaitEvent(p->s_in, s.ev_done, 0));
   if (n > 0) {
@@ -466,10 +473,20 @@ static int submit_chunk(orbfe_pipeline* p, int slot, int n, int has_predecessor,
   if (n > 0) {
     const orbfe_unproject_cam* d_cams = reinterpret_cast<const orbfe_unproject_cam*>(s.d_in + p->in_cams);
     const orbfe_track_pose* d_poses = reinterpret_cast<const orbfe_track_pose*>(s.d_in + p->in_poses);
-    RCHK(orbfe_extract_batch_device(s.ex_l, s.d_in + p->in_left, n, c.width, c.height, p->pitch, p->image_bytes, d_kl, d_dl, cap,
+    const uint8_t* img_l = s.d_in + p->in_left;
+    const uint8_t* img_r = s.d_in + p->in_right;
+    if (p->rect_l) {   // raw input: each eye's chunk is rectified on its extractor's stream into the block the extractor reads
+      RCHK(orbfe_rectify_batch_device(p->rect_l, img_l, n, p->pitch, p->image_bytes, s.d_rect + p->in_left, p->pitch, p->image_bytes,
+                                      p->s_l));
+      RCHK(orbfe_rectify_batch_device(p->rect_r, img_r, n, p->pitch, p->image_bytes, s.d_rect + p->in_right, p->pitch,
+                                      p->image_bytes, p->s_r));
+      img_l = s.d_rect + p->in_left;
+      img_r = s.d_rect + p->in_right;
+    }
+    RCHK(orbfe_extract_batch_device(s.ex_l, img_l, n, c.width, c.height, p->pitch, p->image_bytes, d_kl, d_dl, cap,
                                     d_nl, p->s_l));
     PCHK(hipEventRecord(s.ev_l, p->s_l));
-    RCHK(orbfe_extract_batch_device(s.ex_r, s.d_in + p->in_right, n, c.width, c.height, p->pitch, p->image_bytes, s.d_kps_r,
+    RCHK(orbfe_extract_batch_device(s.ex_r, img_r, n, c.width, c.height, p->pitch, p->image_bytes, s.d_kps_r,
                                     s.d_desc_r, cap, d_nr, p->s_r));
     PCHK(hipEventRecord(s.ev_r, p->s_r));
     PCHK(hipStreamWaitEvent(cs, s.ev_l, 0));
@@ -547,6 +564,44 @@ extern "C" int orbfe_pipeline_submit(orbfe_pipeline* p, int slot, int n, int has
 
 extern "C" int orbfe_pipeline_submit_resident(orbfe_pipeline* p, int slot, int n, int has_predecessor) {
   return submit_chunk(p, slot, n, has_predecessor, true);
+}
+
+extern "C" int orbfe_pipeline_set_rectifiers(orbfe_pipeline* p, orbfe_rectifier* left, orbfe_rectifier* right) {
+  if (!p || !left || !right) {
+    orbfe_set_error("pipeline rectifiers: the handle and both rectifiers are required");
+    return ORBFE_ERR_INVALID;
+  }
+  std::lock_guard<std::mutex> lk(p->mu);
+  if (p->submitted || p->rect_l) {
+    orbfe_set_error("pipeline rectifiers: set them once, after orbfe_pipeline_create and before the first submit");
+    return ORBFE_ERR_INVALID;
+  }
+  for (orbfe_rectifier* r : {left, right}) {
+    orbfe_rectify_camera cam;
+    int dev = -1;
+    RCHK(orbfe_rectifier_info(r, &cam, &dev));
+    if (dev != p->device) {
+      orbfe_set_error("pipeline rectifiers: a rectifier lives on device %d, the handle on device %d", dev, p->device);
+      return ORBFE_ERR_INVALID;
+    }
+    if (cam.src_width != p->cfg.width || cam.src_height != p->cfg.height || cam.dst_width != p->cfg.width ||
+        cam.dst_height != p->cfg.height) {
+      orbfe_set_error("pipeline rectifiers: a rectifier maps %d x %d to %d x %d, the handle works on %d x %d images", cam.src_width,
+                      cam.src_height, cam.dst_width, cam.dst_height, p->cfg.width, p->cfg.height);
+      return ORBFE_ERR_INVALID;
+    }
+  }
+  PCHK(hipSetDevice(p->device));
+  // the rectified images: one more block per slot and eye, laid out like the image part of d_in; zeroed once -- the kernel writes
+  // `width` bytes per row and the padding columns stay as they are here, as they do in d_in
+  const size_t bytes = p->in_cams;
+  for (Slot& s : p->slots) {
+    if (!s.d_rect) PCHK(hipMalloc((void**)&s.d_rect, bytes));
+    PCHK(hipMemset(s.d_rect, 0, bytes));
+  }
+  p->rect_l = left;
+  p->rect_r = right;
+  return ORBFE_OK;
 }
 
 extern "C" int orbfe_pipeline_device_input(orbfe_pipeline* p, int slot, uint8_t** d_left, uint8_t** d_right, int* pitch,

@@ -93,6 +93,13 @@ class StereoPipeline:
         _lib.check(self._L.orbfe_pipeline_device_input(self._h, slot, C.byref(dl), C.byref(dr), C.byref(pitch), C.byref(ib)), "orbfe_pipeline_device_input")
         return dl.value, dr.value, pitch.value, ib.value
 
+    def set_rectifiers(self, left, right):
+        """orbfe_pipeline_set_rectifiers: from now on the slots' images are RAW and each eye's chunk is rectified on the device in front
+        of its extractor.  left / right: rectify.Rectifier objects on the handle's device whose source and destination sizes equal
+        the pipeline's; before the first submit only.  The handle keeps them alive."""
+        _lib.check(self._L.orbfe_pipeline_set_rectifiers(self._h, left.handle, right.handle), "orbfe_pipeline_set_rectifiers")
+        self._rectifiers = (left, right)
+
     def wait(self, slot: int):
         _lib.check(self._L.orbfe_pipeline_wait(self._h, slot), "orbfe_pipeline_wait")
 
