@@ -16,6 +16,11 @@ optimisation, local mapping and loop closing are out of scope.
                         (`python -m torch.distributed.run --nproc-per-node N examples/stereo_kitti.py ... --shard`), every rank
                         processes its chunk and the per-frame keypoint records are gathered with one RCCL all_gather per batch
   --dump FILE.npz       per-frame outputs (keypoints, descriptors, mvuRight, mvDepth, tracked assignments) for parity checks
+  --trajectory FILE     also run Optimizer::PoseOptimization (L/src/Optimizer.cc:233-435) on the matches of every frame -- all frames
+                        of a batch in one launch, each from the identity (its pose in the previous frame's camera) -- compose the
+                        relative motions on the host and write the camera trajectory as System::SaveTrajectoryKITTI does
+                        (L/src/System.cc:452-505): one line of 12 numbers per frame, the rows of Twc.  A frame with fewer than 10
+                        inliers keeps the identity motion and is counted.  Stereo visual odometry, no map: not with --shard.
 
 usage: stereo_kitti.py <sequence_dir> [--features 2000] [--batch 64] [--max-frames N] [--bf 386.1448 --fx 718.856 ...]
 """
@@ -69,7 +74,11 @@ def main():
     ap.add_argument("--th", type=float, default=7.0)
     ap.add_argument("--shard", action="store_true")
     ap.add_argument("--dump", default="")
+    ap.add_argument("--trajectory", default="")
     args = ap.parse_args()
+    if args.trajectory and args.shard:
+        ap.error("--trajectory composes every frame's motion with its predecessor's pose: a rank's first frame has no predecessor "
+                 "on that rank, and stitching shards is not implemented; run it without --shard")
 
     import torch
     import torch.distributed as dist
@@ -119,6 +128,14 @@ def main():
     t_cams = torch.from_numpy(cams.view(np.uint8).reshape(F, -1)).to(dev)
     t_poses = torch.from_numpy(poses.view(np.uint8).reshape(F, -1)).to(dev)
     stream = torch.cuda.Stream(dev)
+    if args.trajectory:
+        from refactored_orb_slam2_amd import optimizer
+        from refactored_orb_slam2_amd._lib import POSE_RESULT_DTYPE
+        p_cam = optimizer.pose_camera(args.fx, args.fy, args.cx, args.cy, args.bf, exL.GetInverseScaleSigmaSquares())
+        t_pcam = torch.from_numpy(p_cam.view(np.uint8).reshape(-1)).to(dev)
+        t_eye = torch.from_numpy(np.tile(np.eye(4, dtype=np.float32)[:3].reshape(12), (F, 1))).to(dev)
+        p_res, p_out = z(F, POSE_RESULT_DTYPE.itemsize), z(F, cap)
+        Twc, traj, n_lost = np.eye(4), [], 0          # T(w <- f) of the last frame, in double
     track_times, n_kp, n_st, n_tr = [], 0, 0, 0
     dump = {}
     gathered = []
@@ -147,6 +164,9 @@ def main():
                                     blocked[:B], assigned[:B], ntr[:B], stream=stream)
                 if not have_prev:   # the first frame of this rank's chunk has no predecessor
                     ntr[0] = 0; assigned[0].fill_(-1)
+                if args.trajectory:   # frame j: its pose in the camera of the frame whose points are in slot j, from the identity
+                    optimizer.pose_optimization_batch(kl[:B], ur[:B], nl[:B], assigned[:B], pts[:B], npts[:B], t_pcam, t_eye[:B],
+                                                      p_res[:B], p_out[:B], frame_shift=0, stream=stream)
             if world > 1:
                 if B < F:
                     nl[B:].zero_()   # padding frames of the last chunk carry no keypoints
@@ -156,6 +176,21 @@ def main():
         if B:
             track_times += [dt / B] * B
             n_kp += int(nl[:B].sum()); n_st += int(nst[:B].sum()); n_tr += int(ntr[:B].sum())
+            if args.trajectory:
+                res = p_res[:B].cpu().numpy().view(POSE_RESULT_DTYPE).reshape(-1)
+                for j, i in enumerate(idx):
+                    if i > 0 and int(res[j]["n_inliers"]) >= 10:      # T(w <- f) = T(w <- f-1) . T(f <- f-1)^-1
+                        Tff = np.eye(4)
+                        Tff[:3] = res[j]["Tcw"].astype(np.float64).reshape(3, 4)
+                        inv = np.eye(4)
+                        inv[:3, :3] = Tff[:3, :3].T
+                        inv[:3, 3] = -Tff[:3, :3].T @ Tff[:3, 3]
+                        Twc = Twc @ inv
+                    elif i > 0:
+                        n_lost += 1
+                    traj.append(Twc[:3].reshape(12).copy())
+                    if args.dump:
+                        dump[f"pose_{i}"] = res[j].copy(); dump[f"outlier_{i}"] = p_out[j, :int(nl[j])].cpu().numpy()
             if args.dump:
                 for j, i in enumerate(idx):
                     n = int(nl[j])
@@ -191,6 +226,11 @@ def main():
         print(f"mean tracking time: {sum(track_times) / len(track_times)}")
         print(f"frames: {n}, keypoints/left image: {n_kp / n:.1f}, stereo matches/frame: {n_st / n:.1f}, tracked/frame: {n_tr / max(n - world, 1):.1f}, "
               f"front-end frames/s of rank 0 (incl. H2D, excl. PNG decoding): {len(track_times) / sum(track_times):.1f}")
+    if args.trajectory:
+        with open(args.trajectory, "w") as f:          # f << fixed << setprecision(9): Rwc(0,:) twc(0) Rwc(1,:) twc(1) Rwc(2,:) twc(2)
+            for T in traj:
+                f.write(" ".join(f"{v:.9f}" for v in T) + "\n")
+        print(f"trajectory saved: {len(traj)} poses, {n_lost} frames with fewer than 10 inliers kept the identity motion")
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()

@@ -102,9 +102,12 @@ int orbfe_device_download(void* h_dst, const void* d_src, size_t bytes);
  *   rectification       source and destination images of 1 .. 4095 pixels per side (orbfe_rectifier_create: the fixed-point map keeps
  *                       X + 1 and Y + 1 in 13 bits each); pitches at least the widths, image strides at least (height - 1) x pitch
  *                       + width, source and destination must not overlap (orbfe_rectify_batch_device)
+ *   pose optimisation   at most 9 500 keypoint rows per frame (the frame limit of the projection searches whose output it reads),
+ *                       n_levels 1 .. ORBFE_MAX_LEVELS, point records of at least 12 bytes and a multiple of 4 bytes apart
+ *                       (orbfe_pose_optimization, orbfe_pose_optimization_batch_device)
  * Each limit is pinned at its largest accepted and its first refused value by tests/test_limits_gpu.py (levels: also
  * tests/test_cabi_cpu.py; depth maps: tests/test_frames_cpu.py and tests/test_frames_gpu.py; rectification:
- * tests/test_rectify_cpu.py and tests/test_rectify_gpu.py).
+ * tests/test_rectify_cpu.py and tests/test_rectify_gpu.py; pose optimisation: tests/test_pose_cpu.py).
  * Threads: a handle serialises its own calls (internal mutex); different handles may be used from different threads at the same
  * time (Frame.cc:91-94 runs the two extractors on two threads).  The library holds no other mutable global state and reads no
  * environment variables.  The matcher entry points that take no handle (orbfe_search_*, orbfe_stereo_match, orbfe_kf_search,
@@ -491,6 +494,61 @@ int orbfe_rectify_image(const orbfe_rectifier* r, const uint8_t* src, int src_st
  * (height - 1) * pitch + width, source and destination must not overlap.  A host-only rectifier: ORBFE_ERR_NO_DEVICE. */
 int orbfe_rectify_batch_device(orbfe_rectifier* r, const uint8_t* d_src, int n_images, int src_pitch, size_t src_image_bytes,
                                uint8_t* d_dst, int dst_pitch, size_t dst_image_bytes, void* stream);
+
+/* ---- Optimizer::PoseOptimization (L/src/Optimizer.cc:233-435) on the device ----------------------------------------------------
+ * What every tracked frame runs after its projection search (Tracking::TrackWithMotionModel L/src/Tracking.cc:798-830,
+ * TrackLocalMap :845-866, TrackReferenceKeyFrame, Relocalization): one 6-DoF vertex, one unary edge per keypoint with a map point --
+ * monocular when mvuRight[i] < 0 (2-D error, Huber delta (float)sqrt(5.991), chi2 bound (float)5.991), stereo otherwise (3-D error,
+ * (float)sqrt(7.815), (float)7.815), information mvInvLevelSigma2[octave] x I -- four rounds of g2o's Levenberg optimize(10), each
+ * from the input pose, edges re-classified after every round, the robust kernels removed after the third, one round only with fewer
+ * than 10 edges, nothing at all with fewer than 3.  csrc/pose_internal.h states the arithmetic (all double) line by line; neither
+ * Eigen nor g2o exists where this library is built and tested, so it is this project's reading of their source, unpinned (DESIGN
+ * section 2), checked against an independent numpy reading (tests/np_pose.py) to one float ulp of the pose and equal flags.
+ * One deliberate deviation: after a round every edge is classified by its chi2 at that round's final pose; the reference reads, for
+ * an edge that was active, the error of the last Levenberg trial even when that trial was rejected (a difference near 1e-10).
+ * Deterministic: a frame's result does not depend on the run, on its position in the batch or on the batch size. */
+typedef struct orbfe_pose_camera {       /* what the edges read of the Frame */
+  float fx, fy, cx, cy, mbf;
+  int32_t n_levels;                      /* 1 .. ORBFE_MAX_LEVELS */
+  float inv_level_sigma2[ORBFE_MAX_LEVELS]; /* mvInvLevelSigma2 */
+} orbfe_pose_camera;                     /* 88 bytes */
+typedef struct orbfe_pose_result {
+  float Tcw[12];                         /* rows of [R | t] after SetPose; the input pose when n_initial < 3 */
+  int32_t n_initial, n_bad, n_inliers;   /* nInitialCorrespondences, nBad, the return value */
+  int32_t rounds, iterations;            /* rounds run (1 or 4; 0 when n_initial < 3), Levenberg iterations over all rounds */
+} orbfe_pose_result;                     /* 68 bytes */
+#define ORBFE_POSE_DISCARD 1   /* also Tracking.cc:815-826: assigned[idx] = -1 and outlier[idx] = 0 for every outlier */
+/* One frame, the per-frame call of Tracking.  HOST pointers, synchronous, on the calling thread's current device; runs the kernel
+ * of the batch form (no CPU fallback: ORBFE_ERR_NO_DEVICE without a device).  frame: n, keys_un and u_right (NULL: every edge is
+ * monocular) are read, desc is not.  assigned[idx] >= 0 <=> mvpMapPoints[idx] != NULL, its value an index into the n_points records
+ * at `points`, point_stride bytes apart, whose first three floats are GetWorldPos() (orbfe_map_point: 72, orbfe_last_point: 60, or
+ * bare positions: 12).  Tcw_in: 12 floats, the rows of [R | t] of mTcw.  outlier[idx] (mvbOutlier) is written for every idx < n:
+ * 0 where there is no point (the reference leaves those entries untouched).
+ * A row whose assigned value is >= n_points or whose octave is outside [0, n_levels) is no edge: nothing is read for it and it is
+ * counted nowhere.  z == 0 of a point in the camera frame is not specified.
+ * Limits (ORBFE_ERR_INVALID): 0 <= n <= 9 500 (the frame limit of the projection searches), n_points >= 0, n_levels 1 ..
+ * ORBFE_MAX_LEVELS, point_stride >= 12 and a multiple of 4, no null pointer except u_right (and keys_un / assigned / points /
+ * outlier when their count is 0). */
+int orbfe_pose_optimization(const orbfe_frame_view* frame, const int32_t* assigned, const void* points, int point_stride,
+                            int n_points, const orbfe_pose_camera* camera, const float* Tcw_in, orbfe_pose_result* result,
+                            uint8_t* outlier);
+/* n_frames frames in one launch, one workgroup per frame.  DEVICE pointers, asynchronous on `stream` (NULL: the NULL stream).
+ * Frame f owns keypoint rows [f*cap, f*cap + d_n[f]) of d_keys_un / d_u_right (nullable: all monocular) / d_assigned / d_outlier;
+ * assigned values index the point records of frame (f - frame_shift) mod n_frames, d_points + that frame * p_cap * point_stride,
+ * of which d_n_points[that frame] exist -- the convention of orbfe_track_queries_device, so the d_assigned of
+ * orbfe_proj_match_batch_device (mode 0 and 1) and of orbfe_search_local_points_batch_device feeds this call unchanged.  d_camera:
+ * ONE record for the batch; d_Tcw_in [n_frames][12]; d_result [n_frames]; d_outlier [n_frames][cap].  d_n[f] is clamped to
+ * [0, cap], d_n_points to [0, p_cap]; rows at and behind d_n[f] are neither read nor written.
+ * flags: 0 or ORBFE_POSE_DISCARD (d_assigned is written only then; the counts in d_result are those before the discard).
+ * Limits (ORBFE_ERR_INVALID): n_frames >= 0 (0: nothing is launched), 1 <= cap <= 9 500, p_cap >= 1, frame_shift >= 0,
+ * point_stride >= 12 and a multiple of 4, unknown flag bits, null pointers other than d_u_right, records not 4-byte aligned.
+ * n_levels lives in device memory and is not validated here: the kernel clamps nothing but treats an octave outside
+ * [0, min(n_levels, ORBFE_MAX_LEVELS)) as no edge. */
+int orbfe_pose_optimization_batch_device(int n_frames, const orbfe_keypoint* d_keys_un, const float* d_u_right, const int32_t* d_n,
+                                         int cap, int32_t* d_assigned, const void* d_points, int point_stride,
+                                         const int32_t* d_n_points, int p_cap, int frame_shift, const orbfe_pose_camera* d_camera,
+                                         const float* d_Tcw_in, orbfe_pose_result* d_result, uint8_t* d_outlier, int flags,
+                                         void* stream);
 
 /* SearchByBoW(KeyFrame*, Frame&, vector<MapPoint*>&) (L/src/ORBmatcher.cc:161-273), entirely on the device.
  * A DBoW2::FeatureVector is passed as its nodes sorted by id, each {node_id, start, count} into an index array

@@ -86,6 +86,14 @@ class Calibration(C.Structure):
 
 
 DEPTH_NONE, DEPTH_U16, DEPTH_F32 = 0, 1, 2
+# orbfe_pose_camera / orbfe_pose_result (Optimizer::PoseOptimization, include/orbfe.h)
+POSE_CAMERA_DTYPE = np.dtype([("fx", "<f4"), ("fy", "<f4"), ("cx", "<f4"), ("cy", "<f4"), ("mbf", "<f4"), ("n_levels", "<i4"),
+                              ("inv_level_sigma2", "<f4", (16,))])
+POSE_RESULT_DTYPE = np.dtype([("Tcw", "<f4", (12,)), ("n_initial", "<i4"), ("n_bad", "<i4"), ("n_inliers", "<i4"), ("rounds", "<i4"),
+                              ("iterations", "<i4")])
+assert POSE_CAMERA_DTYPE.itemsize == 88 and POSE_RESULT_DTYPE.itemsize == 68
+POSE_DISCARD = 1
+POSE_MAX_ROWS = 9500
 
 
 class RectifyCamera(C.Structure):
@@ -127,6 +135,7 @@ EXPORTS = [
     "orbfe_image_bounds", "orbfe_undistort_points", "orbfe_undistort_frames_device",
     "orbfe_rectifier_create", "orbfe_rectifier_destroy", "orbfe_rectifier_info", "orbfe_rectifier_maps", "orbfe_rectifier_coverage",
     "orbfe_rectify_image", "orbfe_rectify_batch_device", "orbfe_pipeline_set_rectifiers",
+    "orbfe_pose_optimization", "orbfe_pose_optimization_batch_device",
 ]
 
 
@@ -232,6 +241,8 @@ def lib():
     L.orbfe_rectify_image.argtypes = [vp, vp, ci, vp, ci]
     L.orbfe_rectify_batch_device.argtypes = [vp, vp, ci, ci, sz, vp, ci, sz, vp]
     L.orbfe_pipeline_set_rectifiers.argtypes = [vp, vp, vp]
+    L.orbfe_pose_optimization.argtypes = [C.POINTER(FrameView), vp, vp, ci, ci, vp, vp, vp, vp]
+    L.orbfe_pose_optimization_batch_device.argtypes = [ci, vp, vp, vp, ci, vp, vp, ci, vp, ci, ci, vp, vp, vp, vp, ci, vp]
     for name in EXPORTS:
         if name != "orbfe_last_error":
             getattr(L, name).restype = ci

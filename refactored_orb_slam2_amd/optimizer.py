@@ -1,0 +1,69 @@
+"""Optimizer::PoseOptimization over the C ABI of liborbfe.so (L/src/Optimizer.cc:233-435, L/ = Source/Libraries/ORB_SLAM2/): the
+pose of a frame from its keypoint <-> map-point pairs, and which pairs were wrong.
+
+pose_optimization is the per-frame call of Tracking on host arrays; pose_optimization_batch optimises every frame of a batch in one
+launch on device tensors (pose_kernels.hip, one workgroup per frame) and reads the `assigned` array of the batched projection
+searches unchanged.  Both run the same kernel; there is no CPU path.
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from . import _lib
+from ._lib import POSE_CAMERA_DTYPE, POSE_DISCARD, POSE_RESULT_DTYPE
+
+__all__ = ["POSE_CAMERA_DTYPE", "POSE_RESULT_DTYPE", "POSE_DISCARD", "pose_camera", "pose_optimization", "pose_optimization_batch"]
+
+
+def pose_camera(fx, fy, cx, cy, mbf, inv_level_sigma2) -> np.ndarray:
+    """One orbfe_pose_camera record: the Frame's fx, fy, cx, cy, mbf and mvInvLevelSigma2 (its length is n_levels)."""
+    sig = np.asarray(inv_level_sigma2, np.float32).reshape(-1)
+    cam = np.zeros(1, POSE_CAMERA_DTYPE)
+    cam["fx"], cam["fy"], cam["cx"], cam["cy"], cam["mbf"] = fx, fy, cx, cy, mbf
+    cam["n_levels"] = len(sig)
+    cam["inv_level_sigma2"][0, :min(len(sig), _lib.MAX_LEVELS)] = sig[:_lib.MAX_LEVELS]
+    return cam
+
+
+def pose_optimization(keys_un, u_right, assigned, points, camera, Tcw):
+    """Optimizer::PoseOptimization of one frame.  keys_un: KP_DTYPE (n) = mvKeysUn; u_right: (n) float32 = mvuRight or None (every
+    edge monocular); assigned: (n) int32, >= 0 <=> mvpMapPoints[i] != NULL, an index into points; points: a structured array whose
+    first three floats are the world position (MAP_POINT_DTYPE, LAST_POINT_DTYPE) or an (m, 3) float32 array; camera: pose_camera(...);
+    Tcw: 12 or 3 x 4 / 4 x 4 floats.  Returns (result, outlier): one POSE_RESULT_DTYPE record and mvbOutlier as (n) uint8."""
+    keys_un = np.ascontiguousarray(keys_un, _lib.KP_DTYPE)
+    n = len(keys_un)
+    ur = None if u_right is None else np.ascontiguousarray(u_right, np.float32)
+    assigned = np.ascontiguousarray(assigned, np.int32)
+    if len(assigned) != n or (ur is not None and len(ur) != n):
+        raise ValueError("keys_un, u_right and assigned must have one entry per keypoint")
+    points = np.ascontiguousarray(points)
+    if points.dtype.fields is None:
+        points = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+        stride = 12
+    else:
+        stride = points.dtype.itemsize
+    T = np.ascontiguousarray(np.asarray(Tcw, np.float32).reshape(-1)[:12])
+    cam = np.ascontiguousarray(camera, POSE_CAMERA_DTYPE).reshape(1)
+    fv = _lib.FrameView(n, keys_un.ctypes.data if n else None, None, ur.ctypes.data if ur is not None and n else None, 0, 0, 0, 0)
+    res = np.zeros(1, POSE_RESULT_DTYPE)
+    outlier = np.zeros(n, np.uint8)
+    _lib.check(_lib.lib().orbfe_pose_optimization(C.byref(fv), _lib.ptr(assigned), _lib.ptr(points), stride, len(points), _lib.ptr(cam),
+                                                  _lib.ptr(T), _lib.ptr(res), _lib.ptr(outlier)), "orbfe_pose_optimization")
+    return res[0], outlier
+
+
+def pose_optimization_batch(keys_un, u_right, n, assigned, points, n_points, camera, Tcw_in, result, outlier, frame_shift: int = 0,
+                            flags: int = 0, stream=None):
+    """orbfe_pose_optimization_batch_device on torch CUDA tensors: keys_un (F,cap,28) u8, u_right (F,cap) f32 or None, n (F) i32,
+    assigned (F,cap) i32 (written only with POSE_DISCARD), points (F,p_cap,stride) u8 whose records start with the position, n_points
+    (F) i32, camera (88) u8 = one POSE_CAMERA_DTYPE record, Tcw_in (F,12) f32, result (F,68) u8 = POSE_RESULT_DTYPE, outlier (F,cap) u8.
+    The points of frame f are those of frame (f - frame_shift) mod F.  stream: a torch.cuda.Stream, or None for the NULL stream."""
+    F, cap = int(keys_un.shape[0]), int(keys_un.shape[1])
+    p_cap, stride = int(points.shape[1]), int(points.shape[2])
+    _lib.check(_lib.lib().orbfe_pose_optimization_batch_device(F, _lib.ptr(keys_un), _lib.ptr(u_right), _lib.ptr(n), cap,
+                                                               _lib.ptr(assigned), _lib.ptr(points), stride, _lib.ptr(n_points), p_cap,
+                                                               int(frame_shift), _lib.ptr(camera), _lib.ptr(Tcw_in), _lib.ptr(result),
+                                                               _lib.ptr(outlier), int(flags), _lib.stream_handle(stream)),
+               "orbfe_pose_optimization_batch_device")
