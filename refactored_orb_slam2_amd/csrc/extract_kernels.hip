@@ -2396,11 +2396,18 @@ __device__ __forceinline__ void patch_store16(uint8_t* base, int r, int c, const
 #define PATCH_BYTES (2 * OD_BUF)                           // 4736
 // lane l's 16 bytes land at lds_dst + 16 l: the windows' LDS images are exactly that order -- raw patch 31 rows x 3 pieces at pitch 48,
 // blurred patch 37 rows x 4 pieces at pitch 64 or x 3 pieces at pitch 48 (piece i = row * pieces + column at byte 16 i).  The compiler
-// does not count these loads: every wait for them is an explicit s_waitcnt vmcnt below.  M0 (the destination) is saved and restored.
-#define OD_DMA(gsrc, lds_dst) do { \
-    unsigned keep_m0; \
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0" \
-                 : "=&s"(keep_m0) : "v"(gsrc), "s"(lds_dst) : "memory"); \
+// does not count these loads: every wait for them is an explicit s_waitcnt vmcnt below.
+// The address is a 32-bit byte offset per lane on a wave-uniform 64-bit plane address (no 64-bit vector add per piece).  M0 is
+// written and not restored -- the compiler keeps nothing in M0 in this kernel (tests/test_describe_isa.py reads the listing for that) --
+// and, in the second form, only the lanes of `mask` requesting: EXEC is narrowed around the load, without a branch.  The padding
+// gives the five wait states a plane address fresh from v_readlane needs before a memory instruction reads it (the M0 write and the
+// EXEC write count as one each; the M0 write needs one before the load).
+#define OD_DMA_S(voff, sbase, lds_dst) \
+    asm volatile("s_mov_b32 m0, %2\n\ts_nop 3\n\tglobal_load_lds_dwordx4 %0, %1" : : "v"(voff), "s"(sbase), "s"(lds_dst) : "memory")
+#define OD_DMA_SM(voff, sbase, lds_dst, mask) do { \
+    unsigned long long keep_exec; \
+    asm volatile("s_mov_b32 m0, %3\n\ts_nop 2\n\ts_and_saveexec_b64 %0, %4\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b64 exec, %0" \
+                 : "=&s"(keep_exec) : "v"(voff), "s"(sbase), "s"(lds_dst), "s"(mask) : "memory", "scc"); \
   } while (0)
 #else
 #define PATCH_BYTES ((ORI_BYTES + 37 * DSC_PITCH + 15) & ~15)  // 3856
@@ -2415,8 +2422,10 @@ __device__ __forceinline__ void patch_store16(uint8_t* base, int r, int c, const
 // (a, b) read from lane k.  The moments use v_dot4_i32_i8: a lane owns four (row, 4-column) items of the disc, the per-item
 // weights (u and v as signed bytes, 0 outside the disc; a host-filled table) stay in registers for all eight keypoints, and the
 // pixels enter as I - 128 (one xor per dword).  The disc is symmetric, sum u = sum v = 0, so sum u (I - 128) = sum u I = m10
-// exactly -- integer, hence the same moments as the reference's loops -- and no sum of I is needed: two wave reductions per
-// keypoint instead of three.
+// exactly -- integer, hence the same moments as the reference's loops -- and no sum of I is needed: two sums per keypoint instead
+// of three, folded to eight-lane groups per keypoint and finished for all eight keypoints together (profiles/r07_describe.md).
+// Nothing a loop iteration needs of its keypoint is looked up in it: lane k resolves slot k's planes, window origins and LDS
+// geometry once per wave, and the loops read them with v_readlane (DESIGN lesson 60).
 #ifndef OD_K
 #define OD_K 8
 #ifndef OD_DSC_NARROW
@@ -2429,6 +2438,12 @@ __device__ __forceinline__ void patch_store16(uint8_t* base, int r, int c, const
 #ifndef OD_FAKE_TABLES
 #define OD_FAKE_TABLES 0
 #endif
+#ifndef OD_SCAN6
+#define OD_SCAN6 0
+#endif
+#ifndef OD_BOUND
+#define OD_BOUND 0   // timing experiment only (wrong results; never run the tests on it): every keypoint's windows are taken from the level-0
+#endif               // planes (in bounds for any level's coordinates) and the moment sums are not reduced -- profiles/r07_describe.md
 #if FC_TIMING
 __device__ unsigned long long g_od_prof[4096 * 8];
 extern "C" int orbfe_debug_od_profile(unsigned long long* out, int reset) {
@@ -2497,6 +2512,12 @@ __global__ __launch_bounds__(256, OD_WGS) void orient_describe8_kernel(DescribeP
 
   // slot bookkeeping, lane k for slot s0 + k: level, position, score and output index (-1 = no keypoint in this slot)
   int i_out = -1, i_level = 0, i_cx = 0, i_cy = 0, i_score = 0;
+#if OD_DMA_STAGE
+  unsigned long long pl_rbase, pl_bbase;   // this image's raw / blurred plane of that level
+  int pl_rpitch, pl_bpitch;
+  uint32_t pl_rtiled;
+  float pl_scale, pl_size;
+#endif
   {
     const int slot = s0 + lane;
     int level = 0, off_level = 0;
@@ -2505,6 +2526,19 @@ __global__ __launch_bounds__(256, OD_WGS) void orient_describe8_kernel(DescribeP
       level += ge ? 1 : 0;
       off_level = ge ? P.kp_off[l] : off_level;
     }
+#if OD_DMA_STAGE
+    // Plane lookup, once per wave: lane k fetches what slot k's two windows and its keypoint record need of its level -- vector loads
+    // from the kernel-argument segment, requested with the batch above.  The loops below read them with v_readlane: no scalar load,
+    // no wait for one and no 64-bit image multiply per keypoint (they were redone for every window, sixteen times per wave).
+    const int lq = OD_BOUND ? 0 : level;
+    pl_rbase = reinterpret_cast<unsigned long long>(P.pyr.base[lq]) + (unsigned long long)img * P.pyr.img_stride[lq];
+    pl_bbase = reinterpret_cast<unsigned long long>(P.blur.base[lq]) + (unsigned long long)img * P.blur.img_stride[lq];
+    pl_rpitch = P.pyr.pitch[lq];
+    pl_bpitch = P.blur.pitch[lq];
+    pl_rtiled = (P.pyr.tiled >> lq) & 1u;
+    pl_scale = P.scale[level];
+    pl_size = P.kp_size[level];
+#endif
     const int idx = slot - off_level;
     int out = idx, ln_level = 0;
     for (int l = 0; l < P.n_levels; l++) {
@@ -2579,41 +2613,70 @@ __global__ __launch_bounds__(256, OD_WGS) void orient_describe8_kernel(DescribeP
 #endif
   };
 #endif
+  const int k_first = __ffs((int)valid_mask) - 1;
+#if !OD_DMA_STAGE
   // next valid slot after k (OD_K if none)
   auto next_valid = [&](int k) { const unsigned m = valid_mask >> (k + 1); return m ? k + 1 + (__ffs((int)m) - 1) : OD_K; };
-  const int k_first = __ffs((int)valid_mask) - 1;
+#endif
 
 #if OD_DMA_STAGE
+  // Everything a window request needs of its keypoint is wave-uniform, so lane k works it out for slot k here, eight slots at the
+  // price of one, and the loops fetch it with v_readlane.
+  //   raw window: pieces (row r, 16-byte column c) at  base + (y >> 3) * mA + (y & 7) * mB + c * cs,  y = cy - 15 + r,  one form for both
+  //   storages -- tiled (16 x 8-pixel tiles of 128 bytes): mA = 128 * tiles per tile row, mB = 16, cs = 128; row-major: mA = 8 * pitch,
+  //   mB = pitch, cs = 16 -- with the window's first column already in the base.
+  //   blurred window (always tiled): base + (y >> 3) * mA + (y & 7) * 16 + x16 * 128, y and x16 clamped at 0 (the window may begin two
+  //   rows above and one piece left of the plane; those bytes are never sampled).
+  const uint32_t r_mA = pl_rtiled ? (uint32_t)(pl_rpitch >> 4) << 7 : (uint32_t)pl_rpitch << 3;
+  const uint32_t r_mB = pl_rtiled ? 16u : (uint32_t)pl_rpitch;
+  const uint32_t r_cs = pl_rtiled ? 128u : 16u;
+  const unsigned long long r_base = pl_rbase + (unsigned long long)((uint32_t)((i_cx - 15) >> 4) * r_cs);
+  const int r_blo = (int)(uint32_t)r_base, r_bhi = (int)(uint32_t)(r_base >> 32);
+  const int r_y0 = i_cy - 15;
+  const int r_m = (i_cx - 15) & 15;   // the window's first column inside its first piece
+  const int b_lo = (int)(uint32_t)pl_bbase, b_hi = (int)(uint32_t)(pl_bbase >> 32);
+  const uint32_t b_mA = (uint32_t)(pl_bpitch >> 4) << 7;
+  const int b_x16 = (i_cx - 18) >> 4, b_y0 = i_cy - 18;
+  const int b_wide = ((i_cx - 18) & 15) > 11 ? 1 : 0;   // 37 columns from there need a fourth piece
+  // lane -> (row, piece) of a window of three pieces per row (rounds 0 and 1) and of four (row + 16 per round)
+  const int rN0 = (lane * 43) >> 7, cN0 = lane - 3 * rN0;                  // i / 3, i % 3 for i < 128
+  const int rN1 = ((lane + WAVE) * 43) >> 7, cN1 = lane + WAVE - 3 * rN1;
+  const int rW = lane >> 2, cW = lane & 3;
+#define OD_RL(v, k) __builtin_amdgcn_readlane((v), (k))
+#define OD_RL64(lo, hi, k) (((unsigned long long)(uint32_t)OD_RL(hi, k) << 32) | (unsigned long long)(uint32_t)OD_RL(lo, k))
+  const uint32_t lds_buf = (uint32_t)(uintptr_t)&patch[wv_id][0];
   // ---- phase 1: moments of the keypoints, keypoint k's in lane k.  The window of keypoint k + 1 travels global -> LDS (the other
   // buffer) while k's is summed: no staging registers, no LDS store instructions, no wait between a load's arrival and its store.
-  const uint32_t lds_buf = (uint32_t)(uintptr_t)&patch[wv_id][0];
-  auto dma_ori = [&](int k, uint32_t lds) {
-    const int level = __builtin_amdgcn_readlane(i_level, k), cx = __builtin_amdgcn_readlane(i_cx, k), cy = __builtin_amdgcn_readlane(i_cy, k);
-    const int pitch = P.pyr.pitch[level];
-    const uint8_t* plane = P.pyr.base[level] + (size_t)img * P.pyr.img_stride[level];
-    const bool tiled = (P.pyr.tiled >> level) & 1u;
-    const int ax_o = (cx - 15) & ~15;
-#pragma unroll
-    for (int j = 0; j < 2; j++) {
-      const int i = lane + WAVE * j;
-      const int r = (i * 43) >> 7, c = i - 3 * r;   // i / 3, i % 3 for i < 128
-      if (i < 31 * 3) OD_DMA(plane + orbfe_level_offset(ax_o + 16 * c, cy - 15 + r, pitch, tiled), lds + 1024u * j);
-    }
+  auto dma_ori = [&](int k, uint32_t lds) {   // 31 x 3 pieces: one full round, 29 lanes of a second
+    const unsigned long long base = OD_RL64(r_blo, r_bhi, k);
+    const uint32_t mA = (uint32_t)OD_RL((int)r_mA, k), mB = (uint32_t)OD_RL((int)r_mB, k), cs = (uint32_t)OD_RL((int)r_cs, k);
+    const int y0 = OD_RL(r_y0, k);
+    const uint32_t ya = (uint32_t)(y0 + rN0), yb = (uint32_t)(y0 + rN1);
+    const uint32_t oa = __umul24(ya >> 3, mA) + __umul24(ya & 7u, mB) + __umul24((uint32_t)cN0, cs);
+    const uint32_t ob = __umul24(yb >> 3, mA) + __umul24(yb & 7u, mB) + __umul24((uint32_t)cN1, cs);
+    OD_DMA_S(oa, base, lds);
+    OD_DMA_SM(ob, base, lds + 1024u, (1ull << (31 * 3 - WAVE)) - 1ull);
   };
-  int m10v = 0, m01v = 0;
+  // The moment sums, batched: a keypoint's 64 lane-local partial sums are only folded to one per group of eight lanes (three
+  // v_add_dpp per sum; every step leaves all lanes of the group holding the group's total) and lane 8 g + k keeps group g's total of
+  // keypoint k.  The eight keypoints' groups are added up together behind the loop.  (A six-step scan and a v_readlane per sum, twice
+  // per keypoint, were 28 instructions that produced one value each.)  Integer sums: the same integers in any order.
+  int accA = 0, accB = 0;
   {
-    // every load the compiler knows of (pattern, weights, slot records) has arrived before the first window is requested: it does not
-    // see the LDS-DMA loads, and would otherwise wait for "its" loads inside the loops below -- with a count that also drains the
+    // every load the compiler knows of (pattern, weights, slot records, plane constants) has arrived before the loop: it does not see
+    // the LDS-DMA loads, and would otherwise wait for "its" loads inside the loops below -- with a count that also drains the
     // window that was just requested (s_waitcnt vmcnt(0), expcnt / lgkmcnt untouched)
-    // (the first window is requested in front of that wait: its latency passes together with the tables')
     dma_ori(k_first, lds_buf);
     __builtin_amdgcn_s_waitcnt(0x0F70);
+    unsigned rem = valid_mask & (valid_mask - 1u);   // the slots behind k
     uint32_t par = 0;
-    for (int k = k_first; k < OD_K; k = next_valid(k), par ^= 1u) {
-      const int kn = next_valid(k);
+    for (int k = k_first;; par ^= 1u) {
+      const int kn = __builtin_ctz(rem | (1u << OD_K));   // the next slot that holds a keypoint (OD_K: none)
+      const bool more = kn < OD_K;
+      rem &= rem - 1u;
       // (the buffer the next window lands in was last read two keypoints ago; those reads were consumed before that iteration ended.
       //  Three buffers with the windows of k + 1 AND k + 2 in flight: 0.269 ms against 0.262 -- more requests in flight are not faster)
-      if (kn < OD_K) {
+      if (more) {
         dma_ori(kn, lds_buf + (par ^ 1u) * OD_BUF);
         asm volatile("s_waitcnt vmcnt(2)" ::: "memory");   // everything older than the two loads just issued: this keypoint's window
       } else {
@@ -2621,8 +2684,7 @@ __global__ __launch_bounds__(256, OD_WGS) void orient_describe8_kernel(DescribeP
       }
       FC_T(1);   // wait for the raw patch
       const uint8_t* ob = &patch[wv_id][0] + par * OD_BUF;
-      const int cx = __builtin_amdgcn_readlane(i_cx, k);
-      const int m = (cx - 15) & 15;
+      const int m = OD_RL(r_m, k);
       int A = 0, B = 0;
       const uint32_t sh = (uint32_t)(m & 3);
 #pragma unroll
@@ -2635,113 +2697,139 @@ __global__ __launch_bounds__(256, OD_WGS) void orient_describe8_kernel(DescribeP
         A = __builtin_amdgcn_sdot4(px, (int)wu[j], A, false);
         B = __builtin_amdgcn_sdot4(px, (int)wv[j], B, false);
       }
-      const int At = __builtin_amdgcn_readlane(wave_incl_scan(A), 63), Bt = __builtin_amdgcn_readlane(wave_incl_scan(B), 63);
-      if (lane == k) { m10v = At; m01v = Bt; }
+#if OD_SCAN6   // timing experiment only (wrong angles): the two full scans per keypoint of rounds 2-6 in this kernel
+      A = __builtin_amdgcn_readlane(wave_incl_scan(A), 63);
+      B = __builtin_amdgcn_readlane(wave_incl_scan(B), 63);
+#elif !OD_BOUND
+      A += __builtin_amdgcn_update_dpp(0, A, 0xB1, 0xf, 0xf, false);    // quad_perm:[1,0,3,2]
+      B += __builtin_amdgcn_update_dpp(0, B, 0xB1, 0xf, 0xf, false);
+      A += __builtin_amdgcn_update_dpp(0, A, 0x4E, 0xf, 0xf, false);    // quad_perm:[2,3,0,1]: every lane holds its quad's sum
+      B += __builtin_amdgcn_update_dpp(0, B, 0x4E, 0xf, 0xf, false);
+      A += __builtin_amdgcn_update_dpp(0, A, 0x141, 0xf, 0xf, false);   // row_half_mirror: a lane of the group's other quad
+      B += __builtin_amdgcn_update_dpp(0, B, 0x141, 0xf, 0xf, false);
+#endif
+      const bool mine = (lane & 7) == k;
+      accA = mine ? A : accA;
+      accB = mine ? B : accB;
       FC_T(2);   // moments
+      if (!more) break;
+      k = kn;
     }
   }
   // ---- phase 2: lane k computes keypoint k's angle and rotation; the first blurred patch is already on its way
-  auto dsc_wide = [&](int k) { return ((__builtin_amdgcn_readlane(i_cx, k) - 18) & 15) > 11; };
-  auto dma_dsc = [&](int k, uint32_t lds) {
-    const int level = __builtin_amdgcn_readlane(i_level, k), cx = __builtin_amdgcn_readlane(i_cx, k), cy = __builtin_amdgcn_readlane(i_cy, k);
-    const int bpitch = P.blur.pitch[level];
-    const uint8_t* bplane = P.blur.base[level] + (size_t)img * P.blur.img_stride[level];
-    const int ax_d = (cx - 18) & ~15;
-    // 37 x 3 pieces (two rounds) where the window's 37 columns end inside the third 16-byte piece, 37 x 4 (three) otherwise
-    const bool wide = ((cx - 18) & 15) > 11;
-    const int n_pieces = wide ? 37 * 4 : 37 * 3;
-#pragma unroll
-    for (int j = 0; j < 3; j++) {
-      const int i = lane + WAVE * j;
-      const int q3 = (i * 43) >> 7;
-      const int r = wide ? (i >> 2) : q3, c = wide ? (i & 3) : i - 3 * q3;
-      if (j < 2 || wide)   // (wave-uniform: the third round exists only for the wide window)
-        if (i < n_pieces) OD_DMA(bplane + blur_tiled_offset(max(ax_d + 16 * c, 0), max(cy - 18 + r, 0), bpitch), lds + 1024u * j);
+  auto dma_dsc = [&](int k, uint32_t lds, bool wide) {
+    // 37 x 3 pieces (one round and 47 lanes) where the window's 37 columns end inside the third 16-byte piece, 37 x 4 (two rounds and 20
+    // lanes) otherwise.  One code path for the first two rounds: the lane -> (row, piece) map is selected by the wave-uniform flag
+    const unsigned long long base = OD_RL64(b_lo, b_hi, k);
+    const uint32_t mA = (uint32_t)OD_RL((int)b_mA, k);
+    const int x16 = OD_RL(b_x16, k), y0 = OD_RL(b_y0, k);
+    const uint32_t xc = (uint32_t)max(x16 + (wide ? cW : cN0), 0), xd = (uint32_t)max(x16 + (wide ? cW : cN1), 0);
+    const uint32_t ya = (uint32_t)max(y0 + (wide ? rW : rN0), 0), yb = (uint32_t)max(y0 + (wide ? rW + 16 : rN1), 0);
+    const uint32_t oa = __umul24(ya >> 3, mA) + ((ya & 7u) << 4) + (xc << 7);
+    const uint32_t ob = __umul24(yb >> 3, mA) + ((yb & 7u) << 4) + (xd << 7);
+    OD_DMA_S(oa, base, lds);
+    OD_DMA_SM(ob, base, lds + 1024u, wide ? ~0ull : (1ull << (37 * 3 - WAVE)) - 1ull);
+    if (wide) {   // (wave-uniform: the third round exists only for the wide window)
+      const uint32_t ye = (uint32_t)max(y0 + rW + 32, 0);
+      const uint32_t oe = __umul24(ye >> 3, mA) + ((ye & 7u) << 4) + (xc << 7);
+      OD_DMA_SM(oe, base, lds + 2048u, (1ull << (37 * 4 - 2 * WAVE)) - 1ull);
     }
   };
-  dma_dsc(k_first, lds_buf);
+  bool wide_k = OD_RL(b_wide, k_first) != 0;
+  dma_dsc(k_first, lds_buf, wide_k);
+  // the four row groups of a keypoint's eight-lane totals: the other group of the row, then the other rows (through the LDS crossbar,
+  // no LDS memory).  Once per wave, for all eight keypoints and both sums
+  accA += __builtin_amdgcn_update_dpp(0, accA, 0x128, 0xf, 0xf, false);   // row_ror:8
+  accB += __builtin_amdgcn_update_dpp(0, accB, 0x128, 0xf, 0xf, false);
+  accA += __builtin_amdgcn_ds_bpermute((lane ^ 16) << 2, accA);
+  accB += __builtin_amdgcn_ds_bpermute((lane ^ 16) << 2, accB);
+  accA += __builtin_amdgcn_ds_bpermute((lane ^ 32) << 2, accA);
+  accB += __builtin_amdgcn_ds_bpermute((lane ^ 32) << 2, accB);
+  const int m10v = accA, m01v = accB;   // lane k (and every lane 8 g + k): keypoint k's moments
   const float angle_v = fast_atan2_deg((float)m01v, (float)m10v);
   const float factorPI = (float)(3.1415926535897932384626433832795 / 180.f);
   float a_v, b_v;
   glibc_sincosf(angle_v * factorPI, &b_v, &a_v);
+  // the keypoint record: lane k writes keypoint k's seven words here, not seven lanes behind every descriptor (a switch over the lane
+  // and two scalar loads per keypoint)
+  if (i_out >= 0) {
+    float fx = (float)i_cx, fy = (float)i_cy;
+    if (i_level != 0) {
+      fx *= pl_scale;
+      fy *= pl_scale;
+    }
+    uint32_t* o = reinterpret_cast<uint32_t*>(P.out_kps + (size_t)img * P.cap + i_out);
+    o[0] = __float_as_uint(fx);
+    o[1] = __float_as_uint(fy);
+    o[2] = __float_as_uint(pl_size);
+    o[3] = __float_as_uint(angle_v);
+    o[4] = __float_as_uint((float)i_score);
+    o[5] = (uint32_t)i_level;
+    o[6] = 0xFFFFFFFFu;
+  }
+  // the descriptor's address and the window's LDS geometry, lane k for keypoint k.
+  // cvRound of the rotated coordinates (L/src/ORBextractor.cc:119-121) by the magic-number addition: v + 1.5 * 2^23 rounds |v| < 2^22
+  // to nearest-even in the mantissa's low bits -- one v_add_f32 where v_rndne_f32 + v_cvt_i32_f32 were two.  The integers are never
+  // separated from the magic word: its low 24 bits are 2^22 + v, so v_mad_u32_u24 gives (2^22 + ry) * PITCH + (M + rx), the patch index
+  // plus a constant that goes into the wave-uniform base.  PITCH, 64 for the wide window and 48 for the narrow one, is an operand of
+  // that one instruction: one code path for both.
+  const uint32_t MB = 0x4B400000u;   // the magic number's bit pattern
+  const uint32_t d_pitch = b_wide ? 64u : 48u;
+  const uint32_t d_bc = 18u * d_pitch + 18u + (uint32_t)((i_cx - 18) & 15) - ((1u << 22) * d_pitch + MB);
+  const unsigned long long d_out = ((unsigned long long)img * (unsigned)P.cap + (unsigned)max(i_out, 0)) * 32ull;   // byte offset in out_desc
+  const int d_olo = (int)(uint32_t)d_out, d_ohi = (int)(uint32_t)(d_out >> 32);
   FC_T(3);   // angle, sin / cos
   // ---- phase 3: steered BRIEF on the blurred level
   {
+    const float MAGIC = 12582912.0f;
+    const uint32_t sel0 = lane == 0 ? ~0u : 0u, sel1 = lane == 1 ? ~0u : 0u, sel2 = lane == 2 ? ~0u : 0u, sel3 = lane == 3 ? ~0u : 0u;
+    unsigned rem = valid_mask & (valid_mask - 1u);
     uint32_t par = 0;
-    for (int k = k_first; k < OD_K; k = next_valid(k), par ^= 1u) {
-      const int level = __builtin_amdgcn_readlane(i_level, k), cx = __builtin_amdgcn_readlane(i_cx, k), cy = __builtin_amdgcn_readlane(i_cy, k);
-      const int out = __builtin_amdgcn_readlane(i_out, k), score = __builtin_amdgcn_readlane(i_score, k);
-      const float a = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(a_v), k)), b = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(b_v), k)),
-                  angle = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(angle_v), k));
-      const int ax_d = (cx - 18) & ~15;
-      const bool wide = ((cx - 18) & 15) > 11;
-      const int kn = next_valid(k);
-      // the queue holds, oldest first: this keypoint's window, the previous keypoint's two stores, then the loads issued here
-      if (kn < OD_K) {
-        dma_dsc(kn, lds_buf + (par ^ 1u) * OD_BUF);
-        if (dsc_wide(kn)) asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
+    for (int k = k_first;; par ^= 1u) {
+      const int kn = __builtin_ctz(rem | (1u << OD_K));   // the next slot that holds a keypoint (OD_K: none)
+      const bool more = kn < OD_K;
+      rem &= rem - 1u;
+      const float a = __int_as_float(OD_RL(__float_as_int(a_v), k)), b = __int_as_float(OD_RL(__float_as_int(b_v), k));
+      const uint32_t pitch = wide_k ? 64u : 48u;
+      // the queue holds, oldest first: this keypoint's window, the previous keypoint's descriptor store, then the loads issued here
+      if (more) {
+        wide_k = OD_RL(b_wide, kn) != 0;
+        dma_dsc(kn, lds_buf + (par ^ 1u) * OD_BUF, wide_k);
+        if (wide_k) asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
         else asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
       } else {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       }
       FC_T(4);   // wait for the blurred patch
       const uint8_t* dsc = &patch[wv_id][0] + par * OD_BUF;
-      // cvRound of the rotated coordinates (L/src/ORBextractor.cc:119-121) by the magic-number addition: v + 1.5 * 2^23 rounds |v| < 2^22
-      // to nearest-even in the mantissa's low bits -- one v_add_f32 where v_rndne_f32 + v_cvt_i32_f32 were two.  The integers are never
-      // separated from the magic word: in 32-bit wrap-around arithmetic (M + ry) * PITCH + (M + rx) is the patch index plus a constant
-      // that goes into the wave-uniform base.  PITCH is 64 for the wide window and 48 for the narrow one (3 * 16: a shift-add more).
-      const float MAGIC = 12582912.0f;
-      const uint32_t MB = 0x4B400000u;   // its bit pattern
-      const uint32_t pitch = wide ? 64u : 48u;
-      const uint32_t bc0 = 18u * pitch + (uint32_t)(cx - ax_d) - (MB * pitch + MB);
-      uint8_t* dout = P.out_desc + ((size_t)img * P.cap + out) * 32;
+      const uint32_t bc0 = (uint32_t)OD_RL((int)d_bc, k);
+      uint2* dout = reinterpret_cast<uint2*>(P.out_desc + OD_RL64(d_olo, d_ohi, k));
+      // all eight samples requested before the first comparison, and the 32 descriptor bytes stored by lanes 0 .. 3 in one instruction
       int t0[4], t1[4];
-      if (wide) {
 #pragma unroll
-        for (int r = 0; r < 4; r++) {
-          const float x0 = pk[r].x, y0 = pk[r].y, x1 = pk[r].z, y1 = pk[r].w;
-          const uint32_t ry0 = __float_as_uint((x0 * b + y0 * a) + MAGIC), rx0 = __float_as_uint((x0 * a - y0 * b) + MAGIC);
-          const uint32_t ry1 = __float_as_uint((x1 * b + y1 * a) + MAGIC), rx1 = __float_as_uint((x1 * a - y1 * b) + MAGIC);
-          t0[r] = dsc[bc0 + ry0 * 64u + rx0];
-          t1[r] = dsc[bc0 + ry1 * 64u + rx1];
-        }
-      } else {
-#pragma unroll
-        for (int r = 0; r < 4; r++) {
-          const float x0 = pk[r].x, y0 = pk[r].y, x1 = pk[r].z, y1 = pk[r].w;
-          const uint32_t ry0 = __float_as_uint((x0 * b + y0 * a) + MAGIC), rx0 = __float_as_uint((x0 * a - y0 * b) + MAGIC);
-          const uint32_t ry1 = __float_as_uint((x1 * b + y1 * a) + MAGIC), rx1 = __float_as_uint((x1 * a - y1 * b) + MAGIC);
-          t0[r] = dsc[bc0 + ry0 * 48u + rx0];
-          t1[r] = dsc[bc0 + ry1 * 48u + rx1];
-        }
+      for (int r = 0; r < 4; r++) {
+        const float x0 = pk[r].x, y0 = pk[r].y, x1 = pk[r].z, y1 = pk[r].w;
+        const uint32_t ry0 = __float_as_uint((x0 * b + y0 * a) + MAGIC), rx0 = __float_as_uint((x0 * a - y0 * b) + MAGIC);
+        const uint32_t ry1 = __float_as_uint((x1 * b + y1 * a) + MAGIC), rx1 = __float_as_uint((x1 * a - y1 * b) + MAGIC);
+        t0[r] = dsc[bc0 + __umul24(ry0, pitch) + rx0];
+        t1[r] = dsc[bc0 + __umul24(ry1, pitch) + rx1];
       }
       {
         const unsigned long long b0 = __ballot(t0[0] < t1[0]), b1 = __ballot(t0[1] < t1[1]), b2 = __ballot(t0[2] < t1[2]), b3 = __ballot(t0[3] < t1[3]);
-        const unsigned long long mine = lane == 0 ? b0 : lane == 1 ? b1 : lane == 2 ? b2 : b3;
-        if (lane < 4) reinterpret_cast<unsigned long long*>(dout)[lane] = mine;
+        // ballot r into lane r with per-lane masks (v_and_or_b32 on the scalar ballots): a conditional expression over the lane became
+        // branches around vector moves
+        uint2 mine;
+        mine.x = ((uint32_t)b0 & sel0) | ((uint32_t)b1 & sel1) | ((uint32_t)b2 & sel2) | ((uint32_t)b3 & sel3);
+        mine.y = ((uint32_t)(b0 >> 32) & sel0) | ((uint32_t)(b1 >> 32) & sel1) | ((uint32_t)(b2 >> 32) & sel2) | ((uint32_t)(b3 >> 32) & sel3);
+        if (lane < 4) dout[lane] = mine;
       }
-      {
-        float fx = (float)cx, fy = (float)cy;
-        if (level != 0) {
-          fx *= P.scale[level];
-          fy *= P.scale[level];
-        }
-        uint32_t wvv;
-        switch (lane) {
-          case 0: wvv = __float_as_uint(fx); break;
-          case 1: wvv = __float_as_uint(fy); break;
-          case 2: wvv = __float_as_uint(P.kp_size[level]); break;
-          case 3: wvv = __float_as_uint(angle); break;
-          case 4: wvv = __float_as_uint((float)score); break;
-          case 5: wvv = (uint32_t)level; break;
-          default: wvv = 0xFFFFFFFFu; break;
-        }
-        // (every keypoint issues exactly these two stores: the wait above counts on it)
-        if (lane < 7) reinterpret_cast<uint32_t*>(P.out_kps + (size_t)img * P.cap + out)[lane] = wvv;
-      }
-      FC_T(5);   // BRIEF + stores
+      FC_T(5);   // BRIEF + store
+      if (!more) break;
+      k = kn;
     }
   }
+#undef OD_RL
+#undef OD_RL64
 #else
   // ---- phase 1: moments of the keypoints, keypoint k's in lane k.
   // The loads of keypoint k + 1 are in flight while k is summed.  (Requesting the raw patches of TWO keypoints with three load instructions
