@@ -105,6 +105,9 @@ int orbfe_device_download(void* h_dst, const void* d_src, size_t bytes);
  *   pose optimisation   at most 9 500 keypoint rows per frame (the frame limit of the projection searches whose output it reads),
  *                       n_levels 1 .. ORBFE_MAX_LEVELS, point records of at least 12 bytes and a multiple of 4 bytes apart
  *                       (orbfe_pose_optimization, orbfe_pose_optimization_batch_device)
+ *   new map points      at most 65 535 keypoints per keyframe (orbfe_triangulate_matches*, orbfe_create_new_map_points: the descriptor
+ *                       limit of SearchForTriangulation), at most 65 535 pairs per batch launch, n_levels 1 .. ORBFE_MAX_LEVELS
+ *                       (pinned by tests/test_mapping_cpu.py)
  * Each limit is pinned at its largest accepted and its first refused value by tests/test_limits_gpu.py (levels: also
  * tests/test_cabi_cpu.py; depth maps: tests/test_frames_cpu.py and tests/test_frames_gpu.py; rectification:
  * tests/test_rectify_cpu.py and tests/test_rectify_gpu.py; pose optimisation: tests/test_pose_cpu.py).
@@ -651,6 +654,100 @@ int orbfe_search_for_triangulation(const orbfe_keypoint* keysA, const uint8_t* d
                                    const float* u_rightB, const uint8_t* has_mpB, int nB, const orbfe_featvec_node* nodesB,
                                    int n_nodesB, const int32_t* idxB, const orbfe_epipolar* ep, int only_stereo,
                                    int check_orientation, int32_t* matchA, int* n_matches);
+
+/* ---- LocalMapping::CreateNewMapPoints (L/src/LocalMapping.cc:185-423) -----------------------------------------------------------
+ * The loop body behind SearchForTriangulation, per match (idx1, idx2) of a (pKF1, pKF2) pair (:261-402): parallax of the two rays,
+ * stereo parallax, the choice between linear triangulation / UnprojectStereo(idx1) / UnprojectStereo(idx2) / reject, and the gates
+ * in the reference's order and precision.  For an accepted pair the record also holds what MapPoint::UpdateNormalAndDepth
+ * (L/src/MapPoint.cc:340-381) yields for the new point with exactly these two observations and pKF1 as reference keyframe, so it
+ * fills an orbfe_map_point / orbfe_kf_point directly.  What stays with the caller is what the reference interleaves: new MapPoint,
+ * AddObservation, AddMapPoint, ComputeDistinctiveDescriptors, mlpRecentAddedMapPoints.
+ * csrc/mapping_internal.h states the arithmetic once (cv::Mat expressions as frustum_kernels.hip reads them, `cos` / `atan2` the
+ * float overloads).  The 4x4 decomposition of the linear path is this project's own one-sided Jacobi in double on the float matrix
+ * (cv::SVD is not available where this library is built); UnprojectStereo reads the UNDISTORTED keypoint
+ * (the reference reads mvKeys, equal for rectified stereo and for the undistorted input this library produces).
+ * Deterministic: no atomics, a row's record depends on that row's inputs only.  No CPU fallback (ORBFE_ERR_NO_DEVICE). */
+typedef struct orbfe_tri_view {        /* what the loop reads of one KeyFrame */
+  float Rcw[9], tcw[3], Ow[3];         /* GetRotation() row-major, GetTranslation(), GetCameraCenter() */
+  float fx, fy, cx, cy, invfx, invfy, mb, mbf;
+  int32_t n_levels;                    /* mnScaleLevels, 1 .. ORBFE_MAX_LEVELS */
+  float scale_factors[ORBFE_MAX_LEVELS]; /* mvScaleFactors; slot 1 is read as mfScaleFactor (ratioFactor, :210) whatever n_levels is */
+  float level_sigma2[ORBFE_MAX_LEVELS];  /* mvLevelSigma2 */
+} orbfe_tri_view;                      /* 224 bytes */
+enum {                                 /* orbfe_new_point.code: 0 accepted, else the first `continue` the pair takes */
+  ORBFE_TRI_OK = 0,
+  ORBFE_TRI_NO_MATCH = 1,              /* matchA[i] < 0 or >= nB, or an octave outside [0, n_levels) of its view: nothing more is read */
+  ORBFE_TRI_W_ZERO = 2,                /* :311  the homogeneous coordinate of the linear solution is 0 */
+  ORBFE_TRI_LOW_PARALLAX = 3,          /* :322  no stereo and very low parallax (also: a stereo keypoint with depth <= 0) */
+  ORBFE_TRI_BEHIND1 = 4,               /* :328  z1 <= 0 */
+  ORBFE_TRI_BEHIND2 = 5,               /* :332  z2 <= 0 */
+  ORBFE_TRI_REPROJ1 = 6,               /* :346 / :355  reprojection error in pKF1 (5.991 mono, 7.8 stereo, compared in double) */
+  ORBFE_TRI_REPROJ2 = 7,               /* :370 / :379  in pKF2 (its right-image term uses pKF1's mbf, as :374 does) */
+  ORBFE_TRI_DIST_ZERO = 8,             /* :391 */
+  ORBFE_TRI_SCALE = 9                  /* :400  scale consistency */
+};
+enum { ORBFE_TRI_PATH_NONE = 0, ORBFE_TRI_PATH_LINEAR = 1, ORBFE_TRI_PATH_UNPROJECT1 = 2, ORBFE_TRI_PATH_UNPROJECT2 = 3 };
+typedef struct orbfe_new_point {
+  float pos[3], normal[3];             /* x3D; mNormalVector.  All eight floats are 0 unless code == 0 */
+  float min_distance, max_distance;    /* mfMinDistance, mfMaxDistance (un-scaled, see orbfe_map_point) */
+  int32_t idx2;                        /* the pKF2 feature, -1 for ORBFE_TRI_NO_MATCH */
+  int32_t code;                        /* ORBFE_TRI_* */
+  int32_t path;                        /* ORBFE_TRI_PATH_*: how x3D was (or would have been) obtained */
+} orbfe_new_point;                     /* 44 bytes */
+/* One (pKF1, pKF2) pair, geometry only.  HOST pointers, synchronous, on the calling thread's current device.  keys = mvKeysUn,
+ * u_right = mvuRight and depth = mvDepth of both keyframes (u_right and depth NULL together: every keypoint monocular), matchA[i] =
+ * the pKF2 feature matched to pKF1 feature i or -1 (the output of orbfe_search_for_triangulation).  out[i] for every i < nA,
+ * *n_new = the number of accepted rows.
+ * Limits (ORBFE_ERR_INVALID): 0 <= nA, nB <= 65 535 (the descriptor limit of the search), n_levels of both views in 1 ..
+ * ORBFE_MAX_LEVELS, u_right without depth, null pointers other than u_right / depth (keys / matchA / out may be NULL when their
+ * count is 0).  nA == 0 launches nothing. */
+int orbfe_triangulate_matches(const orbfe_tri_view* view1, const orbfe_keypoint* keys1, const float* u_right1, const float* depth1,
+                              int nA, const orbfe_tri_view* view2, const orbfe_keypoint* keys2, const float* u_right2,
+                              const float* depth2, int nB, const int32_t* matchA, orbfe_new_point* out, int* n_new);
+/* The same for K independent pairs (pKF1, neighbour k) in one launch.  DEVICE pointers, asynchronous on `stream` (NULL: the NULL
+ * stream).  pKF1: ONE view and one block of capA keypoint rows; pair k reads its first d_nA[k] rows, its matches d_matchA rows
+ * [k*capA, k*capA + d_nA[k]) and writes the same rows of d_out; neighbour k is d_view2[k] and rows [k*capB, k*capB + d_nB[k]) of
+ * d_keys2 / d_u_right2 / d_depth2.  d_nA[k] is clamped to [0, capA], d_nB[k] to [0, capB]; rows at and behind d_nA[k] are neither
+ * read nor written.  d_n_new[k] = accepted rows of pair k.  A pair's records do not depend on K or on its position in the batch.
+ * Limits (ORBFE_ERR_INVALID): 0 <= K <= 65 535 (0: nothing is launched), 1 <= capA, capB <= 65 535, u_right without depth, null
+ * pointers other than d_u_right* / d_depth*, records not 4-byte aligned.  n_levels lives in device memory and is not validated
+ * here: an octave outside [0, min(n_levels, ORBFE_MAX_LEVELS)) makes the row ORBFE_TRI_NO_MATCH. */
+int orbfe_triangulate_matches_batch_device(int K, const orbfe_tri_view* d_view1, const orbfe_keypoint* d_keys1, const float* d_u_right1,
+                                           const float* d_depth1, const int32_t* d_nA, int capA, const orbfe_tri_view* d_view2,
+                                           const orbfe_keypoint* d_keys2, const float* d_u_right2, const float* d_depth2,
+                                           const int32_t* d_nB, int capB, const int32_t* d_matchA, orbfe_new_point* d_out,
+                                           int32_t* d_n_new, void* stream);
+/* The loop of :215-422 for pKF1 and K neighbours in covisibility order: per neighbour the baseline gate (:221-235), the search of
+ * orbfe_search_for_triangulation and the triangulation, back to back on one stream.  pKF1 is uploaded once, its candidate mask
+ * stays on the device and the triangulation clears it at every accepted feature, so neighbour k+1's search skips what neighbour k
+ * gave a map point (ORBmatcher.cc:655-664); nothing synchronises with the host between neighbours and everything comes back in
+ * one copy.  A neighbour record is side B of orbfe_search_for_triangulation plus depth, its view, its epipolar record (F12 and the
+ * epipole stay the caller's) and, for the monocular gate, ComputeSceneMedianDepth(2). */
+typedef struct orbfe_tri_neighbor {
+  const orbfe_keypoint* keys;          /* pKF2->mvKeysUn */
+  const uint8_t* desc;                 /* mDescriptors */
+  const float* u_right;                /* mvuRight, NULL: monocular */
+  const float* depth;                  /* mvDepth, NULL with u_right */
+  const uint8_t* has_mp;               /* GetMapPoint(i) != NULL */
+  const orbfe_featvec_node* nodes;     /* mFeatVec */
+  const int32_t* idx;
+  int32_t n, n_nodes;
+  orbfe_tri_view view;
+  orbfe_epipolar ep;
+  float median_depth;                  /* read when monocular != 0 */
+} orbfe_tri_neighbor;                  /* 464 bytes (LP64) */
+/* HOST pointers, synchronous.  has_mpA is in/out: accepted features are set.  monocular = mbMonocular selects the gate: 0 skips a
+ * neighbour with baseline < its mb, else one with baseline / median_depth < 0.01 (compared in double).  only_stereo is the search's
+ * bOnlyStereo (false in the reference), check_orientation the matcher's.  The sequential replay of the search (a pKF1 feature listed
+ * under two vocabulary nodes) keeps its meaning per neighbour.  The reference's early exit on CheckNewKeyFrames(): pass fewer
+ * neighbours.  points[k*nA + i] = the record of pKF1 feature i with neighbour k (all ORBFE_TRI_NO_MATCH for a skipped one),
+ * n_matches[k] = the search's return value or -1 for a neighbour the gate skipped, n_new[k] = accepted points.
+ * Limits (ORBFE_ERR_INVALID): as orbfe_triangulate_matches for nA, every neighbours[k].n and the views; K >= 0 (0: nothing is
+ * launched); node counts >= 0; the FeatureVector checks of orbfe_search_for_triangulation. */
+int orbfe_create_new_map_points(const orbfe_keypoint* keysA, const uint8_t* descA, const float* u_rightA, const float* depthA,
+                                uint8_t* has_mpA, int nA, const orbfe_featvec_node* nodesA, int n_nodesA, const int32_t* idxA,
+                                const orbfe_tri_view* viewA, const orbfe_tri_neighbor* neighbors, int K, int monocular,
+                                int only_stereo, int check_orientation, orbfe_new_point* points, int32_t* n_matches, int32_t* n_new);
 
 /* SearchForInitialization (L/src/ORBmatcher.cc:388-492), the monocular map-initialisation matcher: level-0
  * keypoints of F1 are searched in a window of `window_size` pixels around prev_matched_xy[2*i..2*i+1] in F2; a

@@ -94,6 +94,20 @@ POSE_RESULT_DTYPE = np.dtype([("Tcw", "<f4", (12,)), ("n_initial", "<i4"), ("n_b
 assert POSE_CAMERA_DTYPE.itemsize == 88 and POSE_RESULT_DTYPE.itemsize == 68
 POSE_DISCARD = 1
 POSE_MAX_ROWS = 9500
+# orbfe_tri_view / orbfe_new_point / orbfe_tri_neighbor (LocalMapping::CreateNewMapPoints, include/orbfe.h)
+TRI_VIEW_DTYPE = np.dtype([("Rcw", "<f4", (9,)), ("tcw", "<f4", (3,)), ("Ow", "<f4", (3,)), ("fx", "<f4"), ("fy", "<f4"), ("cx", "<f4"),
+                           ("cy", "<f4"), ("invfx", "<f4"), ("invfy", "<f4"), ("mb", "<f4"), ("mbf", "<f4"), ("n_levels", "<i4"),
+                           ("scale_factors", "<f4", (16,)), ("level_sigma2", "<f4", (16,))])
+NEW_POINT_DTYPE = np.dtype([("pos", "<f4", (3,)), ("normal", "<f4", (3,)), ("min_distance", "<f4"), ("max_distance", "<f4"),
+                            ("idx2", "<i4"), ("code", "<i4"), ("path", "<i4")])
+TRI_NEIGHBOR_DTYPE = np.dtype([("keys", "<u8"), ("desc", "<u8"), ("u_right", "<u8"), ("depth", "<u8"), ("has_mp", "<u8"), ("nodes", "<u8"),
+                               ("idx", "<u8"), ("n", "<i4"), ("n_nodes", "<i4"), ("view", TRI_VIEW_DTYPE), ("ep", EPIPOLAR_DTYPE),
+                               ("median_depth", "<f4")])
+assert TRI_VIEW_DTYPE.itemsize == 224 and NEW_POINT_DTYPE.itemsize == 44 and TRI_NEIGHBOR_DTYPE.itemsize == 464
+(TRI_OK, TRI_NO_MATCH, TRI_W_ZERO, TRI_LOW_PARALLAX, TRI_BEHIND1, TRI_BEHIND2, TRI_REPROJ1, TRI_REPROJ2, TRI_DIST_ZERO,
+ TRI_SCALE) = range(10)
+TRI_PATH_NONE, TRI_PATH_LINEAR, TRI_PATH_UNPROJECT1, TRI_PATH_UNPROJECT2 = range(4)
+TRI_MAX_ROWS = 65535
 
 
 class RectifyCamera(C.Structure):
@@ -136,6 +150,7 @@ EXPORTS = [
     "orbfe_rectifier_create", "orbfe_rectifier_destroy", "orbfe_rectifier_info", "orbfe_rectifier_maps", "orbfe_rectifier_coverage",
     "orbfe_rectify_image", "orbfe_rectify_batch_device", "orbfe_pipeline_set_rectifiers",
     "orbfe_pose_optimization", "orbfe_pose_optimization_batch_device",
+    "orbfe_triangulate_matches", "orbfe_triangulate_matches_batch_device", "orbfe_create_new_map_points",
 ]
 
 
@@ -243,6 +258,9 @@ def lib():
     L.orbfe_pipeline_set_rectifiers.argtypes = [vp, vp, vp]
     L.orbfe_pose_optimization.argtypes = [C.POINTER(FrameView), vp, vp, ci, ci, vp, vp, vp, vp]
     L.orbfe_pose_optimization_batch_device.argtypes = [ci, vp, vp, vp, ci, vp, vp, ci, vp, ci, ci, vp, vp, vp, vp, ci, vp]
+    L.orbfe_triangulate_matches.argtypes = [vp, vp, vp, vp, ci, vp, vp, vp, vp, ci, vp, vp, pi]
+    L.orbfe_triangulate_matches_batch_device.argtypes = [ci, vp, vp, vp, vp, vp, ci, vp, vp, vp, vp, vp, ci, vp, vp, vp, vp]
+    L.orbfe_create_new_map_points.argtypes = [vp, vp, vp, vp, vp, ci, vp, ci, vp, vp, vp, ci, ci, ci, ci, vp, vp, vp]
     for name in EXPORTS:
         if name != "orbfe_last_error":
             getattr(L, name).restype = ci

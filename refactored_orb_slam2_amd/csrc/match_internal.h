@@ -1,5 +1,8 @@
 // match_internal.h -- structs shared by matcher.cpp and match_kernels.hip
 #pragma once
+#include <mutex>
+#include <vector>
+
 #include "orbfe_internal.h"
 
 #define GRID_CELLS (ORBFE_GRID_COLS * ORBFE_GRID_ROWS)
@@ -98,6 +101,27 @@ struct TriParams {
   orbfe_epipolar ep;
 };
 void orbfe_launch_triangulation(const TriParams& p, int n_pairs, hipStream_t s);
+// matcher.cpp: the halves of orbfe_search_for_triangulation around its upload, shared with orbfe_create_new_map_points (mapping.cpp)
+struct TriSearchPlan {
+  std::vector<BowPair> pairs;   // the common vocabulary nodes
+  int totA = 0, totB = 0;       // entries of the two index arrays
+  int sequential = 0;           // a pKF1 feature is listed under two nodes
+};
+struct TriSearchBuffers {       // device pointers of one search
+  const BowPair* pairs; int n_pairs;
+  const uint8_t* descA; const uint8_t* descB;
+  const orbfe_keypoint* keysA; const orbfe_keypoint* keysB;
+  const int32_t* idxA; const int32_t* idxB;
+  const uint8_t* validA; const uint8_t* validB;     // candidate masks: no map point, and stereo under bOnlyStereo
+  const uint8_t* stereoA; const uint8_t* stereoB;   // mvuRight >= 0
+  int32_t* matchA;              // [nA], pre-set to -1
+  int32_t* counters;            // 64 ints, pre-set to 0; [1] = nmatches afterwards
+  int32_t* push_idx; uint8_t* push_bin;   // scratch, max(totA, nA) entries each
+};
+int orbfe_tri_search_plan(int nA, const orbfe_featvec_node* nodesA, int n_nodesA, const int32_t* idxA, int nB,
+                          const orbfe_featvec_node* nodesB, int n_nodesB, const int32_t* idxB, TriSearchPlan& plan);
+int orbfe_tri_search_enqueue(const TriSearchBuffers& b, const orbfe_epipolar* ep, int check_orientation, int sequential, hipStream_t s);
+int orbfe_internal_thread_block(size_t bytes, std::unique_lock<std::mutex>& lk, hipStream_t* s, uint8_t** dev, uint8_t** pinned);
 void orbfe_launch_proj_best(const FrameBatch& f, const QueryBatch& q, int gate, const float* inv_sigma2, int32_t* best_idx,
                             int32_t* best_dist, int n_frames, hipStream_t s);
 void orbfe_launch_hamming_matrix(const uint8_t* A, int nA, const uint8_t* B, int nB, uint16_t* out, hipStream_t s);

@@ -787,6 +787,74 @@ extern "C" int orbfe_kf_search(const orbfe_frame_view* f, const float* inv_level
   return ORBFE_OK;
 }
 
+// The host half of SearchForTriangulation in front of the upload: the merge-join of the two FeatureVectors on NodeId and the
+// checks that keep a malformed one from indexing past the arrays on the device.  ORBFE_OK with no pairs: nothing to search.
+int orbfe_tri_search_plan(int nA, const orbfe_featvec_node* nodesA, int n_nodesA, const int32_t* idxA, int nB,
+                          const orbfe_featvec_node* nodesB, int n_nodesB, const int32_t* idxB, TriSearchPlan& plan) {
+  plan.pairs.clear();
+  plan.totA = plan.totB = plan.sequential = 0;
+  int ia = 0, ib = 0;
+  while (ia < n_nodesA && ib < n_nodesB) {
+    if (nodesA[ia].node_id == nodesB[ib].node_id) {
+      plan.pairs.push_back(BowPair{nodesA[ia].start, nodesA[ia].count, nodesB[ib].start, nodesB[ib].count});
+      if (nodesB[ib].count > 60000) return ORBFE_ERR_INVALID;
+      ia++; ib++;
+    } else if (nodesA[ia].node_id < nodesB[ib].node_id) ia++;
+    else ib++;
+  }
+  for (int i = 0; i < n_nodesA; i++) plan.totA = std::max(plan.totA, nodesA[i].start + nodesA[i].count);
+  for (int i = 0; i < n_nodesB; i++) plan.totB = std::max(plan.totB, nodesB[i].start + nodesB[i].count);
+  if (plan.pairs.empty()) return ORBFE_OK;
+  // a pKF1 feature listed under two nodes (never produced by DBoW2) is visited twice by the reference: replay in order
+  std::vector<uint8_t> seen((size_t)nA, 0);
+  for (const BowPair& pr : plan.pairs) {
+    if (pr.startA < 0 || pr.countA < 0 || pr.startB < 0 || pr.countB < 0) return ORBFE_ERR_INVALID;
+    for (int t = 0; t < pr.countA; t++) {
+      const int j = idxA[pr.startA + t];
+      if (j < 0 || j >= nA) return ORBFE_ERR_INVALID;
+      if (seen[j]) plan.sequential = 1;
+      seen[j] = 1;
+    }
+    for (int t = 0; t < pr.countB; t++)
+      if (idxB[pr.startB + t] < 0 || idxB[pr.startB + t] >= nB) return ORBFE_ERR_INVALID;
+  }
+  return ORBFE_OK;
+}
+
+// The enqueue half: the search and its rotation-histogram pass on stream s, every pointer a device pointer
+int orbfe_tri_search_enqueue(const TriSearchBuffers& b, const orbfe_epipolar* ep, int check_orientation, int sequential, hipStream_t s) {
+  TriParams t;
+  memset(&t, 0, sizeof(t));
+  t.b.pairs = b.pairs;
+  t.b.descA = b.descA; t.b.validA = b.validA; t.b.idxA = b.idxA;
+  t.b.descB = b.descB; t.b.validB = b.validB; t.b.idxB = b.idxB;
+  t.b.check_ori = check_orientation; t.b.sequential = sequential; t.b.n_pairs = b.n_pairs;
+  t.b.kf_mode = 1;   // bow_finish_kernel: rotation rejects clear matchA[push_idx]
+  t.b.matchA = b.matchA; t.b.matchB = nullptr;
+  t.b.counters = b.counters; t.b.push_idx = b.push_idx; t.b.push_bin = b.push_bin;
+  t.keysA = b.keysA; t.keysB = b.keysB;
+  t.stereoA = b.stereoA; t.stereoB = b.stereoB;
+  t.ep = *ep;
+  orbfe_launch_triangulation(t, b.n_pairs, s);
+  return launch_ok();
+}
+
+// The calling thread's handle for another translation unit (mapping.cpp): its stream, and a device block with a pinned host mirror of
+// at least `bytes` each.  lk holds the handle until the caller lets go of it.
+int orbfe_internal_thread_block(size_t bytes, std::unique_lock<std::mutex>& lk, hipStream_t* s, uint8_t** dev, uint8_t** pinned) {
+  orbfe_matcher* m;
+  int rc;
+  if ((rc = tls_matcher(&m))) return rc;
+  lk = std::unique_lock<std::mutex>(m->mu);
+  HIPCHK(hipSetDevice(m->device));
+  if ((rc = mb_alloc(m->st_in, bytes))) return rc;
+  if ((rc = pin_alloc(m->h_pin, m->h_pin_bytes, bytes))) return rc;
+  *s = m->stream;
+  *dev = (uint8_t*)m->st_in.p;
+  *pinned = (uint8_t*)m->h_pin;
+  return ORBFE_OK;
+}
+
 // SearchForTriangulation (L/src/ORBmatcher.cc:614-764), host pointers, synchronous
 extern "C" int orbfe_search_for_triangulation(const orbfe_keypoint* keysA, const uint8_t* descA, const float* u_rightA,
                                               const uint8_t* has_mpA, int nA, const orbfe_featvec_node* nodesA, int n_nodesA,
@@ -800,41 +868,17 @@ extern "C" int orbfe_search_for_triangulation(const orbfe_keypoint* keysA, const
   for (int i = 0; i < nA; i++) matchA[i] = -1;
   if (nA == 0 || nB == 0 || n_nodesA == 0 || n_nodesB == 0) return ORBFE_OK;
   if (!keysA || !descA || !has_mpA || !nodesA || !idxA || !keysB || !descB || !has_mpB || !nodesB || !idxB) return ORBFE_ERR_INVALID;
-  std::vector<BowPair> pairs;
-  int ia = 0, ib = 0, totA = 0, totB = 0;
-  while (ia < n_nodesA && ib < n_nodesB) {
-    if (nodesA[ia].node_id == nodesB[ib].node_id) {
-      pairs.push_back(BowPair{nodesA[ia].start, nodesA[ia].count, nodesB[ib].start, nodesB[ib].count});
-      if (nodesB[ib].count > 60000) return ORBFE_ERR_INVALID;
-      ia++; ib++;
-    } else if (nodesA[ia].node_id < nodesB[ib].node_id) ia++;
-    else ib++;
-  }
-  for (int i = 0; i < n_nodesA; i++) totA = std::max(totA, nodesA[i].start + nodesA[i].count);
-  for (int i = 0; i < n_nodesB; i++) totB = std::max(totB, nodesB[i].start + nodesB[i].count);
+  TriSearchPlan plan;
+  int rc;
+  if ((rc = orbfe_tri_search_plan(nA, nodesA, n_nodesA, idxA, nB, nodesB, n_nodesB, idxB, plan))) return rc;
+  const std::vector<BowPair>& pairs = plan.pairs;
+  const int totA = plan.totA, totB = plan.totB;
   if (pairs.empty()) return ORBFE_OK;
-  // a pKF1 feature listed under two nodes (never produced by DBoW2) is visited twice by the reference: replay in order
-  int sequential = 0;
-  {
-    std::vector<uint8_t> seen((size_t)nA, 0);
-    for (const BowPair& pr : pairs) {
-      if (pr.startA < 0 || pr.countA < 0 || pr.startB < 0 || pr.countB < 0) return ORBFE_ERR_INVALID;
-      for (int t = 0; t < pr.countA; t++) {
-        const int j = idxA[pr.startA + t];
-        if (j < 0 || j >= nA) return ORBFE_ERR_INVALID;
-        if (seen[j]) sequential = 1;
-        seen[j] = 1;
-      }
-      for (int t = 0; t < pr.countB; t++)
-        if (idxB[pr.startB + t] < 0 || idxB[pr.startB + t] >= nB) return ORBFE_ERR_INVALID;
-    }
-  }
   // candidate masks and stereo flags (:655-664, 677-686)
   std::vector<uint8_t> vA((size_t)nA), vB((size_t)nB), sA((size_t)nA), sB((size_t)nB);
   for (int i = 0; i < nA; i++) { sA[i] = u_rightA && u_rightA[i] >= 0; vA[i] = !has_mpA[i] && (!only_stereo || sA[i]); }
   for (int i = 0; i < nB; i++) { sB[i] = u_rightB && u_rightB[i] >= 0; vB[i] = !has_mpB[i] && (!only_stereo || sB[i]); }
   orbfe_matcher* m;
-  int rc;
   if ((rc = tls_matcher(&m))) return rc;
   std::lock_guard<std::mutex> lk(m->mu);
   HIPCHK(hipSetDevice(m->device));
@@ -861,20 +905,15 @@ extern "C" int orbfe_search_for_triangulation(const orbfe_keypoint* keysA, const
   HIPCHK(hipMemcpyAsync(d + o_sB, sB.data(), (size_t)nB, hipMemcpyHostToDevice, s));
   HIPCHK(hipMemsetAsync(d + o_mA, 0xff, (size_t)nA * 4, s));
   HIPCHK(hipMemsetAsync(d + o_cnt, 0, 256, s));
-  TriParams t;
-  memset(&t, 0, sizeof(t));
-  t.b.pairs = (const BowPair*)(d + o_pairs);
-  t.b.descA = d + o_dA; t.b.validA = d + o_vA; t.b.idxA = (const int32_t*)(d + o_iA);
-  t.b.descB = d + o_dB; t.b.validB = d + o_vB; t.b.idxB = (const int32_t*)(d + o_iB);
-  t.b.check_ori = check_orientation; t.b.sequential = sequential; t.b.n_pairs = (int)pairs.size();
-  t.b.kf_mode = 1;   // bow_finish_kernel: rotation rejects clear matchA[push_idx]
-  t.b.matchA = (int32_t*)(d + o_mA); t.b.matchB = nullptr;
-  t.b.counters = (int32_t*)(d + o_cnt); t.b.push_idx = (int32_t*)(d + o_pi); t.b.push_bin = d + o_pb;
-  t.keysA = (const orbfe_keypoint*)(d + o_kA); t.keysB = (const orbfe_keypoint*)(d + o_kB);
-  t.stereoA = d + o_sA; t.stereoB = d + o_sB;
-  t.ep = *ep;
-  orbfe_launch_triangulation(t, (int)pairs.size(), s);
-  if ((rc = launch_ok())) return rc;
+  TriSearchBuffers b;
+  b.pairs = (const BowPair*)(d + o_pairs); b.n_pairs = (int)pairs.size();
+  b.descA = d + o_dA; b.descB = d + o_dB;
+  b.keysA = (const orbfe_keypoint*)(d + o_kA); b.keysB = (const orbfe_keypoint*)(d + o_kB);
+  b.idxA = (const int32_t*)(d + o_iA); b.idxB = (const int32_t*)(d + o_iB);
+  b.validA = d + o_vA; b.validB = d + o_vB; b.stereoA = d + o_sA; b.stereoB = d + o_sB;
+  b.matchA = (int32_t*)(d + o_mA); b.counters = (int32_t*)(d + o_cnt);
+  b.push_idx = (int32_t*)(d + o_pi); b.push_bin = d + o_pb;
+  if ((rc = orbfe_tri_search_enqueue(b, ep, check_orientation, plan.sequential, s))) return rc;
   int32_t cnt[2] = {0, 0};
   HIPCHK(hipMemcpyAsync(matchA, d + o_mA, (size_t)nA * 4, hipMemcpyDeviceToHost, s));
   HIPCHK(hipMemcpyAsync(cnt, d + o_cnt, 8, hipMemcpyDeviceToHost, s));
