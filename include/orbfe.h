@@ -749,6 +749,79 @@ int orbfe_create_new_map_points(const orbfe_keypoint* keysA, const uint8_t* desc
                                 const orbfe_tri_view* viewA, const orbfe_tri_neighbor* neighbors, int K, int monocular,
                                 int only_stereo, int check_orientation, orbfe_new_point* points, int32_t* n_matches, int32_t* n_new);
 
+/* ---- Sim3Solver (L/src/Sim3Solver.cc) ---------------------------------------------------------------------------------------------
+ * The RANSAC of LoopClosing::ComputeSim3 between orbfe_search_by_bow and the Sim3 search: a hypothesis is Horn's closed-form
+ * similarity from three correspondences (ComputeSim3, :216-322), its score the two-sided reprojection test of CheckInliers
+ * (:324-344).  All H hypotheses of a problem are independent, so one launch evaluates them all (one wave per hypothesis, the
+ * verdicts of 64 correspondences are one ballot) and a second one applies the sequential rule of iterate (:178-193) to the
+ * counts: the solver returns the FIRST hypothesis with count > min_inliers -- every earlier one has a smaller count, so the
+ * reference's `>=` test on mnBestInliers holds there -- and without one its best is the LAST hypothesis with the maximal count.
+ * iterate(n) in chunks is a cursor over the same sequence (refactored_orb_slam2_amd/sim3.py: iterate_replay).
+ * The caller draws the triples (Sim3Solver.cc:155-172; sim3.py: draw_triples); the library holds no random state.
+ * csrc/sim3_internal.h states the arithmetic once, float where the reference is float (centroids, Pr, M, P3, projections, errors)
+ * and double where it is double (the sums of N, ang, nom / den).  cv::eigen and cv::Rodrigues are not available where this library
+ * is built: the eigenvector of the largest eigenvalue of the 4x4 comes from this project's own cyclic Jacobi in double on the float
+ * matrix, Rodrigues is evaluated in double and rounded to float.  Two properties:
+ *   - q and -q give the same rotation through the atan2 form (the axis flips and the angle 2 * ang becomes 2 * pi - 2 * ang), so the
+ *     sign convention of the eigenvector does not matter;
+ *   - a quaternion with a zero imaginary part (norm(vec) == 0) is 0 / 0 in the reference: every comparison with NaN is false and the
+ *     hypothesis has 0 inliers.  Here too: n_inliers == 0 and an all-zero inlier word row, the rest of the record unspecified (it may
+ *     hold NaN); nothing traps and no other record is touched.
+ * Deterministic: no atomics, a hypothesis' record and words depend on its problem and its triple only.  No CPU fallback. */
+#define ORBFE_SIM3_MAX_PAIRS 1024        /* correspondences of a problem: 48 bytes each once prepared, 48 KiB = the LDS a workgroup
+                                            stages them in (three workgroups per CU); a loop candidate has tens to hundreds */
+#define ORBFE_SIM3_MAX_HYPOTHESES 4096   /* the reference never exceeds its maxIterations (300) */
+typedef struct orbfe_sim3_view {         /* what the solver reads of one KeyFrame */
+  float Rcw[9], tcw[3];                  /* GetRotation() row-major, GetTranslation() */
+  float fx, fy, cx, cy;                  /* mK */
+} orbfe_sim3_view;                       /* 64 bytes */
+typedef struct orbfe_sim3_pair {         /* one kept match (Sim3Solver.cc:62-100) */
+  float Xw1[3], Xw2[3];                  /* pMP1->GetWorldPos(), pMP2->GetWorldPos() */
+  float max_err1, max_err2;              /* (float)(size_t)(9.210 * mvLevelSigma2[octave]): the caller truncates, as the
+                                            reference's vector<size_t> does (include/Sim3Solver.h:74-75) */
+} orbfe_sim3_pair;                       /* 32 bytes */
+typedef struct orbfe_sim3_hypothesis {
+  float s, R[9], t[3];                   /* ms12i, mR12i row-major, mt12i; all 0 for a triple the device form rejects */
+  int32_t n_inliers;                     /* mnInliersi */
+  int32_t reserved[2];
+} orbfe_sim3_hypothesis;                 /* 64 bytes */
+typedef struct orbfe_sim3_result {
+  int32_t returned;                      /* the hypothesis iterate returns on (first count > min_inliers), or -1 */
+  int32_t n_inliers;                     /* its count, 0 without one */
+  int32_t best;                          /* == returned when >= 0, else the last hypothesis with the maximal count; -1: none evaluated */
+  int32_t best_inliers;                  /* mnBestInliers */
+  float T12[12];                         /* mBestT12, rows 0-2: [s * R | t] */
+  float s, R[9], t[3];                   /* GetEstimatedScale / Rotation / Translation */
+  int32_t reserved[3];
+} orbfe_sim3_result;                     /* 128 bytes */
+/* SetRansacParameters (:112-136) for N correspondences: epsilon = (float)min_inliers / N, ceil(log(1 - probability) /
+ * log(1 - pow(epsilon, 3))) in double, 1 when min_inliers == N, then max(1, min(that, max_iterations)).  Pure host.
+ * ORBFE_ERR_INVALID: N < 1, min_inliers < 0 or > N, max_iterations < 0, probability outside (0, 1). */
+int orbfe_sim3_ransac_iterations(int N, double probability, int min_inliers, int max_iterations);
+/* One problem.  HOST pointers, synchronous, on the calling thread's current device.  triples[3*h .. 3*h+2] index the pairs.
+ * hyps[H] and words[H][ceil(n/64)] are optional (NULL skips their download); bit (i & 63) of word i / 64 is the verdict of pair i,
+ * the tail bits of the last word are 0 and n_inliers is the popcount of the row.  result_mask[ceil(n/64)] is the word row of
+ * result->best (zeros without one).  n < 3 or n < min_inliers (:144-147): returned = best = -1, no hypothesis is evaluated, hyps
+ * and words come back zero and nothing is launched.  One packed upload, one packed download, one synchronisation.
+ * Limits (ORBFE_ERR_INVALID): 0 <= n <= ORBFE_SIM3_MAX_PAIRS, 0 <= H <= ORBFE_SIM3_MAX_HYPOTHESES, min_inliers >= 0, a triple
+ * index outside [0, n) or repeated within its triple, null views / result / result_mask, null pairs with n > 0 or triples with H > 0. */
+int orbfe_sim3_solve(const orbfe_sim3_view* view1, const orbfe_sim3_view* view2, const orbfe_sim3_pair* pairs, int n,
+                     const int32_t* triples, int H, int fix_scale, int min_inliers, orbfe_sim3_hypothesis* hyps, uint64_t* words,
+                     orbfe_sim3_result* result, uint64_t* result_mask);
+/* P problems in one launch pair.  DEVICE pointers, asynchronous on `stream` (NULL: the NULL stream).  Problem p: d_view1[p],
+ * d_view2[p], d_fix_scale[p], d_min_inliers[p], pair rows [p*cap, p*cap + d_n[p]), triple rows [p*h_cap, p*h_cap + d_H[p]); it writes
+ * the same rows of d_hyps, the first ceil(d_n[p]/64) words of rows [p*h_cap, ..) of d_words (row stride W = ceil(cap/64)), d_result[p]
+ * and the first ceil(d_n[p]/64) words of d_result_mask[p*W ..].  Counts are clamped to [0, cap] / [0, h_cap]; rows and words behind
+ * them are neither read nor written.  A triple with an index outside [0, d_n[p]) or a repeated one yields an all-zero record and
+ * word row and reads nothing outside the problem.  A problem with fewer than 3 or than min_inliers pairs gets returned = best = -1
+ * and nothing else.  A problem's bytes do not depend on P, on its position in the batch or on the run.
+ * Limits (ORBFE_ERR_INVALID): 0 <= P <= 65 535 (0: nothing is launched), 1 <= cap <= ORBFE_SIM3_MAX_PAIRS, 1 <= h_cap <=
+ * ORBFE_SIM3_MAX_HYPOTHESES, null pointers, records not 4-byte (d_words / d_result_mask: 8-byte) aligned. */
+int orbfe_sim3_solve_batch_device(int P, const orbfe_sim3_view* d_view1, const orbfe_sim3_view* d_view2, const orbfe_sim3_pair* d_pairs,
+                                  const int32_t* d_n, int cap, const int32_t* d_triples, const int32_t* d_H, int h_cap,
+                                  const int32_t* d_fix_scale, const int32_t* d_min_inliers, orbfe_sim3_hypothesis* d_hyps,
+                                  uint64_t* d_words, orbfe_sim3_result* d_result, uint64_t* d_result_mask, void* stream);
+
 /* SearchForInitialization (L/src/ORBmatcher.cc:388-492), the monocular map-initialisation matcher: level-0
  * keypoints of F1 are searched in a window of `window_size` pixels around prev_matched_xy[2*i..2*i+1] in F2; a
  * closer later keypoint steals an earlier match (vMatchedDistance / vnMatches21).  matches12[i] = F2 index or -1;

@@ -108,6 +108,16 @@ assert TRI_VIEW_DTYPE.itemsize == 224 and NEW_POINT_DTYPE.itemsize == 44 and TRI
  TRI_SCALE) = range(10)
 TRI_PATH_NONE, TRI_PATH_LINEAR, TRI_PATH_UNPROJECT1, TRI_PATH_UNPROJECT2 = range(4)
 TRI_MAX_ROWS = 65535
+# orbfe_sim3_view / orbfe_sim3_pair / orbfe_sim3_hypothesis / orbfe_sim3_result (Sim3Solver, include/orbfe.h)
+SIM3_VIEW_DTYPE = np.dtype([("Rcw", "<f4", (9,)), ("tcw", "<f4", (3,)), ("fx", "<f4"), ("fy", "<f4"), ("cx", "<f4"), ("cy", "<f4")])
+SIM3_PAIR_DTYPE = np.dtype([("Xw1", "<f4", (3,)), ("Xw2", "<f4", (3,)), ("max_err1", "<f4"), ("max_err2", "<f4")])
+SIM3_HYPOTHESIS_DTYPE = np.dtype([("s", "<f4"), ("R", "<f4", (9,)), ("t", "<f4", (3,)), ("n_inliers", "<i4"), ("reserved", "<i4", (2,))])
+SIM3_RESULT_DTYPE = np.dtype([("returned", "<i4"), ("n_inliers", "<i4"), ("best", "<i4"), ("best_inliers", "<i4"), ("T12", "<f4", (12,)),
+                              ("s", "<f4"), ("R", "<f4", (9,)), ("t", "<f4", (3,)), ("reserved", "<i4", (3,))])
+assert SIM3_VIEW_DTYPE.itemsize == 64 and SIM3_PAIR_DTYPE.itemsize == 32 and SIM3_HYPOTHESIS_DTYPE.itemsize == 64
+assert SIM3_RESULT_DTYPE.itemsize == 128
+SIM3_MAX_PAIRS, SIM3_MAX_HYPOTHESES, SIM3_MAX_PROBLEMS = 1024, 4096, 65535
+SIM3_WAVES = 4   # hypotheses per workgroup of sim3_hypotheses_kernel (csrc/sim3_internal.h)
 
 
 class RectifyCamera(C.Structure):
@@ -151,6 +161,7 @@ EXPORTS = [
     "orbfe_rectify_image", "orbfe_rectify_batch_device", "orbfe_pipeline_set_rectifiers",
     "orbfe_pose_optimization", "orbfe_pose_optimization_batch_device",
     "orbfe_triangulate_matches", "orbfe_triangulate_matches_batch_device", "orbfe_create_new_map_points",
+    "orbfe_sim3_ransac_iterations", "orbfe_sim3_solve", "orbfe_sim3_solve_batch_device",
 ]
 
 
@@ -261,6 +272,9 @@ def lib():
     L.orbfe_triangulate_matches.argtypes = [vp, vp, vp, vp, ci, vp, vp, vp, vp, ci, vp, vp, pi]
     L.orbfe_triangulate_matches_batch_device.argtypes = [ci, vp, vp, vp, vp, vp, ci, vp, vp, vp, vp, vp, ci, vp, vp, vp, vp]
     L.orbfe_create_new_map_points.argtypes = [vp, vp, vp, vp, vp, ci, vp, ci, vp, vp, vp, ci, ci, ci, ci, vp, vp, vp]
+    L.orbfe_sim3_ransac_iterations.argtypes = [ci, C.c_double, ci, ci]
+    L.orbfe_sim3_solve.argtypes = [vp, vp, vp, ci, vp, ci, ci, ci, vp, vp, vp, vp]
+    L.orbfe_sim3_solve_batch_device.argtypes = [ci, vp, vp, vp, vp, ci, vp, vp, ci, vp, vp, vp, vp, vp, vp, vp]
     for name in EXPORTS:
         if name != "orbfe_last_error":
             getattr(L, name).restype = ci
