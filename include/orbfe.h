@@ -108,6 +108,9 @@ int orbfe_device_download(void* h_dst, const void* d_src, size_t bytes);
  *   new map points      at most 65 535 keypoints per keyframe (orbfe_triangulate_matches*, orbfe_create_new_map_points: the descriptor
  *                       limit of SearchForTriangulation), at most 65 535 pairs per batch launch, n_levels 1 .. ORBFE_MAX_LEVELS
  *                       (pinned by tests/test_mapping_cpu.py)
+ *   Sim3 optimisation   at most 9 500 correspondences per problem (orbfe_optimize_sim3, orbfe_optimize_sim3_batch_device: the frame
+ *                       limit of the Sim3 search whose matches it reads), at most 65 535 problems per batch launch, th2 > 0
+ *                       (pinned by tests/test_optsim3_cpu.py)
  * Each limit is pinned at its largest accepted and its first refused value by tests/test_limits_gpu.py (levels: also
  * tests/test_cabi_cpu.py; depth maps: tests/test_frames_cpu.py and tests/test_frames_gpu.py; rectification:
  * tests/test_rectify_cpu.py and tests/test_rectify_gpu.py; pose optimisation: tests/test_pose_cpu.py).
@@ -821,6 +824,56 @@ int orbfe_sim3_solve_batch_device(int P, const orbfe_sim3_view* d_view1, const o
                                   const int32_t* d_n, int cap, const int32_t* d_triples, const int32_t* d_H, int h_cap,
                                   const int32_t* d_fix_scale, const int32_t* d_min_inliers, orbfe_sim3_hypothesis* d_hyps,
                                   uint64_t* d_words, orbfe_sim3_result* d_result, uint64_t* d_result_mask, void* stream);
+
+/* ---- Optimizer::OptimizeSim3 (L/src/Optimizer.cc:1381-1573) ----------------------------------------------------------------------
+ * The last step of LoopClosing::ComputeSim3 (L/src/LoopClosing.cc:224-322): the similarity S12 of orbfe_sim3_result and the matches
+ * of the Sim3 search are refined by g2o's Levenberg on one 7-DoF vertex with two Huber edges per correspondence -- x1 = S12 X2 in
+ * image 1 and x2 = S12^-1 X1 in image 2, points fixed -- and the candidate is accepted when the return value is >= 20.  Schedule:
+ * optimize(5); every correspondence with chi2 > th2 on either edge is dropped (nBad); fewer than 10 left: return 0 and the
+ * similarity is NOT written, although the dropped matches are already nulled; otherwise optimize(10 when nBad > 0, else 5) on the
+ * rest, a second classification, and the estimate is returned with the number of correspondences that survived both.
+ * csrc/optsim3_internal.h states the arithmetic once, all in double: g2o::Sim3 (exp with its four branches on 1e-5, map, inverse,
+ * operator*), oplus with the fixed-scale rule, the edges' NUMERIC Jacobians (central differences, delta = 1e-9, through oplus: the
+ * reference's edges have no linearizeOplus), Huber, the quadratic form and g2o's Levenberg (lambda = 1e-5 * max diag H at iteration
+ * 0 of each call, at most 10 trials per iteration).  The camera-frame points are the float gemm R * Xw + t of the reference.  Eigen
+ * and g2o cannot be built where this library is built: the 7 x 7 system is solved by this project's unpivoted L D L^T, the
+ * quaternion formulas are Eigen's written out (a reading, unpinned).
+ * One deliberate deviation, the one of orbfe_pose_optimization: a correspondence is classified by its chi2 at the final estimate of
+ * the optimize() call.  The reference reads the error that the last Levenberg trial left in the edge, also when that trial was
+ * rejected; such a step is taken at a large lambda and is tiny.
+ * Deterministic: no atomics, a problem's result and flags depend on its own rows only.  No CPU fallback. */
+typedef struct orbfe_optsim3_pair {      /* one correspondence that passed the filters of Optimizer.cc:1436-1468; 48 bytes */
+  float Xw1[3], Xw2[3];                  /* GetWorldPos() of pMP1, pMP2 */
+  float obs1[2], obs2[2];                /* mvKeysUn[i].pt of KF1, mvKeysUn[i2].pt of KF2 */
+  float inv_sigma2_1, inv_sigma2_2;      /* mvInvLevelSigma2[octave] of each */
+} orbfe_optsim3_pair;
+typedef struct orbfe_optsim3_result {    /* s, R[9], t[3]: the input's bits when n_inliers == 0 by the < 10 rule */
+  float s, R[9], t[3];                   /* g2oS12: scale(), rotation().toRotationMatrix() row-major, translation() */
+  int32_t n_pairs, n_bad, n_inliers;     /* nCorrespondences, nBad of the first classification, the return value */
+  int32_t iterations[2];                 /* Levenberg iterations of the two optimize() calls (reported, not part of parity) */
+  int32_t reserved[2];
+} orbfe_optsim3_result;                  /* 80 bytes */
+/* One problem.  HOST pointers, synchronous, on the calling thread's current device.  view1 / view2: GetRotation, GetTranslation and
+ * mK of pKF1 / pKF2; s_R_t_in: g2oS12 as 13 floats (scale, rotation row-major, translation -- LoopClosing builds it from the float
+ * matrices of the solver); th2: the chi-square bound (10 in LoopClosing), its float square root is the Huber delta; bad[n]: 1 where
+ * the reference nulls the vpMatches1 entry (in either classification).  n < 10 still runs the first optimize(5) and classification,
+ * as the reference does, and returns n_inliers == 0 with the input transform; n == 0 launches nothing.  One packed upload, one
+ * launch, one packed download.
+ * Limits (ORBFE_ERR_INVALID): 0 <= n <= 9 500, th2 > 0 (a NaN is refused), null views / s_R_t_in / result, null pairs or bad with
+ * n > 0. */
+int orbfe_optimize_sim3(const orbfe_sim3_view* view1, const orbfe_sim3_view* view2, const orbfe_optsim3_pair* pairs, int n,
+                        const float* s_R_t_in, float th2, int fix_scale, orbfe_optsim3_result* result, uint8_t* bad);
+/* P problems in one launch, one workgroup each.  DEVICE pointers, asynchronous on `stream` (NULL: the NULL stream).  Problem p:
+ * d_view1[p], d_view2[p], d_s_R_t_in[13 * p ..], d_th2[p], d_fix_scale[p], pair rows [p*cap, p*cap + d_n[p]); it writes d_result[p] and
+ * the same rows of d_bad.  Counts are clamped to [0, cap]; rows behind them are neither read nor written.  A d_th2[p] that is not
+ * > 0 is not checked on the device: every comparison with it decides as IEEE does, nothing traps and no other problem is touched.
+ * A problem's bytes do not depend on P, on its position in the batch or on the run.
+ * Limits (ORBFE_ERR_INVALID): 0 <= P <= 65 535 (0: nothing is launched), 0 <= cap <= 9 500, null pointers (d_pairs and d_bad may be
+ * null when cap == 0), records not 4-byte aligned. */
+int orbfe_optimize_sim3_batch_device(int P, const orbfe_sim3_view* d_view1, const orbfe_sim3_view* d_view2,
+                                     const orbfe_optsim3_pair* d_pairs, const int32_t* d_n, int cap, const float* d_s_R_t_in,
+                                     const float* d_th2, const int32_t* d_fix_scale, orbfe_optsim3_result* d_result, uint8_t* d_bad,
+                                     void* stream);
 
 /* SearchForInitialization (L/src/ORBmatcher.cc:388-492), the monocular map-initialisation matcher: level-0
  * keypoints of F1 are searched in a window of `window_size` pixels around prev_matched_xy[2*i..2*i+1] in F2; a

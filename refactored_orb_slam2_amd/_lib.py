@@ -118,6 +118,13 @@ assert SIM3_VIEW_DTYPE.itemsize == 64 and SIM3_PAIR_DTYPE.itemsize == 32 and SIM
 assert SIM3_RESULT_DTYPE.itemsize == 128
 SIM3_MAX_PAIRS, SIM3_MAX_HYPOTHESES, SIM3_MAX_PROBLEMS = 1024, 4096, 65535
 SIM3_WAVES = 4   # hypotheses per workgroup of sim3_hypotheses_kernel (csrc/sim3_internal.h)
+# orbfe_optsim3_pair / orbfe_optsim3_result (Optimizer::OptimizeSim3, include/orbfe.h)
+OPTSIM3_PAIR_DTYPE = np.dtype([("Xw1", "<f4", (3,)), ("Xw2", "<f4", (3,)), ("obs1", "<f4", (2,)), ("obs2", "<f4", (2,)),
+                               ("inv_sigma2_1", "<f4"), ("inv_sigma2_2", "<f4")])
+OPTSIM3_RESULT_DTYPE = np.dtype([("s", "<f4"), ("R", "<f4", (9,)), ("t", "<f4", (3,)), ("n_pairs", "<i4"), ("n_bad", "<i4"),
+                                 ("n_inliers", "<i4"), ("iterations", "<i4", (2,)), ("reserved", "<i4", (2,))])
+assert OPTSIM3_PAIR_DTYPE.itemsize == 48 and OPTSIM3_RESULT_DTYPE.itemsize == 80
+OPTSIM3_MAX_PAIRS, OPTSIM3_MAX_PROBLEMS = 9500, 65535
 
 
 class RectifyCamera(C.Structure):
@@ -162,6 +169,7 @@ EXPORTS = [
     "orbfe_pose_optimization", "orbfe_pose_optimization_batch_device",
     "orbfe_triangulate_matches", "orbfe_triangulate_matches_batch_device", "orbfe_create_new_map_points",
     "orbfe_sim3_ransac_iterations", "orbfe_sim3_solve", "orbfe_sim3_solve_batch_device",
+    "orbfe_optimize_sim3", "orbfe_optimize_sim3_batch_device",
 ]
 
 
@@ -275,6 +283,8 @@ def lib():
     L.orbfe_sim3_ransac_iterations.argtypes = [ci, C.c_double, ci, ci]
     L.orbfe_sim3_solve.argtypes = [vp, vp, vp, ci, vp, ci, ci, ci, vp, vp, vp, vp]
     L.orbfe_sim3_solve_batch_device.argtypes = [ci, vp, vp, vp, vp, ci, vp, vp, ci, vp, vp, vp, vp, vp, vp, vp]
+    L.orbfe_optimize_sim3.argtypes = [vp, vp, vp, ci, vp, cf, ci, vp, vp]
+    L.orbfe_optimize_sim3_batch_device.argtypes = [ci, vp, vp, vp, vp, ci, vp, vp, vp, vp, vp, vp]
     for name in EXPORTS:
         if name != "orbfe_last_error":
             getattr(L, name).restype = ci

@@ -1,4 +1,4 @@
-// Optimizer_hip.h -- host-side adapter that puts ORB_SLAM2::Optimizer::PoseOptimization on liborbfe.
+// Optimizer_hip.h -- host-side adapters that put ORB_SLAM2::Optimizer::PoseOptimization and Optimizer::OptimizeSim3 on liborbfe.
 //
 // The reference's function (Source/Libraries/ORB_SLAM2/src/Optimizer.cc:233-435) builds a g2o graph of one pose vertex and one
 // unary edge per keypoint with a map point, optimises it and writes the pose and the outlier flags back into the Frame.  This
@@ -9,8 +9,15 @@
 // Members used (same names as the reference):
 //   Frame:    N, mvKeysUn, mvuRight, mvpMapPoints, mvbOutlier, mvInvLevelSigma2, fx, fy, cx, cy, mbf, mTcw, SetPose(cv::Mat)
 //   MapPoint: GetWorldPos(), the static mutex mGlobalMutex (held while the positions are read, as Optimizer.cc:273 does)
+//
+// OptimizeSim3 (Optimizer.cc:1381-1573) is the same kind of adapter for orbfe_optimize_sim3; it is a template over the KeyFrame, the
+// MapPoint and the g2o::Sim3 type and is unit-tested by tests/cpp_optsim3.  Members used:
+//   KeyFrame: mK, GetRotation(), GetTranslation(), GetMapPointMatches(), mvKeysUn, mvInvLevelSigma2
+//   MapPoint: isBad(), GetWorldPos(), GetIndexInKeyFrame(pKF)
+//   Sim3:     rotation() (with toRotationMatrix()), translation(), scale(), and the constructor (Matrix3, Vector3, double)
 #pragma once
 #include <stdio.h>
+#include <string.h>
 
 #include <mutex>
 #include <type_traits>
@@ -74,6 +81,101 @@ int PoseOptimization(FrameT* pFrame) {
   for (int r = 0; r < 3; r++)
     for (int c = 0; c < 4; c++) pose.template at<float>(r, c) = res.Tcw[4 * r + c];
   pFrame->SetPose(pose);
+  return res.n_inliers;
+}
+
+// int Optimizer::OptimizeSim3(KeyFrame* pKF1, KeyFrame* pKF2, vector<MapPoint*>& vpMatches1, g2o::Sim3& g2oS12, const float th2,
+// const bool bFixScale).  The filters of :1436-1468 run here; the library gets the correspondences that pass them.  vpMatches1 and
+// g2oS12 are written exactly where the reference writes them: the entries of the correspondences dropped in either classification
+// are nulled, and with fewer than 10 left after the first one the function returns 0 WITHOUT writing g2oS12 (:1545).
+// The ABI carries the similarity as floats.  LoopClosing::ComputeSim3 builds g2oS12 from the float matrices of the solver, so nothing
+// is lost on the way in; on the way out the estimate is rounded to float and g2oS12 rebuilt by Sim3(R, t, s), whose quaternion is
+// normalised -- 1e-7 relative, against the reference's unrounded doubles.
+// Errors (no device, more correspondences than the library's limit) are logged and return 0 with nothing written.
+// The graph construction of :1396-1514 as the library's arguments: the two views, the correspondences that pass the filters and,
+// for each, its index in vpMatches1 (vnIndexEdge).
+template <class KeyFrameT, class MapPointT>
+void OptimizeSim3Marshal(KeyFrameT* pKF1, KeyFrameT* pKF2, const std::vector<MapPointT*>& vpMatches1, orbfe_sim3_view& v1,
+                         orbfe_sim3_view& v2, std::vector<orbfe_optsim3_pair>& pairs, std::vector<size_t>& vnIndexEdge) {
+  auto view = [](KeyFrameT* pKF) {
+    orbfe_sim3_view v;
+    memset(&v, 0, sizeof(v));
+    const cv::Mat R = pKF->GetRotation(), t = pKF->GetTranslation();
+    for (int r = 0; r < 3; r++) {
+      for (int c = 0; c < 3; c++) v.Rcw[3 * r + c] = R.template at<float>(r, c);
+      v.tcw[r] = t.template at<float>(r);
+    }
+    v.fx = pKF->mK.template at<float>(0, 0); v.fy = pKF->mK.template at<float>(1, 1);
+    v.cx = pKF->mK.template at<float>(0, 2); v.cy = pKF->mK.template at<float>(1, 2);
+    return v;
+  };
+  v1 = view(pKF1);
+  v2 = view(pKF2);
+  const int N = (int)vpMatches1.size();
+  const std::vector<MapPointT*> vpMapPoints1 = pKF1->GetMapPointMatches();
+  pairs.clear();
+  vnIndexEdge.clear();
+  pairs.reserve(N);
+  vnIndexEdge.reserve(N);
+  for (int i = 0; i < N; i++) {   // :1436-1514
+    if (!vpMatches1[i]) continue;
+    MapPointT* pMP1 = vpMapPoints1[i];
+    MapPointT* pMP2 = vpMatches1[i];
+    const int i2 = pMP2->GetIndexInKeyFrame(pKF2);
+    if (!pMP1 || !pMP2) continue;
+    if (pMP1->isBad() || pMP2->isBad() || i2 < 0) continue;
+    orbfe_optsim3_pair p;
+    const cv::Mat P3D1w = pMP1->GetWorldPos(), P3D2w = pMP2->GetWorldPos();
+    for (int r = 0; r < 3; r++) {
+      p.Xw1[r] = P3D1w.template at<float>(r);
+      p.Xw2[r] = P3D2w.template at<float>(r);
+    }
+    const auto& kpUn1 = pKF1->mvKeysUn[i];
+    const auto& kpUn2 = pKF2->mvKeysUn[i2];
+    p.obs1[0] = kpUn1.pt.x; p.obs1[1] = kpUn1.pt.y;
+    p.obs2[0] = kpUn2.pt.x; p.obs2[1] = kpUn2.pt.y;
+    p.inv_sigma2_1 = pKF1->mvInvLevelSigma2[kpUn1.octave];
+    p.inv_sigma2_2 = pKF2->mvInvLevelSigma2[kpUn2.octave];
+    pairs.push_back(p);
+    vnIndexEdge.push_back((size_t)i);
+  }
+}
+
+template <class KeyFrameT, class MapPointT, class Sim3T>
+int OptimizeSim3(KeyFrameT* pKF1, KeyFrameT* pKF2, std::vector<MapPointT*>& vpMatches1, Sim3T& g2oS12, const float th2,
+                 const bool bFixScale) {
+  orbfe_sim3_view v1, v2;
+  std::vector<orbfe_optsim3_pair> pairs;
+  std::vector<size_t> vnIndexEdge;
+  OptimizeSim3Marshal(pKF1, pKF2, vpMatches1, v1, v2, pairs, vnIndexEdge);
+  float sRt[13];
+  {
+    const auto R = g2oS12.rotation().toRotationMatrix();
+    const auto& t = g2oS12.translation();
+    sRt[0] = (float)g2oS12.scale();
+    for (int r = 0; r < 3; r++) {
+      for (int c = 0; c < 3; c++) sRt[1 + 3 * r + c] = (float)R(r, c);
+      sRt[10 + r] = (float)t[r];
+    }
+  }
+  const int n = (int)pairs.size();
+  orbfe_optsim3_result res;
+  std::vector<uint8_t> bad((size_t)n, 0);
+  const int rc = orbfe_optimize_sim3(&v1, &v2, pairs.data(), n, sRt, th2, bFixScale ? 1 : 0, &res, bad.data());
+  if (rc != ORBFE_OK) {
+    fprintf(stderr, "orbfe OptimizeSim3: %s (code %d)\n", orbfe_last_error(), rc);
+    return 0;
+  }
+  for (int k = 0; k < n; k++)
+    if (bad[k]) vpMatches1[vnIndexEdge[k]] = static_cast<MapPointT*>(NULL);   // :1530, :1562
+  if (res.n_pairs - res.n_bad < 10) return 0;                                // :1545, before g2oS12 is written
+  std::decay_t<decltype(g2oS12.rotation().toRotationMatrix())> R;
+  std::decay_t<decltype(g2oS12.translation())> t;
+  for (int r = 0; r < 3; r++) {
+    for (int c = 0; c < 3; c++) R(r, c) = (double)res.R[3 * r + c];
+    t[r] = (double)res.t[r];
+  }
+  g2oS12 = Sim3T(R, t, (double)res.s);
   return res.n_inliers;
 }
 

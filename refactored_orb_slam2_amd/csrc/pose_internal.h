@@ -338,14 +338,16 @@ struct PoseLM {
   double lambda, ni;
 };
 
-// Good / bad step bookkeeping of one trial (optimization_algorithm_levenberg.cpp:125-146).  Returns true when the step is accepted.
-__host__ __device__ inline bool pose_lm_trial(PoseLM& lm, bool ok2, double current_chi, double temp_chi, const double* x, const double* b,
-                                              double* rho_out) {
+// Good / bad step bookkeeping of one trial (optimization_algorithm_levenberg.cpp:125-146) for a vertex of N dimensions (6: the pose,
+// 7: the similarity of optsim3_internal.h).  Returns true when the step is accepted.
+template <int N>
+__host__ __device__ inline bool pose_lm_trial_n(PoseLM& lm, bool ok2, double current_chi, double temp_chi, const double* x, const double* b,
+                                                double* rho_out) {
   double scale = 1.0;
   if (ok2) {
     scale = 0.0;
 #pragma unroll
-    for (int j = 0; j < 6; j++) scale += x[j] * (lm.lambda * x[j] + b[j]);   // computeScale
+    for (int j = 0; j < N; j++) scale += x[j] * (lm.lambda * x[j] + b[j]);   // computeScale
     scale = scale + 1e-3;
   } else {
     temp_chi = 1.7976931348623157e308;   // std::numeric_limits<double>::max()
@@ -364,6 +366,11 @@ __host__ __device__ inline bool pose_lm_trial(PoseLM& lm, bool ok2, double curre
   lm.lambda *= lm.ni;
   lm.ni *= 2;
   return false;
+}
+
+__host__ __device__ inline bool pose_lm_trial(PoseLM& lm, bool ok2, double current_chi, double temp_chi, const double* x, const double* b,
+                                              double* rho_out) {
+  return pose_lm_trial_n<6>(lm, ok2, current_chi, temp_chi, x, b, rho_out);
 }
 
 void orbfe_launch_pose_optimize(int n_frames, const orbfe_keypoint* keys_un, const float* u_right, const int32_t* n, int cap,

@@ -1,9 +1,13 @@
-"""Optimizer::PoseOptimization over the C ABI of liborbfe.so (L/src/Optimizer.cc:233-435, L/ = Source/Libraries/ORB_SLAM2/): the
-pose of a frame from its keypoint <-> map-point pairs, and which pairs were wrong.
+"""Optimizer::PoseOptimization and Optimizer::OptimizeSim3 over the C ABI of liborbfe.so (L/src/Optimizer.cc:233-435, :1381-1573,
+L/ = Source/Libraries/ORB_SLAM2/): the pose of a frame from its keypoint <-> map-point pairs, and which pairs were wrong; the
+similarity between two keyframes of a loop candidate from their matched map points, and which matches were wrong.
 
 pose_optimization is the per-frame call of Tracking on host arrays; pose_optimization_batch optimises every frame of a batch in one
 launch on device tensors (pose_kernels.hip, one workgroup per frame) and reads the `assigned` array of the batched projection
 searches unchanged.  Both run the same kernel; there is no CPU path.
+
+optimize_sim3 is the per-candidate call of LoopClosing::ComputeSim3 on host arrays; optimize_sim3_batch optimises every candidate of
+a batch in one launch on device tensors (optsim3_kernels.hip, one workgroup per candidate).
 """
 from __future__ import annotations
 
@@ -12,9 +16,10 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import POSE_CAMERA_DTYPE, POSE_DISCARD, POSE_RESULT_DTYPE
+from ._lib import OPTSIM3_PAIR_DTYPE, OPTSIM3_RESULT_DTYPE, POSE_CAMERA_DTYPE, POSE_DISCARD, POSE_RESULT_DTYPE, SIM3_VIEW_DTYPE
 
-__all__ = ["POSE_CAMERA_DTYPE", "POSE_RESULT_DTYPE", "POSE_DISCARD", "pose_camera", "pose_optimization", "pose_optimization_batch"]
+__all__ = ["POSE_CAMERA_DTYPE", "POSE_RESULT_DTYPE", "POSE_DISCARD", "pose_camera", "pose_optimization", "pose_optimization_batch",
+           "OPTSIM3_PAIR_DTYPE", "OPTSIM3_RESULT_DTYPE", "sim3_view", "optimize_sim3", "optimize_sim3_batch"]
 
 
 def pose_camera(fx, fy, cx, cy, mbf, inv_level_sigma2) -> np.ndarray:
@@ -67,3 +72,41 @@ def pose_optimization_batch(keys_un, u_right, n, assigned, points, n_points, cam
                                                                int(frame_shift), _lib.ptr(camera), _lib.ptr(Tcw_in), _lib.ptr(result),
                                                                _lib.ptr(outlier), int(flags), _lib.stream_handle(stream)),
                "orbfe_pose_optimization_batch_device")
+
+
+def sim3_view(Rcw, tcw, fx, fy, cx, cy) -> np.ndarray:
+    """One orbfe_sim3_view record: GetRotation() (row-major), GetTranslation() and mK of a KeyFrame."""
+    v = np.zeros(1, SIM3_VIEW_DTYPE)
+    v["Rcw"][0] = np.asarray(Rcw, np.float32).reshape(9)
+    v["tcw"][0] = np.asarray(tcw, np.float32).reshape(3)
+    v["fx"], v["fy"], v["cx"], v["cy"] = fx, fy, cx, cy
+    return v
+
+
+def optimize_sim3(view1, view2, pairs, s_R_t_in, th2, fix_scale):
+    """Optimizer::OptimizeSim3 of one loop candidate.  view1 / view2: sim3_view(...) of pKF1 / pKF2; pairs: OPTSIM3_PAIR_DTYPE (n), the
+    correspondences that passed the filters of Optimizer.cc:1436-1468; s_R_t_in: g2oS12 as 13 floats (scale, rotation row-major,
+    translation); th2: the chi-square bound.  Returns (result, bad): one OPTSIM3_RESULT_DTYPE record -- n_inliers is the reference's
+    return value, s / R / t are the input's bits when it is 0 by the fewer-than-10 rule -- and (n) uint8, 1 where the vpMatches1 entry
+    is nulled."""
+    v1 = np.ascontiguousarray(view1, SIM3_VIEW_DTYPE).reshape(1)
+    v2 = np.ascontiguousarray(view2, SIM3_VIEW_DTYPE).reshape(1)
+    pairs = np.ascontiguousarray(pairs, OPTSIM3_PAIR_DTYPE).reshape(-1)
+    n = len(pairs)
+    sRt = np.ascontiguousarray(np.asarray(s_R_t_in, np.float32).reshape(13))
+    res = np.zeros(1, OPTSIM3_RESULT_DTYPE)
+    bad = np.zeros(n, np.uint8)
+    _lib.check(_lib.lib().orbfe_optimize_sim3(_lib.ptr(v1), _lib.ptr(v2), _lib.ptr(pairs) if n else None, n, _lib.ptr(sRt), float(th2),
+                                              1 if fix_scale else 0, _lib.ptr(res), _lib.ptr(bad) if n else None), "orbfe_optimize_sim3")
+    return res[0], bad
+
+
+def optimize_sim3_batch(view1, view2, pairs, n, s_R_t_in, th2, fix_scale, result, bad, stream=None):
+    """orbfe_optimize_sim3_batch_device on torch CUDA tensors: view1, view2 (P,64) u8 = SIM3_VIEW_DTYPE, pairs (P,cap,48) u8 =
+    OPTSIM3_PAIR_DTYPE, n (P) i32, s_R_t_in (P,13) f32, th2 (P) f32, fix_scale (P) i32, result (P,80) u8 = OPTSIM3_RESULT_DTYPE, bad
+    (P,cap) u8.  Rows behind n[p] are neither read nor written.  stream: a torch.cuda.Stream, or None for the NULL stream."""
+    P, cap = int(pairs.shape[0]), int(pairs.shape[1])
+    _lib.check(_lib.lib().orbfe_optimize_sim3_batch_device(P, _lib.ptr(view1), _lib.ptr(view2), _lib.ptr(pairs), _lib.ptr(n), cap,
+                                                           _lib.ptr(s_R_t_in), _lib.ptr(th2), _lib.ptr(fix_scale), _lib.ptr(result),
+                                                           _lib.ptr(bad), _lib.stream_handle(stream)),
+               "orbfe_optimize_sim3_batch_device")
