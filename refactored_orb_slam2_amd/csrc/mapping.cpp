@@ -6,21 +6,11 @@
 #include <algorithm>
 #include <vector>
 
+#include "host_internal.h"
 #include "mapping_internal.h"
 #include "match_internal.h"
 
-void orbfe_set_error(const char* fmt, ...);
-
 #define TRI_MAX_ROWS 65535   // the descriptor limit of SearchForTriangulation (match_kernels.hip packs a position into 16 bits)
-
-static bool have_device() {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) {
-    orbfe_set_error("no HIP device available (liborbfe has no CPU fallback)");
-    return false;
-  }
-  return true;
-}
 
 static bool view_ok(const orbfe_tri_view* v, const char* what) {
   if (v->n_levels < 1 || v->n_levels > ORBFE_MAX_LEVELS) {
@@ -28,11 +18,6 @@ static bool view_ok(const orbfe_tri_view* v, const char* what) {
     return false;
   }
   return true;
-}
-
-static int hip_fail(const char* where, hipError_t e) {
-  orbfe_set_error("%s: %s", where, hipGetErrorString(e));
-  return ORBFE_ERR_HIP;
 }
 
 extern "C" int orbfe_triangulate_matches_batch_device(int K, const orbfe_tri_view* d_view1, const orbfe_keypoint* d_keys1,
@@ -74,11 +59,6 @@ extern "C" int orbfe_triangulate_matches_batch_device(int K, const orbfe_tri_vie
 }
 
 namespace {
-// offsets at 256-byte boundaries of one block
-struct Layout {
-  size_t off = 0;
-  size_t add(size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; }
-};
 // one device allocation, released on every path
 struct Staging {
   uint8_t* base = nullptr;

@@ -1,6 +1,5 @@
 // match_internal.h -- structs shared by matcher.cpp and match_kernels.hip
 #pragma once
-#include <mutex>
 #include <vector>
 
 #include "orbfe_internal.h"
@@ -121,7 +120,6 @@ struct TriSearchBuffers {       // device pointers of one search
 int orbfe_tri_search_plan(int nA, const orbfe_featvec_node* nodesA, int n_nodesA, const int32_t* idxA, int nB,
                           const orbfe_featvec_node* nodesB, int n_nodesB, const int32_t* idxB, TriSearchPlan& plan);
 int orbfe_tri_search_enqueue(const TriSearchBuffers& b, const orbfe_epipolar* ep, int check_orientation, int sequential, hipStream_t s);
-int orbfe_internal_thread_block(size_t bytes, std::unique_lock<std::mutex>& lk, hipStream_t* s, uint8_t** dev, uint8_t** pinned);
 void orbfe_launch_proj_best(const FrameBatch& f, const QueryBatch& q, int gate, const float* inv_sigma2, int32_t* best_idx,
                             int32_t* best_dist, int n_frames, hipStream_t s);
 void orbfe_launch_hamming_matrix(const uint8_t* A, int nA, const uint8_t* B, int nB, uint16_t* out, hipStream_t s);

@@ -14,10 +14,10 @@
 #include <mutex>
 #include <vector>
 
+#include "host_internal.h"
 #include "pipeline_internal.h"
 #include "match_internal.h"
 
-void orbfe_set_error(const char* fmt, ...);
 int orbfe_internal_pyr_view(const orbfe_extractor* e, PyrView* v, int* n_images);
 int orbfe_internal_tables(const orbfe_extractor* e, float* scale, float* inv_scale, int* n_levels, int* device);
 
@@ -57,11 +57,6 @@ static int pin_alloc(void*& p, size_t& have, size_t bytes) {
   have = bytes;
   return ORBFE_OK;
 }
-// lays parts out at 256-byte boundaries of a staging buffer
-struct Layout {
-  size_t off = 0;
-  size_t add(size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; }
-};
 // Results of the one-frame host entry points (stereo association, projection searches) leave the device staging block for its
 // pinned mirror by a copy kernel of four workgroups (pipeline_kernels.hip) instead of hipMemcpyAsync: the runtime's device-to-host
 // path costs ~8 us more per call (ComputeStereoMatches 0.088 -> 0.080 ms, SearchByProjection(cur, last) 0.181 -> 0.179 per frame;

@@ -2,29 +2,10 @@
 // points validate, stage and launch optsim3_kernels.hip.  No CPU fallback: without a device both forms are an error.
 #include <string.h>
 
-#include <mutex>
-
+#include "host_internal.h"
 #include "optsim3_internal.h"
 
-void orbfe_set_error(const char* fmt, ...);
-// the calling thread's matcher handle (matcher.cpp): its stream and a device block with a pinned mirror
-int orbfe_internal_thread_block(size_t bytes, std::unique_lock<std::mutex>& lk, hipStream_t* s, uint8_t** dev, uint8_t** pinned);
-
 #define OS_MAX_PAIRS 9500   // the frame limit of the projection searches (include/orbfe.h: hard limits)
-
-static bool have_device() {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) {
-    orbfe_set_error("no HIP device available (liborbfe has no CPU fallback)");
-    return false;
-  }
-  return true;
-}
-
-static int hip_fail(const char* where, hipError_t e) {
-  orbfe_set_error("%s: %s", where, hipGetErrorString(e));
-  return ORBFE_ERR_HIP;
-}
 
 extern "C" int orbfe_optimize_sim3_batch_device(int P, const orbfe_sim3_view* d_view1, const orbfe_sim3_view* d_view2,
                                                 const orbfe_optsim3_pair* d_pairs, const int32_t* d_n, int cap, const float* d_s_R_t_in,
@@ -54,14 +35,6 @@ extern "C" int orbfe_optimize_sim3_batch_device(int P, const orbfe_sim3_view* d_
   if (le != hipSuccess) return hip_fail("optimize sim3 batch: kernel launch failed", le);
   return ORBFE_OK;
 }
-
-namespace {
-// offsets at 256-byte boundaries of one block
-struct Layout {
-  size_t off = 0;
-  size_t add(size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; }
-};
-}  // namespace
 
 extern "C" int orbfe_optimize_sim3(const orbfe_sim3_view* view1, const orbfe_sim3_view* view2, const orbfe_optsim3_pair* pairs, int n,
                                    const float* s_R_t_in, float th2, int fix_scale, orbfe_optsim3_result* result, uint8_t* bad) {

@@ -9,21 +9,21 @@
 //   EdgeSim3ProjectXYZ / EdgeInverseSim3...       G/types/sim3/types_seven_dof_expmap.h:180-187, :201-209 (no linearizeOplus: :189, :211)
 //   project                                       G/types/slam3d/se3_ops.hpp:47-52
 //   numeric Jacobian (linearizeOplusN)            G/core/base_fixed_sized_edge.hpp:152-209
-//   quadratic form, Huber, Levenberg              as pose_internal.h cites them
-// The quaternion formulas (Quaternion(Matrix3), _transformVector, toRotationMatrix, the normalisation), the Huber kernel and the
-// Levenberg bookkeeping are pose_internal.h's; the camera-frame points are sim3_internal.h's float gemm (Optimizer.cc:1452, :1460).
-// BlockSolverX with LinearSolverEigen factorises the one 7 x 7 block with SimplicialLLT; here it is this project's unpivoted L D L^T
-// widened to 7, as the pose reading does for its dense solver.  A reading, unpinned.
+// Sim3 holds its rotation and translation as pose_internal.h's SE3Quat does, with that header's quaternion formulas; the optimiser
+// around the edges is lm_internal.h's, for a vertex of 7 dimensions; the camera-frame points are sim3_internal.h's float gemm
+// (Optimizer.cc:1452, :1460).  BlockSolverX with LinearSolverEigen factorises the one 7 x 7 block with SimplicialLLT; here it is
+// lm_internal.h's unpivoted L D L^T, as for the pose reading's dense solver.  A reading, unpinned.
 //
 // The edges have no analytic Jacobian: column d of both is the central difference (e(+delta e_d) - e(-delta e_d)) / (2 delta) with
 // delta = 1e-9 through oplus, i.e. through Sim3(update) * estimate.  With a fixed scale oplus zeroes update[6] before it is used, so
 // both perturbed estimates of column 6 are the same and the column is exactly zero: H[6][6] is lambda alone and x[6] == 0.
 // Sim3(Vector7) does not normalise its quaternion and operator* does not either; inverse() does (through the constructor).
 #pragma once
+#include "lm_internal.h"
 #include "pose_internal.h"
 #include "sim3_internal.h"
 
-#define OS_NACC 36       // 28 upper entries of H (row-major, i <= j), 7 of b, chi
+constexpr int OS_NACC = lm_nacc<7>;   // 28 upper entries of H, 7 of b, chi
 #define OS_NTRANSFORMS 15   // the estimate, then (+delta, -delta) of each of the 7 dimensions
 
 struct OsSim3 {   // g2o::Sim3: rotation and translation as PoseSE3 holds them, and the scale
@@ -200,83 +200,6 @@ __host__ __device__ inline double os_chi2(double e0, double e1, double w) { retu
 
 // scalar * (e(+) - e(-)) of linearizeOplusN, scalar = 1 / (2 * delta)
 __host__ __device__ inline double os_central(double ep, double em) { return (1 / (2 * 1e-9)) * (ep - em); }
-
-// constructQuadraticForm of one edge with its 2 x 7 Jacobian (rows J0, J1) into acc[OS_NACC]
-__host__ __device__ inline void os_edge_accumulate(const double* J0, const double* J1, double e0, double e1, double w, double rho0,
-                                                   double rho1, double* acc) {
-  const double ow = rho1 * w;                // robustInformation = rho[1] * information
-  const double we0 = (-(w * e0)) * rho1;     // omega_r = -information * error; omega_r *= rho[1]
-  const double we1 = (-(w * e1)) * rho1;
-  int k = 0;
-#pragma unroll
-  for (int i = 0; i < 7; i++) {
-    const double a0 = J0[i] * ow, a1 = J1[i] * ow;   // A^T * omega
-#pragma unroll
-    for (int j = i; j < 7; j++, k++) acc[k] += a0 * J0[j] + a1 * J1[j];
-  }
-#pragma unroll
-  for (int i = 0; i < 7; i++) acc[28 + i] += J0[i] * we0 + J1[i] * we1;
-  acc[35] += rho0;
-}
-
-// index of H[i][i] among the 28 upper entries
-__host__ __device__ constexpr int os_diag(int i) { return i * 7 - i * (i - 1) / 2; }
-
-// computeLambdaInit: tau * max |H_jj|
-__host__ __device__ inline double os_lambda_init(const double* Hu) {
-  double m = 0.0;
-#pragma unroll
-  for (int i = 0; i < 7; i++) m = fmax(fabs(Hu[os_diag(i)]), m);
-  return 1e-5 * m;
-}
-
-// (H + lambda I) x = b with H given by its 28 upper entries; false when a pivot is not > 0.  Fully unrolled: no run-time index.
-__host__ __device__ inline bool os_ldlt_solve(const double* Hu, double lambda, const double* b, double* x) {
-  double H[7][7], L[7][7], D[7], y[7];
-  {
-    int k = 0;
-#pragma unroll
-    for (int i = 0; i < 7; i++)
-#pragma unroll
-      for (int j = i; j < 7; j++, k++) {
-        H[i][j] = Hu[k];
-        H[j][i] = Hu[k];
-      }
-  }
-#pragma unroll
-  for (int j = 0; j < 7; j++) H[j][j] = H[j][j] + lambda;
-  bool ok = true;
-#pragma unroll
-  for (int j = 0; j < 7; j++) {
-    double d = H[j][j];
-#pragma unroll
-    for (int k = 0; k < j; k++) d -= L[j][k] * L[j][k] * D[k];
-    if (!(d > 0.0)) ok = false;
-    D[j] = d;
-#pragma unroll
-    for (int i = j + 1; i < 7; i++) {
-      double s = H[i][j];
-#pragma unroll
-      for (int k = 0; k < j; k++) s -= L[i][k] * L[j][k] * D[k];
-      L[i][j] = s / d;
-    }
-  }
-#pragma unroll
-  for (int i = 0; i < 7; i++) {
-    double s = b[i];
-#pragma unroll
-    for (int k = 0; k < i; k++) s -= L[i][k] * y[k];
-    y[i] = s;
-  }
-#pragma unroll
-  for (int i = 6; i >= 0; i--) {
-    double s = y[i] / D[i];
-#pragma unroll
-    for (int k = i + 1; k < 7; k++) s -= L[k][i] * x[k];
-    x[i] = s;
-  }
-  return ok;
-}
 
 // one correspondence from the caller's record: the camera-frame points in float, everything widened
 __host__ __device__ inline void os_prepare(const orbfe_sim3_view& V1, const orbfe_sim3_view& V2, const orbfe_optsim3_pair& p, float* c1,

@@ -1,7 +1,7 @@
 // optsim3_kernels.hip -- Optimizer::OptimizeSim3 (L/src/Optimizer.cc:1381-1573) for a batch of loop candidates: one 7-DoF similarity
 // vertex, two edges per correspondence (x1 = S12 X2 in image 1, x2 = S21 X1 in image 2) with numeric Jacobians, optimize(5), the
 // first classification, optimize(10 or 5) on the survivors and the second classification, all inside one launch.  The arithmetic
-// is optsim3_internal.h's.
+// is optsim3_internal.h's and, for the optimiser around the edges, lm_internal.h's.
 //
 // One workgroup of 256 threads per problem.  Lane t owns correspondences t, t + 256, ... and walks them in that order.  The first
 // 2 048 are prepared once into LDS as the floats they are (the two camera-frame points of the float gemm, the observations, the two
@@ -10,18 +10,18 @@
 // Per Levenberg iteration lanes 0 .. 14 of wave 0 build the estimate's 14 perturbed copies (+-1e-9 along each dimension, through
 // oplus) and the inverses of all 15 and put them in LDS; every lane then evaluates, per correspondence, the 2 x 15 projections, the
 // two 2 x 7 central-difference Jacobians and adds into the 28 upper entries of H, the 7 of b and chi, in double.  Every trial is
-// one pass for chi alone.  Reduction order: correspondence index -> lane (sequential, e12 before e21) -> xor butterfly inside the wave
-// (a + b == b + a, so every lane holds the same bits) -> the wave sums in wave order through LDS.  It depends on nothing but the
-// problem's own rows: a problem's result is byte-identical from run to run, at any position in a batch and for any batch size.  No
-// atomics.  H, b and chi are left in LDS; wave 0 runs the 7 x 7 solve, oplus and the inverse of a trial and hands them to the others
+// one pass for chi alone.  The sums are lm_reduce.h's, a lane adding e12 before e21: in an order that depends on nothing but the
+// problem's own rows, so a problem's result is byte-identical from run to run, at any position in a batch and for any batch size.
+// H, b and chi are left in LDS; wave 0 runs the 7 x 7 solve, oplus and the inverse of a trial and hands them to the others
 // through LDS; the Levenberg bookkeeping is repeated by every lane on those identical values, so control flow is uniform over the
-// workgroup, which is what lets the barriers sit inside the trial loop.  The 7 x 7 factorisation is fully unrolled and the Jacobian
-// of an edge passes through the lane's own LDS slots (an array indexed at run time lives in scratch memory, DESIGN lesson 58).
+// workgroup, which is what lets the barriers sit inside the trial loop.  The Jacobian of an edge passes through the lane's own LDS
+// slots (an array indexed at run time lives in scratch memory, DESIGN lesson 58).
 //
 // Deliberate deviation, the pose kernel's: after an optimize() call every correspondence is classified by its
 // chi2 at the call's final estimate.  The reference reads the error that the last Levenberg trial left in the edge, also when that
 // trial was rejected; such a step is taken at a large lambda and is tiny.
 #include "optsim3_internal.h"
+#include "lm_reduce.h"
 
 #ifndef OS_THREADS
 #define OS_THREADS 256   // 64 and 128 threads were measured against it: profiles/optimize_sim3.md
@@ -60,41 +60,6 @@ __device__ inline bool os_pair(const orbfe_sim3_view* views, const orbfe_optsim3
   return bad[i] != 0;
 }
 
-// The N sums of the workgroup, left in tot[0 .. N): lane order inside a wave by the xor butterfly, then the wave sums in wave order
-template <int N>
-__device__ inline void os_reduce(double* v, double* red, double* tot, int tid) {
-#pragma unroll
-  for (int k = 0; k < N; k++) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v[k] += __shfl_xor(v[k], off, 64);
-  }
-  __syncthreads();   // the readers of the reduction before are done
-  if ((tid & 63) == 0) {
-#pragma unroll
-    for (int k = 0; k < N; k++) red[(tid >> 6) * OS_NACC + k] = v[k];
-  }
-  __syncthreads();
-  if (tid < N) {
-    double s = red[tid];
-#pragma unroll
-    for (int w = 1; w < OS_WAVES; w++) s += red[w * OS_NACC + tid];
-    tot[tid] = s;
-  }
-  __syncthreads();
-}
-
-__device__ inline int os_reduce_count(int c, int* red, int tid) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) c += __shfl_xor(c, off, 64);
-  __syncthreads();
-  if ((tid & 63) == 0) red[tid >> 6] = c;
-  __syncthreads();
-  int s = 0;
-#pragma unroll
-  for (int w = 0; w < OS_WAVES; w++) s += red[w];
-  return s;
-}
-
 // One edge at the 15 transforms T[0 .. 15) into acc: error and chi2 at T[0], column d of the Jacobian from T[1 + 2 d], T[2 + 2 d].
 // The loop over the columns is a real loop -- unrolled, the edge's 15 transforms (120 doubles, invariant in the loop over the
 // correspondences) are read ahead of that loop, their projections scheduled together, and they spill -- so the 14 entries of the
@@ -118,8 +83,8 @@ __device__ inline void os_edge(const OsSim3* T, const OsCam& K, double X, double
     J1[d] = J[(2 * d + 1) * OS_THREADS];
   }
   double rho0, rho1;
-  pose_huber(os_chi2(e0, e1, w), delta, &rho0, &rho1);
-  os_edge_accumulate(J0, J1, e0, e1, w, rho0, rho1, acc);
+  lm_huber(os_chi2(e0, e1, w), delta, &rho0, &rho1);
+  lm_accumulate<7>(J0, J1, J0, false, e0, e1, 0.0, w, rho0, rho1, acc);   // two rows: the third J0 is a stand-in
 }
 
 __device__ inline double os_edge_chi2(const OsSim3& S, const OsCam& K, double X, double Y, double Z, double ou, double ov, double w) {
@@ -196,7 +161,7 @@ __global__ __launch_bounds__(OS_THREADS) void optimize_sim3_kernel(OsLaunch L) {
   int n_bad = 0;
   for (int call = 0; call < 2; call++) {
     const int max_its = call == 0 ? 5 : (n_bad > 0 ? 10 : 5);   // Optimizer.cc:1518, :1539-1551
-    PoseLM lm;
+    LmState lm;
     lm.lambda = 0.0;
     lm.ni = 2.0;
     int its = 0;
@@ -216,10 +181,10 @@ __global__ __launch_bounds__(OS_THREADS) void optimize_sim3_kernel(OsLaunch L) {
         os_edge(sh_T, K1, E.x2, E.y2, E.z2, E.u1, E.v1, E.w1, delta, sh_J + tid, acc);                    // e12
         os_edge(sh_T + OS_NTRANSFORMS, K2, E.x1, E.y1, E.z1, E.u2, E.v2, E.w2, delta, sh_J + tid, acc);   // e21
       }
-      os_reduce<OS_NACC>(acc, red, Hb, tid);
-      double current_chi = Hb[35];
+      lm_reduce<OS_NACC, OS_NACC, OS_WAVES>(acc, red, Hb, tid);
+      double current_chi = Hb[lm_chi<7>];
       if (it == 0) {
-        lm.lambda = os_lambda_init(Hb);
+        lm.lambda = lm_lambda_init<7>(Hb);
         lm.ni = 2.0;
       }
       double rho = 0.0;
@@ -227,7 +192,7 @@ __global__ __launch_bounds__(OS_THREADS) void optimize_sim3_kernel(OsLaunch L) {
       do {
         if (tid < 64) {   // the 7 x 7 solve, oplus and the inverse: one wave
           double xs[7];
-          const bool ok = os_ldlt_solve(Hb, lm.lambda, Hb + 28, xs);
+          const bool ok = lm_ldlt_solve<7>(Hb, lm.lambda, Hb + lm_b<7>, xs);
           OsSim3 t = S;
           if (ok) t = os_oplus(S, xs, fix_scale);
           const OsSim3 ti = os_inverse(t);
@@ -252,15 +217,15 @@ __global__ __launch_bounds__(OS_THREADS) void optimize_sim3_kernel(OsLaunch L) {
             OsPair E;
             if (os_pair(views, pairs, bad, cache, i, E)) continue;
             double rho0, rho1;
-            pose_huber(os_edge_chi2(trial, K1, E.x2, E.y2, E.z2, E.u1, E.v1, E.w1), delta, &rho0, &rho1);
+            lm_huber(os_edge_chi2(trial, K1, E.x2, E.y2, E.z2, E.u1, E.v1, E.w1), delta, &rho0, &rho1);
             temp_chi += rho0;
-            pose_huber(os_edge_chi2(trial_inv, K2, E.x1, E.y1, E.z1, E.u2, E.v2, E.w2), delta, &rho0, &rho1);
+            lm_huber(os_edge_chi2(trial_inv, K2, E.x1, E.y1, E.z1, E.u2, E.v2, E.w2), delta, &rho0, &rho1);
             temp_chi += rho0;
           }
-          os_reduce<1>(&temp_chi, red, &chi_t, tid);
+          lm_reduce<1, OS_NACC, OS_WAVES>(&temp_chi, red, &chi_t, tid);
           temp_chi = chi_t;
         }
-        if (pose_lm_trial_n<7>(lm, ok2, current_chi, temp_chi, x, Hb + 28, &rho)) {
+        if (lm_trial<7>(lm, ok2, current_chi, temp_chi, x, Hb + lm_b<7>, &rho)) {
           current_chi = temp_chi;
           S = trial;
         } else if (!isfinite(lm.lambda)) {
@@ -289,7 +254,7 @@ __global__ __launch_bounds__(OS_THREADS) void optimize_sim3_kernel(OsLaunch L) {
         nb++;
       }
     }
-    nb = os_reduce_count(nb, red_i, tid);
+    nb = lm_reduce_count<OS_WAVES>(nb, red_i, tid);
     if (call == 0) {
       n_bad = nb;
       res.n_bad = nb;

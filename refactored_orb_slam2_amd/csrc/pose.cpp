@@ -1,24 +1,14 @@
 // pose.cpp -- C ABI of Optimizer::PoseOptimization (include/orbfe.h: orbfe_pose_optimization*).  Both entry points validate and
 // launch pose_kernels.hip; the host form stages one frame through device memory around the same launch.  No CPU fallback: without
 // a device both are an error.
+#include "host_internal.h"
 #include "pose_internal.h"
-
-void orbfe_set_error(const char* fmt, ...);
 
 #define POSE_MAX_ROWS 9500   // the frame limit of the projection searches (matcher.cpp), whose output this call reads
 
 static bool stride_ok(int point_stride) {
   if (point_stride < 12 || (point_stride & 3)) {
     orbfe_set_error("pose optimisation: point_stride %d (at least 12 bytes -- three floats -- and a multiple of 4)", point_stride);
-    return false;
-  }
-  return true;
-}
-
-static bool have_device() {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) {
-    orbfe_set_error("no HIP device available (liborbfe has no CPU fallback)");
     return false;
   }
   return true;

@@ -8,22 +8,19 @@
 //   EdgeStereoSE3ProjectXYZOnlyPose        G/types/sba/edge_project_stereo_xyz_onlypose.cpp:59-109
 //   SE3Quat (map, exp, operator*)          G/types/slam3d/se3quat.h:53-56, :97-103, :200-230, :251-256
 //   VertexSE3Expmap::oplusImpl             G/types/sba/vertex_se3_expmap.cpp:48-51
-//   RobustKernelHuber::robustify           G/core/robust_kernel_impl.cpp:60-74
-//   quadratic form                         G/core/base_fixed_sized_edge.hpp:49-63, :114-130; G/core/base_edge.h:156-162
-//   OptimizationAlgorithmLevenberg::solve  G/core/optimization_algorithm_levenberg.cpp:60-176
-//   LinearSolverDense::solve               G/solvers/dense/linear_solver_dense.h:96-104
+// The Huber kernel, the quadratic form, the Levenberg bookkeeping and the dense solve are lm_internal.h's, for a vertex of 6 dimensions.
 // Neither Eigen nor g2o can be built where this library is built: the quaternion formulas are Eigen's (Quaternion(Matrix3),
-// toRotationMatrix, _transformVector, operator*), fixed-size products are taken in index order, and the dense solver is an
-// unpivoted L D L^T (Eigen::LDLT pivots on the largest diagonal; both report failure on a non-positive pivot).  A reading,
-// unpinned.  theta^3 of SE3Quat::exp is theta * theta * theta, not pow(theta, 3).
+// toRotationMatrix, _transformVector, operator*) and fixed-size products are taken in index order.  A reading, unpinned (DESIGN
+// section 2).  theta^3 of SE3Quat::exp is theta * theta * theta, not pow(theta, 3).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
 
 #include "../../include/orbfe.h"
+#include "lm_internal.h"
 
-#define POSE_NACC 28   // 21 upper entries of H (row-major, i <= j), 6 of b, chi
+constexpr int POSE_NACC = lm_nacc<6>;   // 21 upper entries of H, 6 of b, chi
 
 struct PoseSE3 {   // g2o::SE3Quat: unit quaternion (w >= 0) and translation
   double qx, qy, qz, qw;
@@ -196,19 +193,6 @@ __host__ __device__ inline PoseSE3 pose_exp(const double* u) {
   return p;
 }
 
-// RobustKernelHuber::robustify: rho[0] and rho[1]
-__host__ __device__ inline void pose_huber(double e, double delta, double* rho0, double* rho1) {
-  const double dsqr = delta * delta;
-  if (e <= dsqr) {
-    *rho0 = e;
-    *rho1 = 1.0;
-  } else {
-    const double sqrte = sqrt(e);
-    *rho0 = 2 * sqrte * delta - dsqr;
-    *rho1 = delta / sqrte;
-  }
-}
-
 // One edge as the optimiser holds it: the observation and Xw are the Frame's / the MapPoint's floats widened, w = mvInvLevelSigma2
 struct PoseEdge {
   double ou, ov, our;   // mvKeysUn[i].pt, mvuRight[i]
@@ -237,12 +221,11 @@ __host__ __device__ inline double pose_edge_error(const PoseEdge& E, const PoseI
   return e[0] * (E.w * e[0]) + e[1] * (E.w * e[1]);
 }
 
-// linearizeOplus + constructQuadraticForm of one edge into acc[POSE_NACC]; rho1 = 1 without a robust kernel, rho0 = chi2 then
-__host__ __device__ inline void pose_edge_accumulate(const PoseEdge& E, const PoseIntr& K, const double* e, double x, double y, double z,
-                                                     double rho0, double rho1, double* acc) {
+// linearizeOplus of one edge at the camera-frame point (x, y, z): the rows of its Jacobian (J2: the stereo edge's third), which the
+// caller hands to lm_accumulate<6> with E.stereo, e, E.w and the robust kernel's rho
+__host__ __device__ inline void pose_edge_jacobian(const PoseIntr& K, double x, double y, double z, double* J0, double* J1, double* J2) {
   const double invz = 1.0 / z;
   const double invz_2 = invz * invz;
-  double J0[6], J1[6], J2[6];
   J0[0] = x * y * invz_2 * K.fx;
   J0[1] = -(1 + (x * x * invz_2)) * K.fx;
   J0[2] = y * invz * K.fx;
@@ -261,116 +244,6 @@ __host__ __device__ inline void pose_edge_accumulate(const PoseEdge& E, const Po
   J2[3] = J0[3];
   J2[4] = 0;
   J2[5] = J0[5] - K.bf * invz_2;
-  const double ow = rho1 * E.w;                 // robustInformation = rho[1] * information
-  const double we0 = (-(E.w * e[0])) * rho1;    // omega_r = -information * error; omega_r *= rho[1]
-  const double we1 = (-(E.w * e[1])) * rho1;
-  const double we2 = (-(E.w * e[2])) * rho1;
-  int k = 0;
-#pragma unroll
-  for (int i = 0; i < 6; i++) {
-    const double a0 = J0[i] * ow, a1 = J1[i] * ow, a2 = J2[i] * ow;   // A^T * omega
-#pragma unroll
-    for (int j = i; j < 6; j++, k++) {
-      double h = a0 * J0[j] + a1 * J1[j];
-      if (E.stereo) h = h + a2 * J2[j];
-      acc[k] += h;
-    }
-  }
-#pragma unroll
-  for (int i = 0; i < 6; i++) {
-    double g = J0[i] * we0 + J1[i] * we1;
-    if (E.stereo) g = g + J2[i] * we2;
-    acc[21 + i] += g;
-  }
-  acc[27] += rho0;
-}
-
-// (H + lambda I) x = b with H given by its 21 upper entries; false when a pivot is not > 0.  Fully unrolled: no run-time index.
-__host__ __device__ inline bool pose_ldlt_solve(const double* Hu, double lambda, const double* b, double* x) {
-  double H[6][6], L[6][6], D[6], y[6];
-  {
-    int k = 0;
-#pragma unroll
-    for (int i = 0; i < 6; i++)
-#pragma unroll
-      for (int j = i; j < 6; j++, k++) {
-        H[i][j] = Hu[k];
-        H[j][i] = Hu[k];
-      }
-  }
-#pragma unroll
-  for (int j = 0; j < 6; j++) H[j][j] = H[j][j] + lambda;
-  bool ok = true;
-#pragma unroll
-  for (int j = 0; j < 6; j++) {
-    double d = H[j][j];
-#pragma unroll
-    for (int k = 0; k < j; k++) d -= L[j][k] * L[j][k] * D[k];
-    if (!(d > 0.0)) ok = false;
-    D[j] = d;
-#pragma unroll
-    for (int i = j + 1; i < 6; i++) {
-      double s = H[i][j];
-#pragma unroll
-      for (int k = 0; k < j; k++) s -= L[i][k] * L[j][k] * D[k];
-      L[i][j] = s / d;
-    }
-  }
-#pragma unroll
-  for (int i = 0; i < 6; i++) {
-    double s = b[i];
-#pragma unroll
-    for (int k = 0; k < i; k++) s -= L[i][k] * y[k];
-    y[i] = s;
-  }
-#pragma unroll
-  for (int i = 5; i >= 0; i--) {
-    double s = y[i] / D[i];
-#pragma unroll
-    for (int k = i + 1; k < 6; k++) s -= L[k][i] * x[k];
-    x[i] = s;
-  }
-  return ok;
-}
-
-// The state of OptimizationAlgorithmLevenberg across the iterations of one optimize() call
-struct PoseLM {
-  double lambda, ni;
-};
-
-// Good / bad step bookkeeping of one trial (optimization_algorithm_levenberg.cpp:125-146) for a vertex of N dimensions (6: the pose,
-// 7: the similarity of optsim3_internal.h).  Returns true when the step is accepted.
-template <int N>
-__host__ __device__ inline bool pose_lm_trial_n(PoseLM& lm, bool ok2, double current_chi, double temp_chi, const double* x, const double* b,
-                                                double* rho_out) {
-  double scale = 1.0;
-  if (ok2) {
-    scale = 0.0;
-#pragma unroll
-    for (int j = 0; j < N; j++) scale += x[j] * (lm.lambda * x[j] + b[j]);   // computeScale
-    scale = scale + 1e-3;
-  } else {
-    temp_chi = 1.7976931348623157e308;   // std::numeric_limits<double>::max()
-  }
-  const double rho = (current_chi - temp_chi) / scale;
-  *rho_out = rho;
-  if (rho > 0 && isfinite(temp_chi) && ok2) {
-    const double c = 2 * rho - 1;
-    double alpha = 1. - c * c * c;       // pow(2 rho - 1, 3)
-    alpha = alpha < 2. / 3. ? alpha : 2. / 3.;
-    const double f = 1. / 3. < alpha ? alpha : 1. / 3.;
-    lm.lambda *= f;
-    lm.ni = 2;
-    return true;
-  }
-  lm.lambda *= lm.ni;
-  lm.ni *= 2;
-  return false;
-}
-
-__host__ __device__ inline bool pose_lm_trial(PoseLM& lm, bool ok2, double current_chi, double temp_chi, const double* x, const double* b,
-                                              double* rho_out) {
-  return pose_lm_trial_n<6>(lm, ok2, current_chi, temp_chi, x, b, rho_out);
 }
 
 void orbfe_launch_pose_optimize(int n_frames, const orbfe_keypoint* keys_un, const float* u_right, const int32_t* n, int cap,

@@ -1,25 +1,23 @@
 // pose_kernels.hip -- Optimizer::PoseOptimization (L/src/Optimizer.cc:233-435) for a batch of frames: one 6-DoF vertex, one unary
 // edge per keypoint with a map point, four rounds of up to ten Levenberg iterations with up to ten trials each, all inside one
-// launch.  The arithmetic is pose_internal.h's.
+// launch.  The arithmetic is pose_internal.h's and, for the optimiser around the edges, lm_internal.h's.
 //
 // One workgroup of 512 threads per frame.  Lane t owns keypoint rows t, t + 512, ... and walks them in that order.  The edges of the
 // first 2 048 rows are gathered once into LDS (keypoint, mvuRight, assignment -> point record: 7 floats and a flag byte per row); a
 // row behind them is re-read from global memory for every evaluation, so no per-frame workspace exists and `cap` is bounded by
 // nothing but the library's frame limit.  An iteration is one pass that accumulates the 21 upper entries of H, the 6 of b and chi in
-// double, and every trial one pass for chi alone.  Reduction order: keypoint index -> lane (sequential) -> xor butterfly inside the
-// wave (a + b == b + a, so every lane holds the same bits) -> the wave sums in wave order through LDS.  It depends on nothing but
-// the frame's own rows: a frame's result is byte-identical from run to run, at any position in a batch and for any batch size.  No
-// atomics.
+// double, and every trial one pass for chi alone.  The sums are lm_reduce.h's: in an order that depends on nothing but the frame's
+// own rows, so a frame's result is byte-identical from run to run, at any position in a batch and for any batch size.
 // H, b and chi are left in LDS.  One wave runs the 6 x 6 solve, exp and the pose update of a trial and hands x and the trial pose
 // to the others through LDS; the Levenberg bookkeeping (a few operations) is repeated by every lane on those identical values, so
-// control flow is uniform over the workgroup by construction, which is what lets the barriers sit inside the trial loop.  The
-// 6 x 6 factorisation is fully unrolled (a matrix indexed at run time lives in scratch memory, DESIGN lesson 58); mvInvLevelSigma2
-// is indexed per lane and therefore read from LDS, not from a by-value argument.
+// control flow is uniform over the workgroup by construction, which is what lets the barriers sit inside the trial loop.
+// mvInvLevelSigma2 is indexed per lane and therefore read from LDS, not from a by-value argument.
 // Level (0 / 1) of an edge between rounds = a flag bit in LDS (outlier[row] for a row behind the cache), which its own lane wrote.
 //
 // Deliberate deviation: after a round every edge is classified by its chi2 at the round's final pose.  The
 // reference reads, for a level-0 edge, the error its last trial left behind (also a rejected one); the difference is ~1e-10.
 #include "pose_internal.h"
+#include "lm_reduce.h"
 
 #ifndef PO_THREADS
 #define PO_THREADS 512   // 64, 256 and 1 024 threads were measured against it: profiles/pose_optimization.md
@@ -82,43 +80,6 @@ __device__ inline bool po_edge(const PoRows& F, const PoCache& C, const float* s
   return true;
 }
 
-// The N sums of the workgroup, left in tot[0 .. N): lane order inside a wave by the xor butterfly, then the wave sums in wave order.
-// H, b and chi stay in LDS and are read from there (uniform addresses: broadcasts) -- 28 doubles less per lane to keep in registers
-// across the trial loop, which is what lets two waves share a SIMD.
-template <int N>
-__device__ inline void po_reduce(double* v, double* red, double* tot, int tid) {
-#pragma unroll
-  for (int k = 0; k < N; k++) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v[k] += __shfl_xor(v[k], off, 64);
-  }
-  __syncthreads();   // the readers of the reduction before are done
-  if ((tid & 63) == 0) {
-#pragma unroll
-    for (int k = 0; k < N; k++) red[(tid >> 6) * POSE_NACC + k] = v[k];
-  }
-  __syncthreads();
-  if (tid < N) {
-    double s = red[tid];
-#pragma unroll
-    for (int w = 1; w < PO_WAVES; w++) s += red[w * POSE_NACC + tid];
-    tot[tid] = s;
-  }
-  __syncthreads();
-}
-
-__device__ inline int po_reduce_count(int c, int* red, int tid) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) c += __shfl_xor(c, off, 64);
-  __syncthreads();
-  if ((tid & 63) == 0) red[tid >> 6] = c;
-  __syncthreads();
-  int s = 0;
-#pragma unroll
-  for (int w = 0; w < PO_WAVES; w++) s += red[w];
-  return s;
-}
-
 __global__ __launch_bounds__(PO_THREADS) void pose_optimize_kernel(int n_frames, const orbfe_keypoint* __restrict__ keys_un,
                                                                    const float* __restrict__ u_right, const int32_t* __restrict__ n_rows,
                                                                    int cap, int32_t* assigned, const uint8_t* __restrict__ points,
@@ -178,7 +139,7 @@ __global__ __launch_bounds__(PO_THREADS) void pose_optimize_kernel(int n_frames,
       }
     }
   }
-  const int n_initial = po_reduce_count(cnt, red_i, tid);
+  const int n_initial = lm_reduce_count<PO_WAVES>(cnt, red_i, tid);
   const float* Tin = Tcw_in + (size_t)f * 12;
   if (n_initial < 3) {   // Optimizer.cc:357: return 0, the pose is not touched
     if (tid == 0) {
@@ -201,7 +162,7 @@ __global__ __launch_bounds__(PO_THREADS) void pose_optimize_kernel(int n_frames,
   bool robust = true;
   for (int rnd = 0; rnd < 4; rnd++) {
     pose = pose0;   // Optimizer.cc:370: every round starts from the input pose
-    PoseLM lm;
+    LmState lm;
     lm.lambda = 0.0;
     lm.ni = 2.0;
     const int n_active = n_initial - n_bad;   // the level-0 edges
@@ -216,20 +177,15 @@ __global__ __launch_bounds__(PO_THREADS) void pose_optimize_kernel(int n_frames,
         double e[3], x, y, z, rho0, rho1 = 1.0;
         const double chi2 = pose_edge_error(E, K, pose, e, &x, &y, &z);
         rho0 = chi2;
-        if (robust) pose_huber(chi2, pose_delta(E.stereo), &rho0, &rho1);
-        pose_edge_accumulate(E, K, e, x, y, z, rho0, rho1, acc);
+        if (robust) lm_huber(chi2, pose_delta(E.stereo), &rho0, &rho1);
+        double J[3][6];   // linearizeOplus, then constructQuadraticForm
+        pose_edge_jacobian(K, x, y, z, J[0], J[1], J[2]);
+        lm_accumulate<6>(J[0], J[1], J[2], E.stereo, e[0], e[1], e[2], E.w, rho0, rho1, acc);
       }
-      po_reduce<POSE_NACC>(acc, red, Hb, tid);
-      double current_chi = Hb[27];
-      if (it == 0) {   // computeLambdaInit: tau * max |H_jj|
-        double m = 0.0;
-        m = fmax(fabs(Hb[0]), m);
-        m = fmax(fabs(Hb[6]), m);
-        m = fmax(fabs(Hb[11]), m);
-        m = fmax(fabs(Hb[15]), m);
-        m = fmax(fabs(Hb[18]), m);
-        m = fmax(fabs(Hb[20]), m);
-        lm.lambda = 1e-5 * m;
+      lm_reduce<POSE_NACC, POSE_NACC, PO_WAVES>(acc, red, Hb, tid);
+      double current_chi = Hb[lm_chi<6>];
+      if (it == 0) {
+        lm.lambda = lm_lambda_init<6>(Hb);
         lm.ni = 2.0;
       }
       double rho = 0.0;
@@ -238,7 +194,7 @@ __global__ __launch_bounds__(PO_THREADS) void pose_optimize_kernel(int n_frames,
         // the 6 x 6 solve, exp and the pose update: one wave; every wave of a SIMD repeating them would take that SIMD's time again
         if (tid < 64) {
           double xs[6];
-          const bool ok = pose_ldlt_solve(Hb, lm.lambda, Hb + 21, xs);
+          const bool ok = lm_ldlt_solve<6>(Hb, lm.lambda, Hb + lm_b<6>, xs);
           PoseSE3 t = pose;
           if (ok) t = pose_mul(pose_exp(xs), pose);   // oplus
           if (tid == 0) {
@@ -264,13 +220,13 @@ __global__ __launch_bounds__(PO_THREADS) void pose_optimize_kernel(int n_frames,
             double e[3], px, py, pz, rho0, rho1;
             const double chi2 = pose_edge_error(E, K, trial, e, &px, &py, &pz);
             rho0 = chi2;
-            if (robust) pose_huber(chi2, pose_delta(E.stereo), &rho0, &rho1);
+            if (robust) lm_huber(chi2, pose_delta(E.stereo), &rho0, &rho1);
             temp_chi += rho0;
           }
-          po_reduce<1>(&temp_chi, red, &chi_t, tid);
+          lm_reduce<1, POSE_NACC, PO_WAVES>(&temp_chi, red, &chi_t, tid);
           temp_chi = chi_t;
         }
-        if (pose_lm_trial(lm, ok2, current_chi, temp_chi, x, Hb + 21, &rho)) {
+        if (lm_trial<6>(lm, ok2, current_chi, temp_chi, x, Hb + lm_b<6>, &rho)) {
           current_chi = temp_chi;
           pose = trial;
         } else if (!isfinite(lm.lambda)) {
@@ -294,7 +250,7 @@ __global__ __launch_bounds__(PO_THREADS) void pose_optimize_kernel(int n_frames,
       if (i < PO_LDS_ROWS) cache.flags[i] = (uint8_t)((E.stereo ? 3 : 1) | (o ? 4 : 0));
       bad += o;
     }
-    n_bad = po_reduce_count(bad, red_i, tid);
+    n_bad = lm_reduce_count<PO_WAVES>(bad, red_i, tid);
     if (rnd == 2) robust = false;
     rounds++;
     if (n_initial < 10) break;   // Optimizer.cc:423

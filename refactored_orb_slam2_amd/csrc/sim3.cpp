@@ -4,29 +4,11 @@
 #include <string.h>
 
 #include <algorithm>
-#include <mutex>
 
+#include "host_internal.h"
 #include "sim3_internal.h"
 
-void orbfe_set_error(const char* fmt, ...);
-// the calling thread's matcher handle (matcher.cpp): its stream and a device block with a pinned mirror
-int orbfe_internal_thread_block(size_t bytes, std::unique_lock<std::mutex>& lk, hipStream_t* s, uint8_t** dev, uint8_t** pinned);
-
 #define SIM3_MAX_PROBLEMS 65535   // grid.y
-
-static bool have_device() {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) {
-    orbfe_set_error("no HIP device available (liborbfe has no CPU fallback)");
-    return false;
-  }
-  return true;
-}
-
-static int hip_fail(const char* where, hipError_t e) {
-  orbfe_set_error("%s: %s", where, hipGetErrorString(e));
-  return ORBFE_ERR_HIP;
-}
 
 // Sim3Solver::SetRansacParameters (L/src/Sim3Solver.cc:112-136)
 extern "C" int orbfe_sim3_ransac_iterations(int N, double probability, int min_inliers, int max_iterations) {
@@ -81,14 +63,6 @@ extern "C" int orbfe_sim3_solve_batch_device(int P, const orbfe_sim3_view* d_vie
   if (le != hipSuccess) return hip_fail("sim3 batch: kernel launch failed", le);
   return ORBFE_OK;
 }
-
-namespace {
-// offsets at 256-byte boundaries of one block
-struct Layout {
-  size_t off = 0;
-  size_t add(size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; }
-};
-}  // namespace
 
 extern "C" int orbfe_sim3_solve(const orbfe_sim3_view* view1, const orbfe_sim3_view* view2, const orbfe_sim3_pair* pairs, int n,
                                 const int32_t* triples, int H, int fix_scale, int min_inliers, orbfe_sim3_hypothesis* hyps,

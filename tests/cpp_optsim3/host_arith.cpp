@@ -1,6 +1,7 @@
-// host_arith.cpp -- csrc/optsim3_internal.h compiled for the HOST: the loops that optsim3_kernels.hip spreads over the lanes of a
-// workgroup, sequential here, so that the arithmetic the kernel executes can be compared with the numpy yardstick on a machine
-// without a GPU (tests/test_optsim3_cpu.py).  Same flags as the library (-ffp-contract=off).  Sums run in correspondence order.
+// host_arith.cpp -- csrc/optsim3_internal.h, with the lm_internal.h under it, compiled for the HOST: the loops that
+// optsim3_kernels.hip spreads over the lanes of a workgroup, sequential here, so that the arithmetic the kernel executes can be
+// compared with the numpy yardstick on a machine without a GPU (tests/test_optsim3_cpu.py).  Same flags as the library
+// (-ffp-contract=off).  Sums run in correspondence order.
 #include <stddef.h>
 #include <string.h>
 
@@ -28,8 +29,8 @@ void edge(const OsSim3* T, const OsCam& K, double X, double Y, double Z, double 
     J1[d] = os_central(p1, m1);
   }
   double rho0, rho1;
-  pose_huber(os_chi2(e0, e1, w), delta, &rho0, &rho1);
-  os_edge_accumulate(J0, J1, e0, e1, w, rho0, rho1, acc);
+  lm_huber(os_chi2(e0, e1, w), delta, &rho0, &rho1);
+  lm_accumulate<7>(J0, J1, J0, false, e0, e1, 0.0, w, rho0, rho1, acc);   // two rows: the third J0 is a stand-in
 }
 
 double edge_chi2(const OsSim3& S, const OsCam& K, double X, double Y, double Z, double ou, double ov, double w) {
@@ -44,9 +45,9 @@ double robust_chi(const Problem& P, const OsSim3& S) {
   for (size_t i = 0; i < P.E.size(); i++) {
     if (P.bad[i]) continue;
     const OsPair& E = P.E[i];
-    pose_huber(edge_chi2(S, P.K1, E.x2, E.y2, E.z2, E.u1, E.v1, E.w1), P.delta, &rho0, &rho1);
+    lm_huber(edge_chi2(S, P.K1, E.x2, E.y2, E.z2, E.u1, E.v1, E.w1), P.delta, &rho0, &rho1);
     chi += rho0;
-    pose_huber(edge_chi2(Si, P.K2, E.x1, E.y1, E.z1, E.u2, E.v2, E.w2), P.delta, &rho0, &rho1);
+    lm_huber(edge_chi2(Si, P.K2, E.x1, E.y1, E.z1, E.u2, E.v2, E.w2), P.delta, &rho0, &rho1);
     chi += rho0;
   }
   return chi;
@@ -87,7 +88,7 @@ extern "C" void optsim3_host(const orbfe_sim3_view* view1, const orbfe_sim3_view
   int n_bad = 0;
   for (int call = 0; call < 2; call++) {
     const int max_its = call == 0 ? 5 : (n_bad > 0 ? 10 : 5);
-    PoseLM lm{0.0, 2.0};
+    LmState lm{0.0, 2.0};
     int its = 0;
     for (int it = 0; it < max_its; it++) {
       OsSim3 T[2 * OS_NTRANSFORMS];
@@ -102,20 +103,20 @@ extern "C" void optsim3_host(const orbfe_sim3_view* view1, const orbfe_sim3_view
         edge(T, P.K1, E.x2, E.y2, E.z2, E.u1, E.v1, E.w1, P.delta, Hb);
         edge(T + OS_NTRANSFORMS, P.K2, E.x1, E.y1, E.z1, E.u2, E.v2, E.w2, P.delta, Hb);
       }
-      double current_chi = Hb[35];
+      double current_chi = Hb[lm_chi<7>];
       if (it == 0) {
-        lm.lambda = os_lambda_init(Hb);
+        lm.lambda = lm_lambda_init<7>(Hb);
         lm.ni = 2.0;
       }
       double rho = 0.0;
       int qmax = 0;
       do {
         double x[7];
-        const bool ok2 = os_ldlt_solve(Hb, lm.lambda, Hb + 28, x);
+        const bool ok2 = lm_ldlt_solve<7>(Hb, lm.lambda, Hb + lm_b<7>, x);
         OsSim3 trial = S;
         if (ok2) trial = os_oplus(S, x, P.fix_scale);
         const double temp_chi = ok2 ? robust_chi(P, trial) : 0.0;
-        if (pose_lm_trial_n<7>(lm, ok2, current_chi, temp_chi, x, Hb + 28, &rho)) {
+        if (lm_trial<7>(lm, ok2, current_chi, temp_chi, x, Hb + lm_b<7>, &rho)) {
           current_chi = temp_chi;
           S = trial;
         } else if (!isfinite(lm.lambda)) {
@@ -162,6 +163,14 @@ extern "C" void optsim3_host_exp(const double* u, double* out) {
   const OsSim3 S = os_exp(u);
   out[0] = S.q.qx; out[1] = S.q.qy; out[2] = S.q.qz; out[3] = S.q.qw;
   out[4] = S.q.tx; out[5] = S.q.ty; out[6] = S.q.tz; out[7] = S.s;
+}
+
+// lm_internal.h's solve alone, for a vertex of n = 6 or 7 dimensions: (H + lambda I) x = b with H as its n (n + 1) / 2 upper entries.
+// Returns 1 when every pivot was > 0, 0 when one was not, -1 for another n.
+extern "C" int optsim3_host_ldlt(int n, const double* Hu, double lambda, const double* b, double* x) {
+  if (n == 6) return lm_ldlt_solve<6>(Hu, lambda, b, x) ? 1 : 0;
+  if (n == 7) return lm_ldlt_solve<7>(Hu, lambda, b, x) ? 1 : 0;
+  return -1;
 }
 
 // sizeof of the two records of include/orbfe.h, for the layout check of the ctypes side

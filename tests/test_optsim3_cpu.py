@@ -1,7 +1,8 @@
 """CPU suite of the Sim3 optimisation: the numpy reading of tests/np_optsim3.py against closed-form answers, the three conditions that
 make a case a parity case (margin, stability, coverage) ASSERTED on the whole case list, csrc/optsim3_internal.h compiled for the
-host against the reading with the criterion of the GPU test, and the C ABI without a device: struct sizes, exports, every validation
-boundary, ORBFE_ERR_NO_DEVICE from both entry points."""
+host against the reading with the criterion of the GPU test, the solve it shares with the pose kernel (csrc/lm_internal.h) against
+numpy, and the C ABI without a device: struct sizes, exports, every validation boundary, ORBFE_ERR_NO_DEVICE from both entry
+points."""
 import ctypes as C
 import math
 import os
@@ -236,6 +237,32 @@ def test_host_build_against_the_reading(H, runs):
         assert np.array_equal(bad[:n], ref["bad"]), name
         assert (int(res["n_pairs"]), int(res["n_bad"]), int(res["n_inliers"])) == (ref["n_pairs"], ref["n_bad"], ref["n_inliers"]), name
         assert np.all(d <= 1.0), (name, d)
+
+
+@pytest.mark.parametrize("n, rows", [(6, 9), (7, 11)])
+def test_host_build_of_the_shared_solve(H, n, rows):
+    """csrc/lm_internal.h's lm_ldlt_solve<6> and <7> themselves (the pose and the Sim3 kernel's solve), on the matrices of the two
+    test_ldlt_against_numpy tests: against numpy at their rtol, lambda added as the diagonal it is, a non-positive pivot reported"""
+    H.optsim3_host_ldlt.restype = C.c_int
+    iu = np.triu_indices(n)   # row-major, i <= j
+
+    def solve(Hm, lam, b):
+        x = np.zeros(n)
+        rc = H.optsim3_host_ldlt(n, _lib.ptr(np.ascontiguousarray(Hm[iu])), C.c_double(lam), _lib.ptr(b), _lib.ptr(x))
+        return rc, x
+
+    rng = np.random.default_rng(3)
+    A = rng.normal(size=(rows, n))
+    Hm = A.T @ A + 1e-3 * np.eye(n)
+    b = rng.normal(size=n)
+    rc, x = solve(Hm, 0.0, b)
+    assert rc == 1 and np.allclose(x, np.linalg.solve(Hm, b), rtol=1e-9, atol=0)
+    rc_l, x_l = solve(Hm, 0.37, b)
+    rc_d, x_d = solve(Hm + 0.37 * np.eye(n), 0.0, b)
+    assert rc_l == 1 and rc_d == 1 and x_l.tobytes() == x_d.tobytes()
+    Hm[2, 2] = -1.0
+    assert solve(Hm, 0.0, b)[0] == 0
+    assert H.optsim3_host_ldlt(5, _lib.ptr(np.zeros(15)), C.c_double(0.0), _lib.ptr(np.zeros(5)), _lib.ptr(np.zeros(5))) == -1
 
 
 # ---- the C ABI without a device ---------------------------------------------------------------------------------------------------
