@@ -111,6 +111,9 @@ int orbfe_device_download(void* h_dst, const void* d_src, size_t bytes);
  *   Sim3 optimisation   at most 9 500 correspondences per problem (orbfe_optimize_sim3, orbfe_optimize_sim3_batch_device: the frame
  *                       limit of the Sim3 search whose matches it reads), at most 65 535 problems per batch launch, th2 > 0
  *                       (pinned by tests/test_optsim3_cpu.py)
+ *   keyframe database   at most 4 096 words per vector, 65 535 queries per call, 4 194 304 adds between two clears, Q x slots and
+ *                       Q x cand_cap <= 67 108 864 (the ORBFE_KFDB_* constants, each with its reason; pinned by
+ *                       tests/test_kfdb_cpu.py)
  * Each limit is pinned at its largest accepted and its first refused value by tests/test_limits_gpu.py (levels: also
  * tests/test_cabi_cpu.py; depth maps: tests/test_frames_cpu.py and tests/test_frames_gpu.py; rectification:
  * tests/test_rectify_cpu.py and tests/test_rectify_gpu.py; pose optimisation: tests/test_pose_cpu.py).
@@ -874,6 +877,100 @@ int orbfe_optimize_sim3_batch_device(int P, const orbfe_sim3_view* d_view1, cons
                                      const orbfe_optsim3_pair* d_pairs, const int32_t* d_n, int cap, const float* d_s_R_t_in,
                                      const float* d_th2, const int32_t* d_fix_scale, orbfe_optsim3_result* d_result, uint8_t* d_bad,
                                      void* stream);
+
+/* ---- KeyFrameDatabase (L/src/KeyFrameDatabase.cc, D/src/ScoringObject.cpp: L1) -----------------------------------------------------
+ * The first step of both place-recognition chains: DetectRelocalizationCandidates in front of orbfe_search_by_bow .. the pose
+ * optimisation, DetectLoopCandidates in front of orbfe_search_by_bow_kf .. orbfe_optimize_sim3.  The handle keeps the BoW vectors
+ * orbfe_compute_bow produced (word ids and double values) in device memory and answers Q queries per call against every entry.
+ * Every output is decided bit for bit by a plain reading of the reference; no tolerance applies anywhere:
+ *   entries      add appends the keyframe to the list of each of its words, so an entry has an add sequence number: its SLOT.  Slots
+ *                are handed out in add order and are not reused before clear; erase frees the entry, adding the id again takes a new,
+ *                later slot.
+ *   sharing set  S of a query = the live entries with at least one common word (for a loop query: whose id is not in the query's
+ *                connected set); an entry's `words` = the number of common words; lKFsSharingWords = S ordered by (smallest common
+ *                word id, slot)
+ *   thresholds   maxCommonWords = max words over S; minCommonWords = (int)(maxCommonWords * 0.8f); an entry is SCORED when
+ *                words > minCommonWords; si = (float)(-sum / 2.0), sum += fabs(vi - wi) - fabs(vi) - fabs(wi) over the common words
+ *                in ascending word order, in double (vi the query's value)
+ *   relocalisation   every scored entry, in S order, starts acc = best = si and walks its at most 10 covisible neighbours in their
+ *                given order: a neighbour IN S adds its mRelocScore in float (being scored is not required) and replaces the best
+ *                keyframe when its score is strictly larger; bestAccScore starts at 0; an entry is retained when acc > 0.75f *
+ *                bestAccScore; the candidates are the best keyframes of the retained entries, in order, first occurrence only.
+ *                mRelocScore of a neighbour that is in S but not scored is what the most recent earlier query that scored it left
+ *                there; the reference never initialises the field.  The handle carries it per slot, starts it at 0.0f on add (the
+ *                one deviation) and applies the queries of a batch in index order.
+ *   loop         scored entries with si >= minScore form lScoreAndMatch; a neighbour counts only when it is in S and scored, so no
+ *                state crosses queries; bestAccScore starts at minScore; the rest as above
+ *   neighbours   an id that names no live entry at query time is skipped
+ * Limits (ORBFE_ERR_INVALID unless stated): */
+#define ORBFE_KFDB_MAX_WORDS 4096        /* words of one vector, entry or query: a workgroup stages a query's ids and values in 48 KiB
+                                            of LDS.  A frame of 2 000 features has at most 2 000 words. */
+#define ORBFE_KFDB_NEIGHBOURS 10         /* GetBestCovisibilityKeyFrames(10), L/src/KeyFrameDatabase.cc:149, :262 */
+#define ORBFE_KFDB_MAX_QUERIES 65535     /* queries per call: grid.y */
+#define ORBFE_KFDB_MAX_SLOTS 4194304     /* adds between two clears (ORBFE_ERR_CAPACITY): slot indices and strip counts stay far inside
+                                            int32 */
+#define ORBFE_KFDB_MAX_CELLS 67108864    /* Q x slots and Q x cand_cap of one call (ORBFE_ERR_CAPACITY): the work space is ten 4-byte
+                                            arrays of Q x slots, 2.5 GiB at this limit */
+#define ORBFE_KFDB_SCORE_UNKNOWN (-1.0f) /* orbfe_kfdb_score of an id that is not in the database; L1 scores lie in [0, 1] */
+enum { ORBFE_KFDB_L1_NORM = 0, ORBFE_KFDB_L2_NORM, ORBFE_KFDB_CHI_SQUARE, ORBFE_KFDB_KL, ORBFE_KFDB_BHATTACHARYYA,
+       ORBFE_KFDB_DOT_PRODUCT };   /* DBoW2::ScoringType; only L1_NORM, ORBvoc's, is accepted */
+typedef struct orbfe_kfdb orbfe_kfdb;
+typedef struct orbfe_kfdb_query_info {
+  int32_t n_sharing;           /* |S| */
+  int32_t max_common_words, min_common_words;
+  int32_t n_scored;            /* nscores */
+  int32_t n_matches;           /* lScoreAndMatch.size() */
+  float best_acc_score;        /* bestAccScore; 0 when the function returned before the accumulation */
+  float min_score_to_retain;   /* 0.75f * bestAccScore; 0 likewise */
+  int32_t n_candidates;
+} orbfe_kfdb_query_info;       /* 32 bytes */
+/* device < 0: the current device.  Without a device: ORBFE_ERR_NO_DEVICE (there is no CPU fallback). */
+int orbfe_kfdb_create(int n_words, int scoring, int device, orbfe_kfdb** out);
+int orbfe_kfdb_destroy(orbfe_kfdb* db);
+int orbfe_kfdb_clear(orbfe_kfdb* db);   /* entries, covisibility rows and carried scores; slots start at 0 again */
+int orbfe_kfdb_size(const orbfe_kfdb* db, int* n_live, int* n_slots);
+/* the keyframe id of every slot, -1 where erased: the first min(n_slots, cap) are written */
+int orbfe_kfdb_slots(const orbfe_kfdb* db, int64_t* kf_ids, int cap, int* n_slots);
+/* ids ascend strictly and lie in [0, n_words), values are finite and positive, 0 <= n <= ORBFE_KFDB_MAX_WORDS, kf_id >= 0; an id
+ * that is live already is ORBFE_ERR_INVALID.  Synchronous. */
+int orbfe_kfdb_add(orbfe_kfdb* db, int64_t kf_id, const int32_t* bow_ids, const double* bow_vals, int n);
+int orbfe_kfdb_erase(orbfe_kfdb* db, int64_t kf_id);   /* an unknown id is not an error, as in the reference */
+/* GetBestCovisibilityKeyFrames(10) of n_rows keyframes, in its order, rows padded with -1.  Rows are kept by keyframe id until clear
+ * (a keyframe may get its row before it is added and keeps it across erase and add); they are resolved to live entries at the next
+ * query. */
+int orbfe_kfdb_set_covisibles(orbfe_kfdb* db, int n_rows, const int64_t* kf_ids, const int64_t* neigh /* [n_rows][10] */);
+/* Vocabulary::score of one vector against m listed entries (the minScore loop of LoopClosing::DetectLoop, L/src/LoopClosing.cc:
+ * 112-133); out[k] = ORBFE_KFDB_SCORE_UNKNOWN where kf_ids[k] is not live.  HOST pointers, synchronous. */
+int orbfe_kfdb_score(orbfe_kfdb* db, const int32_t* q_ids, const double* q_vals, int n, const int64_t* kf_ids, int m, float* out);
+/* Q queries as a CSR (q_offsets[0] == 0, each vector as for add).  HOST pointers; one packed upload, one packed download, one
+ * synchronisation.  n_cand[q] is the full count; the first min(n_cand[q], cand_cap) ids of row q of cand[Q][cand_cap] are written,
+ * nothing behind them.  Optional (NULL): info[Q]; common_words[Q][n_slots] and scores[Q][n_slots], written where the slot was
+ * scored and untouched elsewhere (orbfe_kfdb_slots names the slots).  Relocalisation queries update the carried scores in index
+ * order; loop queries change nothing.  min_score is finite and not negative; the connected ids of a query ascend strictly. */
+int orbfe_kfdb_detect_relocalization(orbfe_kfdb* db, int Q, const int32_t* q_offsets, const int32_t* q_ids, const double* q_vals,
+                                     int cand_cap, int64_t* cand, int32_t* n_cand, orbfe_kfdb_query_info* info, int32_t* common_words,
+                                     float* scores);
+int orbfe_kfdb_detect_loop(orbfe_kfdb* db, int Q, const int32_t* q_offsets, const int32_t* q_ids, const double* q_vals,
+                           const float* min_score, const int32_t* conn_offsets, const int64_t* conn_ids, int cand_cap, int64_t* cand,
+                           int32_t* n_cand, orbfe_kfdb_query_info* info, int32_t* common_words, float* scores);
+/* The same with DEVICE pointers, asynchronous on `stream` (NULL: the NULL stream).  The vectors are not validated: lengths are clamped
+ * to [0, ORBFE_KFDB_MAX_WORDS], a list that does not ascend finds fewer common words, nothing outside the stated arrays is read or
+ * written.  Rows behind the counts are neither read nor written.  A query's bytes do not depend on Q or on its position in the
+ * batch, except through the carried relocalisation scores as defined above.  The handle's work space serves one call at a time:
+ * calls on one stream order themselves; synchronise the stream before any other call on the handle.  When entries or rows changed
+ * since the last query, the call first uploads the resolved neighbour rows with a blocking copy. */
+int orbfe_kfdb_detect_relocalization_device(orbfe_kfdb* db, int Q, const int32_t* d_q_offsets, const int32_t* d_q_ids,
+                                            const double* d_q_vals, int cand_cap, int64_t* d_cand, int32_t* d_n_cand,
+                                            orbfe_kfdb_query_info* d_info, int32_t* d_common_words, float* d_scores, void* stream);
+int orbfe_kfdb_detect_loop_device(orbfe_kfdb* db, int Q, const int32_t* d_q_offsets, const int32_t* d_q_ids, const double* d_q_vals,
+                                  const float* d_min_score, const int32_t* d_conn_offsets, const int64_t* d_conn_ids, int cand_cap,
+                                  int64_t* d_cand, int32_t* d_n_cand, orbfe_kfdb_query_info* d_info, int32_t* d_common_words,
+                                  float* d_scores, void* stream);
+/* A/B knob of tools/kfdb_rate.py: how the detection calls that FOLLOW arrange their passes.  0 (default): the common pass counts, a
+ * score pass sums the scored pairs alone.  1: the common pass also forms the L1 sum of every pair with a common word, in the same
+ * order, and the score pass only copies.  Results do not depend on it (tests/test_kfdb_gpu.py); profiles/keyframe_database.md has
+ * the times. */
+int orbfe_debug_kfdb_arrangement(int arrangement);
 
 /* SearchForInitialization (L/src/ORBmatcher.cc:388-492), the monocular map-initialisation matcher: level-0
  * keypoints of F1 are searched in a window of `window_size` pixels around prev_matched_xy[2*i..2*i+1] in F2; a

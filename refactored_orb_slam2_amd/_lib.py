@@ -125,6 +125,14 @@ OPTSIM3_RESULT_DTYPE = np.dtype([("s", "<f4"), ("R", "<f4", (9,)), ("t", "<f4", 
                                  ("n_inliers", "<i4"), ("iterations", "<i4", (2,)), ("reserved", "<i4", (2,))])
 assert OPTSIM3_PAIR_DTYPE.itemsize == 48 and OPTSIM3_RESULT_DTYPE.itemsize == 80
 OPTSIM3_MAX_PAIRS, OPTSIM3_MAX_PROBLEMS = 9500, 65535
+# orbfe_kfdb_query_info and the ORBFE_KFDB_* limits (KeyFrameDatabase, include/orbfe.h)
+KFDB_INFO_DTYPE = np.dtype([("n_sharing", "<i4"), ("max_common_words", "<i4"), ("min_common_words", "<i4"), ("n_scored", "<i4"),
+                            ("n_matches", "<i4"), ("best_acc_score", "<f4"), ("min_score_to_retain", "<f4"), ("n_candidates", "<i4")])
+assert KFDB_INFO_DTYPE.itemsize == 32
+KFDB_MAX_WORDS, KFDB_NEIGHBOURS, KFDB_MAX_QUERIES, KFDB_MAX_SLOTS, KFDB_MAX_CELLS = 4096, 10, 65535, 4194304, 67108864
+KFDB_SCORE_UNKNOWN = -1.0
+KFDB_L1_NORM, KFDB_L2_NORM = 0, 1
+KFDB_STRIP = 64   # slots per workgroup of the common and score passes (csrc/kfdb_internal.h)
 
 
 class RectifyCamera(C.Structure):
@@ -170,6 +178,9 @@ EXPORTS = [
     "orbfe_triangulate_matches", "orbfe_triangulate_matches_batch_device", "orbfe_create_new_map_points",
     "orbfe_sim3_ransac_iterations", "orbfe_sim3_solve", "orbfe_sim3_solve_batch_device",
     "orbfe_optimize_sim3", "orbfe_optimize_sim3_batch_device",
+    "orbfe_kfdb_create", "orbfe_kfdb_destroy", "orbfe_kfdb_clear", "orbfe_kfdb_size", "orbfe_kfdb_slots", "orbfe_kfdb_add", "orbfe_kfdb_erase",
+    "orbfe_kfdb_set_covisibles", "orbfe_kfdb_score", "orbfe_kfdb_detect_relocalization", "orbfe_kfdb_detect_loop",
+    "orbfe_kfdb_detect_relocalization_device", "orbfe_kfdb_detect_loop_device", "orbfe_debug_kfdb_arrangement",
 ]
 
 
@@ -285,6 +296,21 @@ def lib():
     L.orbfe_sim3_solve_batch_device.argtypes = [ci, vp, vp, vp, vp, ci, vp, vp, ci, vp, vp, vp, vp, vp, vp, vp]
     L.orbfe_optimize_sim3.argtypes = [vp, vp, vp, ci, vp, cf, ci, vp, vp]
     L.orbfe_optimize_sim3_batch_device.argtypes = [ci, vp, vp, vp, vp, ci, vp, vp, vp, vp, vp, vp]
+    i64 = C.c_int64
+    L.orbfe_kfdb_create.argtypes = [ci, ci, ci, C.POINTER(vp)]
+    L.orbfe_debug_kfdb_arrangement.argtypes = [ci]
+    L.orbfe_kfdb_destroy.argtypes = [vp]
+    L.orbfe_kfdb_clear.argtypes = [vp]
+    L.orbfe_kfdb_size.argtypes = [vp, pi, pi]
+    L.orbfe_kfdb_slots.argtypes = [vp, vp, ci, pi]
+    L.orbfe_kfdb_add.argtypes = [vp, i64, vp, vp, ci]
+    L.orbfe_kfdb_erase.argtypes = [vp, i64]
+    L.orbfe_kfdb_set_covisibles.argtypes = [vp, ci, vp, vp]
+    L.orbfe_kfdb_score.argtypes = [vp, vp, vp, ci, vp, ci, vp]
+    L.orbfe_kfdb_detect_relocalization.argtypes = [vp, ci, vp, vp, vp, ci, vp, vp, vp, vp, vp]
+    L.orbfe_kfdb_detect_loop.argtypes = [vp, ci, vp, vp, vp, vp, vp, vp, ci, vp, vp, vp, vp, vp]
+    L.orbfe_kfdb_detect_relocalization_device.argtypes = [vp, ci, vp, vp, vp, ci, vp, vp, vp, vp, vp, vp]
+    L.orbfe_kfdb_detect_loop_device.argtypes = [vp, ci, vp, vp, vp, vp, vp, vp, ci, vp, vp, vp, vp, vp, vp]
     for name in EXPORTS:
         if name != "orbfe_last_error":
             getattr(L, name).restype = ci
