@@ -111,6 +111,9 @@ int orbfe_device_download(void* h_dst, const void* d_src, size_t bytes);
  *   Sim3 optimisation   at most 9 500 correspondences per problem (orbfe_optimize_sim3, orbfe_optimize_sim3_batch_device: the frame
  *                       limit of the Sim3 search whose matches it reads), at most 65 535 problems per batch launch, th2 > 0
  *                       (pinned by tests/test_optsim3_cpu.py)
+ *   local bundle adj.   at most 64 free and 256 keyframes in all, 65 535 points and 262 140 edges per problem, 65 535 problems per
+ *                       launch (the ORBFE_LBA_MAX_* constants, each with its reason; pinned by tests/test_lba_cpu.py and
+ *                       tests/test_lba_gpu.py)
  *   keyframe database   at most 4 096 words per vector, 65 535 queries per call, 4 194 304 adds between two clears, Q x slots and
  *                       Q x cand_cap <= 67 108 864 (the ORBFE_KFDB_* constants, each with its reason; pinned by
  *                       tests/test_kfdb_cpu.py)
@@ -877,6 +880,93 @@ int orbfe_optimize_sim3_batch_device(int P, const orbfe_sim3_view* d_view1, cons
                                      const orbfe_optsim3_pair* d_pairs, const int32_t* d_n, int cap, const float* d_s_R_t_in,
                                      const float* d_th2, const int32_t* d_fix_scale, orbfe_optsim3_result* d_result, uint8_t* d_bad,
                                      void* stream);
+
+/* ---- Optimizer::LocalBundleAdjustment (L/src/Optimizer.cc:437-760) ------------------------------------------------------------------
+ * The call of LocalMapping::Run behind orbfe_create_new_map_points and the fuse searches: the poses of the local keyframes and the
+ * positions of the map points they see are refined together by g2o's Levenberg, the keyframes that only see those points held fixed.
+ * One vertex of 6 unknowns per free keyframe, one of 3 per point, one edge per observation: EdgeSE3ProjectXYZ (2 rows) where
+ * u_right < 0, EdgeStereoSE3ProjectXYZ (3 rows) otherwise, information inv_sigma2 * I, analytic Jacobians.  Schedule: optimize(5) with
+ * a Huber kernel on every edge (delta = (float)sqrt(5.991) / (float)sqrt(7.815)); every edge with chi2 > 5.991 / 7.815 or a
+ * non-positive depth goes to level 1; all Huber kernels off; optimize(10) over the level-0 edges; a second classification of every
+ * edge is the erase list.  A vertex without a level-0 edge is not active in an optimize call: it keeps its estimate.
+ * csrc/lba_internal.h states the arithmetic once, all in double: the system of BlockSolver_6_3 with the points marginalised (Hpp,
+ * Hll, Hpl, lambda on both diagonals, Hll^-1 per point by Eigen's cofactor formula, Hschur = Hpp - sum Hpl Hll^-1 Hpl^T, back
+ * substitution), updates exp(x) * estimate for poses and += for points, and g2o's Levenberg over all active vertices (lambda = 1e-5 *
+ * max diag at iteration 0 of each optimize call, computeScale over the whole update, at most 10 trials after a failure, push / pop
+ * of every estimate).  An edge is classified by the chi2 its last evaluation left in it -- the last trial of the optimize call, also
+ * a rejected one -- and by its depth at the estimates, as the reference does.  Eigen and g2o cannot be built where this library is
+ * built: SimplicialLLT is a dense unpivoted L L^T of the reduced system here, a pivot that is not > 0 is its failure, and after such a
+ * failure the estimates are left alone (g2o applies the stale solution and pops it).  DESIGN section 2: a reading, unpinned.
+ * Edges must be listed point by point, keyframes ascending inside a point, and no (keyframe, point) pair twice: the reference's
+ * observations are a map keyed by keyframe.  The host form sorts; the device form checks and refuses (rounds = -1).
+ * Not taken over: the stop flag is not read while the launch runs.
+ * Deterministic: no floating-point atomics, every block is summed by one lane in list order; a problem's bytes depend on its own
+ * rows only.  No CPU fallback.
+ * Limits, each refused with ORBFE_ERR_INVALID one step past it (pinned by tests/test_lba_cpu.py and tests/test_lba_gpu.py):
+ *   ORBFE_LBA_MAX_FREE       64 free keyframes: the reduced system of 384 unknowns is 1.2 MB of workspace and its factorisation 9.4
+ *                            million updates per trial on the ONE workgroup a problem has -- a few milliseconds; both grow with
+ *                            the square and the cube, and the local windows of the reference stay below it
+ *   ORBFE_LBA_MAX_KEYFRAMES  256 keyframes, free and fixed: their estimates and the saved ones live in LDS (28 KB)
+ *   ORBFE_LBA_MAX_POINTS     65 535 points
+ *   ORBFE_LBA_MAX_EDGES      65 535 x 4 edges
+ *   ORBFE_LBA_MAX_PROBLEMS   65 535 problems per launch */
+#define ORBFE_LBA_MAX_FREE 64
+#define ORBFE_LBA_MAX_KEYFRAMES 256
+#define ORBFE_LBA_MAX_POINTS 65535
+#define ORBFE_LBA_MAX_EDGES 262140
+#define ORBFE_LBA_MAX_PROBLEMS 65535
+#define ORBFE_LBA_FIRST_ROUND_ONLY 1      /* flags: the reference's bDoMore = false -- round 1, its classification as the erase list */
+#define ORBFE_LBA_ERASE 1                 /* bits of an erase byte: the observation is on the erase list; */
+#define ORBFE_LBA_DROPPED 2               /* the edge was at level 1 in round 2 */
+typedef struct orbfe_lba_edge {           /* one observation; 24 bytes */
+  int32_t kf, point;                      /* indices into the problem's keyframes and points */
+  float u, v, u_right;                    /* mvKeysUn[i].pt, mvuRight[i] (< 0: a monocular edge) */
+  float inv_sigma2;                       /* mvInvLevelSigma2[octave] of the keyframe; finite and > 0 */
+} orbfe_lba_edge;
+typedef struct orbfe_lba_problem {        /* where one problem of a batch lies in the batch's arrays; 24 bytes */
+  int32_t kf_offset, n_kf;                /* rows of d_poses / d_fixed / d_poses_out */
+  int32_t point_offset, n_points;         /* records of d_points, rows of d_points_out */
+  int32_t edge_offset, n_edges;           /* rows of d_edges / d_erase */
+} orbfe_lba_problem;
+typedef struct orbfe_lba_result {         /* 72 bytes, 8-byte aligned */
+  int32_t rounds;                         /* optimize calls run: 0 (no free keyframe or no edge), 1, 2; -1: refused on the device */
+  int32_t n_free, n_edges;
+  int32_t iterations[2], trials[2];       /* Levenberg iterations and trials of each round (reported, not part of parity) */
+  int32_t n_dropped, n_erase;             /* edges at level 1 after round 1, edges on the erase list */
+  int32_t reserved;
+  double chi2_first[2], chi2_final[2];    /* activeRobustChi2 at the start and at the end of each round */
+} orbfe_lba_result;
+/* One problem.  HOST pointers, synchronous, on the calling thread's current device.  camera: fx fy cx cy mbf are read; poses: n_kf x
+ * 12 floats, rows of [R | t] (GetPose); fixed[n_kf]: != 0 for a keyframe of lFixedCameras or with mnId == 0; points: n_points x 3
+ * floats (GetWorldPos); edges in any order (sorted here; the same pair twice is refused).  poses_out: a free keyframe's pose as
+ * Converter::toCvMat(SE3Quat) rounds it, a fixed one's bytes as given; points_out: a point without an edge as given; erase[n_edges]:
+ * ORBFE_LBA_* bits in the caller's edge order.  A problem without a free keyframe or without an edge returns its inputs, rounds = 0.
+ * One upload, one launch, one download; the workspace is allocated for the call.
+ * Limits (ORBFE_ERR_INVALID): the ORBFE_LBA_MAX_* above, n_kf, n_points, n_edges >= 0, every edge's kf and point in range, inv_sigma2
+ * finite and > 0, null camera / result, null arrays with a count > 0, flags outside ORBFE_LBA_FIRST_ROUND_ONLY. */
+int orbfe_local_bundle_adjustment(const orbfe_pose_camera* camera, const float* poses, const uint8_t* fixed, int n_kf, const float* points,
+                                  int n_points, const orbfe_lba_edge* edges, int n_edges, int flags, float* poses_out, float* points_out,
+                                  uint8_t* erase, orbfe_lba_result* result);
+/* The bytes of workspace a batch of P problems needs whose counts stay within kf_cap keyframes, point_cap points and edge_cap edges
+ * each.  HOST pointer.  Limits (ORBFE_ERR_INVALID): 0 <= P <= ORBFE_LBA_MAX_PROBLEMS, the caps >= 0 and within the ORBFE_LBA_MAX_*
+ * (kf_cap: ORBFE_LBA_MAX_KEYFRAMES), null bytes. */
+int orbfe_lba_workspace_bytes(int P, int kf_cap, int point_cap, int edge_cap, size_t* bytes);
+/* P problems in one launch, one workgroup each.  DEVICE pointers, asynchronous on `stream` (NULL: the NULL stream).  Problem p lies
+ * where d_problems[p] says: n_kf rows of d_poses (12 floats) / d_fixed / d_poses_out from kf_offset on, n_points records of d_points
+ * (point_stride bytes apart, the position first: three floats, orbfe_new_point and orbfe_map_point qualify) and rows of d_points_out
+ * (3 floats) from point_offset on, n_edges rows of d_edges / d_erase from edge_offset on.  Rows no problem names are neither read nor
+ * written; inputs are not modified.  A problem whose counts are negative or exceed the caps, which has more than ORBFE_LBA_MAX_FREE
+ * free keyframes, or whose edge list breaks a rule (index out of range, inv_sigma2 not finite or not > 0, not in (point, keyframe)
+ * order, a pair twice) is refused by its workgroup: rounds = -1, poses and points copied through, erase bytes 0; no other problem is
+ * touched.  d_workspace: workspace_bytes >= what orbfe_lba_workspace_bytes states for (P, kf_cap, point_cap, edge_cap), 256-byte
+ * aligned; its contents mean nothing before or after.  A problem's bytes do not depend on P, on its position or on the run.
+ * Limits (ORBFE_ERR_INVALID): as orbfe_lba_workspace_bytes (P == 0: nothing is launched), point_stride >= 12 and a multiple of 4,
+ * a workspace that is too small or misaligned, null pointers, records not 4-byte (d_result: 8-byte) aligned, unknown flags. */
+int orbfe_local_bundle_adjustment_batch_device(int P, const orbfe_pose_camera* d_camera, const orbfe_lba_problem* d_problems,
+                                               const float* d_poses, const uint8_t* d_fixed, const uint8_t* d_points, int point_stride,
+                                               const orbfe_lba_edge* d_edges, int kf_cap, int point_cap, int edge_cap, int flags,
+                                               float* d_poses_out, float* d_points_out, uint8_t* d_erase, orbfe_lba_result* d_result,
+                                               void* d_workspace, size_t workspace_bytes, void* stream);
 
 /* ---- KeyFrameDatabase (L/src/KeyFrameDatabase.cc, D/src/ScoringObject.cpp: L1) -----------------------------------------------------
  * The first step of both place-recognition chains: DetectRelocalizationCandidates in front of orbfe_search_by_bow .. the pose

@@ -125,6 +125,17 @@ OPTSIM3_RESULT_DTYPE = np.dtype([("s", "<f4"), ("R", "<f4", (9,)), ("t", "<f4", 
                                  ("n_inliers", "<i4"), ("iterations", "<i4", (2,)), ("reserved", "<i4", (2,))])
 assert OPTSIM3_PAIR_DTYPE.itemsize == 48 and OPTSIM3_RESULT_DTYPE.itemsize == 80
 OPTSIM3_MAX_PAIRS, OPTSIM3_MAX_PROBLEMS = 9500, 65535
+# orbfe_lba_edge / orbfe_lba_problem / orbfe_lba_result and the ORBFE_LBA_* limits (Optimizer::LocalBundleAdjustment, include/orbfe.h)
+LBA_EDGE_DTYPE = np.dtype([("kf", "<i4"), ("point", "<i4"), ("u", "<f4"), ("v", "<f4"), ("u_right", "<f4"), ("inv_sigma2", "<f4")])
+LBA_PROBLEM_DTYPE = np.dtype([("kf_offset", "<i4"), ("n_kf", "<i4"), ("point_offset", "<i4"), ("n_points", "<i4"), ("edge_offset", "<i4"),
+                              ("n_edges", "<i4")])
+LBA_RESULT_DTYPE = np.dtype([("rounds", "<i4"), ("n_free", "<i4"), ("n_edges", "<i4"), ("iterations", "<i4", (2,)), ("trials", "<i4", (2,)),
+                             ("n_dropped", "<i4"), ("n_erase", "<i4"), ("reserved", "<i4"), ("chi2_first", "<f8", (2,)),
+                             ("chi2_final", "<f8", (2,))])
+assert LBA_EDGE_DTYPE.itemsize == 24 and LBA_PROBLEM_DTYPE.itemsize == 24 and LBA_RESULT_DTYPE.itemsize == 72
+LBA_MAX_FREE, LBA_MAX_KEYFRAMES, LBA_MAX_POINTS, LBA_MAX_EDGES, LBA_MAX_PROBLEMS = 64, 256, 65535, 262140, 65535
+LBA_FIRST_ROUND_ONLY = 1
+LBA_ERASE, LBA_DROPPED = 1, 2
 # orbfe_kfdb_query_info and the ORBFE_KFDB_* limits (KeyFrameDatabase, include/orbfe.h)
 KFDB_INFO_DTYPE = np.dtype([("n_sharing", "<i4"), ("max_common_words", "<i4"), ("min_common_words", "<i4"), ("n_scored", "<i4"),
                             ("n_matches", "<i4"), ("best_acc_score", "<f4"), ("min_score_to_retain", "<f4"), ("n_candidates", "<i4")])
@@ -178,6 +189,7 @@ EXPORTS = [
     "orbfe_triangulate_matches", "orbfe_triangulate_matches_batch_device", "orbfe_create_new_map_points",
     "orbfe_sim3_ransac_iterations", "orbfe_sim3_solve", "orbfe_sim3_solve_batch_device",
     "orbfe_optimize_sim3", "orbfe_optimize_sim3_batch_device",
+    "orbfe_local_bundle_adjustment", "orbfe_lba_workspace_bytes", "orbfe_local_bundle_adjustment_batch_device",
     "orbfe_kfdb_create", "orbfe_kfdb_destroy", "orbfe_kfdb_clear", "orbfe_kfdb_size", "orbfe_kfdb_slots", "orbfe_kfdb_add", "orbfe_kfdb_erase",
     "orbfe_kfdb_set_covisibles", "orbfe_kfdb_score", "orbfe_kfdb_detect_relocalization", "orbfe_kfdb_detect_loop",
     "orbfe_kfdb_detect_relocalization_device", "orbfe_kfdb_detect_loop_device", "orbfe_debug_kfdb_arrangement",
@@ -296,6 +308,9 @@ def lib():
     L.orbfe_sim3_solve_batch_device.argtypes = [ci, vp, vp, vp, vp, ci, vp, vp, ci, vp, vp, vp, vp, vp, vp, vp]
     L.orbfe_optimize_sim3.argtypes = [vp, vp, vp, ci, vp, cf, ci, vp, vp]
     L.orbfe_optimize_sim3_batch_device.argtypes = [ci, vp, vp, vp, vp, ci, vp, vp, vp, vp, vp, vp]
+    L.orbfe_local_bundle_adjustment.argtypes = [vp, vp, vp, ci, vp, ci, vp, ci, ci, vp, vp, vp, vp]
+    L.orbfe_lba_workspace_bytes.argtypes = [ci, ci, ci, ci, C.POINTER(sz)]
+    L.orbfe_local_bundle_adjustment_batch_device.argtypes = [ci, vp, vp, vp, vp, vp, ci, vp, ci, ci, ci, ci, vp, vp, vp, vp, vp, sz, vp]
     i64 = C.c_int64
     L.orbfe_kfdb_create.argtypes = [ci, ci, ci, C.POINTER(vp)]
     L.orbfe_debug_kfdb_arrangement.argtypes = [ci]

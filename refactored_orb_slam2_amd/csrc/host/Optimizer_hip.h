@@ -1,4 +1,5 @@
-// Optimizer_hip.h -- host-side adapters that put ORB_SLAM2::Optimizer::PoseOptimization and Optimizer::OptimizeSim3 on liborbfe.
+// Optimizer_hip.h -- host-side adapters that put ORB_SLAM2::Optimizer::PoseOptimization, Optimizer::OptimizeSim3 and
+// Optimizer::LocalBundleAdjustment on liborbfe.
 //
 // The reference's function (Source/Libraries/ORB_SLAM2/src/Optimizer.cc:233-435) builds a g2o graph of one pose vertex and one
 // unary edge per keypoint with a map point, optimises it and writes the pose and the outlier flags back into the Frame.  This
@@ -15,10 +16,20 @@
 //   KeyFrame: mK, GetRotation(), GetTranslation(), GetMapPointMatches(), mvKeysUn, mvInvLevelSigma2
 //   MapPoint: isBad(), GetWorldPos(), GetIndexInKeyFrame(pKF)
 //   Sim3:     rotation() (with toRotationMatrix()), translation(), scale(), and the constructor (Matrix3, Vector3, double)
+//
+// LocalBundleAdjustment (Optimizer.cc:437-760) is the adapter for orbfe_local_bundle_adjustment; a template over the KeyFrame and the
+// Map type (the MapPoint type is the one the KeyFrame's matches point to), unit-tested by tests/cpp_lba.  Members used:
+//   KeyFrame: mnId, mnBALocalForKF, mnBAFixedForKF, isBad(), GetVectorCovisibleKeyFrames(), GetMapPointMatches(), GetPose(),
+//             SetPose(cv::Mat), mvKeysUn, mvuRight, mvInvLevelSigma2, fx, fy, cx, cy, mbf, EraseMapPointMatch(MapPoint*)
+//   MapPoint: mnBALocalForKF, isBad(), GetObservations(), GetWorldPos(), SetWorldPos(cv::Mat), UpdateNormalAndDepth(),
+//             EraseObservation(KeyFrame*)
+//   Map:      mMutexMapUpdate
 #pragma once
 #include <stdio.h>
 #include <string.h>
 
+#include <list>
+#include <map>
 #include <mutex>
 #include <type_traits>
 #include <vector>
@@ -177,6 +188,156 @@ int OptimizeSim3(KeyFrameT* pKF1, KeyFrameT* pKF2, std::vector<MapPointT*>& vpMa
   }
   g2oS12 = Sim3T(R, t, (double)res.s);
   return res.n_inliers;
+}
+
+// What Optimizer::LocalBundleAdjustment collects and builds before it optimises (Optimizer.cc:440-644), as the library's arguments.
+// Keyframe rows: lLocalKeyFrames in list order, then lFixedCameras; point rows: lLocalMapPoints in list order; edges in the order of
+// the reference's addEdge calls, with the keyframe and the map point of each (vpEdgeKF*, vpMapPointEdge*).
+template <class KeyFrameT, class MapPointT>
+struct LocalBAProblem {
+  std::list<KeyFrameT*> lLocalKeyFrames, lFixedCameras;
+  std::list<MapPointT*> lLocalMapPoints;
+  std::vector<float> poses, points;
+  std::vector<uint8_t> fixed;
+  std::vector<orbfe_lba_edge> edges;
+  std::vector<KeyFrameT*> vpEdgeKF;
+  std::vector<MapPointT*> vpMapPointEdge;
+  orbfe_pose_camera cam;
+};
+
+template <class KeyFrameT, class MapPointT>
+void LocalBundleAdjustmentMarshal(KeyFrameT* pKF, LocalBAProblem<KeyFrameT, MapPointT>& B) {
+  // Local KeyFrames: first breadth search from the current keyframe (:440-451)
+  B.lLocalKeyFrames.push_back(pKF);
+  pKF->mnBALocalForKF = pKF->mnId;
+  const std::vector<KeyFrameT*> vNeighKFs = pKF->GetVectorCovisibleKeyFrames();
+  for (int i = 0, iend = (int)vNeighKFs.size(); i < iend; i++) {
+    KeyFrameT* pKFi = vNeighKFs[i];
+    pKFi->mnBALocalForKF = pKF->mnId;
+    if (!pKFi->isBad()) B.lLocalKeyFrames.push_back(pKFi);
+  }
+  // Local MapPoints seen in Local KeyFrames (:453-469)
+  for (KeyFrameT* pKFi : B.lLocalKeyFrames) {
+    const std::vector<MapPointT*> vpMPs = pKFi->GetMapPointMatches();
+    for (MapPointT* pMP : vpMPs)
+      if (pMP)
+        if (!pMP->isBad())
+          if (pMP->mnBALocalForKF != pKF->mnId) {
+            B.lLocalMapPoints.push_back(pMP);
+            pMP->mnBALocalForKF = pKF->mnId;
+          }
+  }
+  // Fixed Keyframes: keyframes that see Local MapPoints but are not Local Keyframes (:471-490)
+  for (MapPointT* pMP : B.lLocalMapPoints) {
+    const auto observations = pMP->GetObservations();
+    for (auto mit = observations.begin(), mend = observations.end(); mit != mend; mit++) {
+      KeyFrameT* pKFi = mit->first;
+      if (pKFi->mnBALocalForKF != pKF->mnId && pKFi->mnBAFixedForKF != pKF->mnId) {
+        pKFi->mnBAFixedForKF = pKF->mnId;
+        if (!pKFi->isBad()) B.lFixedCameras.push_back(pKFi);
+      }
+    }
+  }
+  // the vertices (:507-533, :564-569)
+  std::map<KeyFrameT*, int32_t> row;
+  auto add = [&B, &row](KeyFrameT* pKFi, bool fixed) {
+    const cv::Mat T = pKFi->GetPose();
+    for (int r = 0; r < 3; r++)
+      for (int c = 0; c < 4; c++) B.poses.push_back(T.template at<float>(r, c));
+    row[pKFi] = (int32_t)B.fixed.size();
+    B.fixed.push_back(fixed ? 1 : 0);
+  };
+  for (KeyFrameT* pKFi : B.lLocalKeyFrames) add(pKFi, pKFi->mnId == 0);
+  for (KeyFrameT* pKFi : B.lFixedCameras) add(pKFi, true);
+  memset(&B.cam, 0, sizeof(B.cam));
+  B.cam.fx = pKF->fx;
+  B.cam.fy = pKF->fy;
+  B.cam.cx = pKF->cx;
+  B.cam.cy = pKF->cy;
+  B.cam.mbf = pKF->mbf;
+  // the edges (:560-644)
+  int32_t p = 0;
+  for (MapPointT* pMP : B.lLocalMapPoints) {
+    const cv::Mat Xw = pMP->GetWorldPos();
+    for (int r = 0; r < 3; r++) B.points.push_back(Xw.template at<float>(r));
+    const auto observations = pMP->GetObservations();
+    for (auto mit = observations.begin(), mend = observations.end(); mit != mend; mit++) {
+      KeyFrameT* pKFi = mit->first;
+      if (pKFi->isBad()) continue;
+      const auto it = row.find(pKFi);
+      if (it == row.end()) continue;   // went bad while the sets were collected: the reference has no vertex for it either
+      const auto& kpUn = pKFi->mvKeysUn[mit->second];
+      orbfe_lba_edge e;
+      e.kf = it->second;
+      e.point = p;
+      e.u = kpUn.pt.x;
+      e.v = kpUn.pt.y;
+      const float kp_ur = pKFi->mvuRight[mit->second];
+      e.u_right = kp_ur < 0 ? -1.0f : kp_ur;
+      e.inv_sigma2 = pKFi->mvInvLevelSigma2[kpUn.octave];
+      B.edges.push_back(e);
+      B.vpEdgeKF.push_back(pKFi);
+      B.vpMapPointEdge.push_back(pMP);
+    }
+    p++;
+  }
+}
+
+// The second half of LocalBundleAdjustment (:726-760) for a problem B and the library's outputs for it: under the map's mutex the
+// erasures on both sides, SetPose of every local keyframe, SetWorldPos and UpdateNormalAndDepth of every local map point.
+template <class KeyFrameT, class MapPointT, class MapT>
+void LocalBundleAdjustmentApply(LocalBAProblem<KeyFrameT, MapPointT>& B, const float* poses_out, const float* points_out,
+                                const uint8_t* erase, MapT* pMap) {
+  std::unique_lock<std::mutex> lock(pMap->mMutexMapUpdate);
+  // vToErase: the monocular edges first, then the stereo ones (:700-736); the edge of a point that went bad is skipped
+  const int n_edges = (int)B.edges.size();
+  for (int pass = 0; pass < 2; pass++)
+    for (int i = 0; i < n_edges; i++) {
+      if ((B.edges[i].u_right < 0) != (pass == 0) || !(erase[i] & ORBFE_LBA_ERASE)) continue;
+      MapPointT* pMPi = B.vpMapPointEdge[i];
+      if (pMPi->isBad()) continue;
+      B.vpEdgeKF[i]->EraseMapPointMatch(pMPi);
+      pMPi->EraseObservation(B.vpEdgeKF[i]);
+    }
+  int k = 0;
+  for (KeyFrameT* pKFi : B.lLocalKeyFrames) {
+    cv::Mat pose = cv::Mat::eye(4, 4, CV_32F);
+    for (int r = 0; r < 3; r++)
+      for (int c = 0; c < 4; c++) pose.template at<float>(r, c) = poses_out[(size_t)12 * k + 4 * r + c];
+    pKFi->SetPose(pose);
+    k++;
+  }
+  int p = 0;
+  for (MapPointT* pMP : B.lLocalMapPoints) {
+    cv::Mat X(3, 1, CV_32F);
+    for (int r = 0; r < 3; r++) X.template at<float>(r) = points_out[(size_t)3 * p + r];
+    pMP->SetWorldPos(X);
+    pMP->UpdateNormalAndDepth();
+    p++;
+  }
+}
+
+// void Optimizer::LocalBundleAdjustment(KeyFrame* pKF, bool* pbStopFlag, Map* pMap).  The stop flag is read before the one library
+// call, not while it runs: an abort raised meanwhile takes effect once the call returns.  Errors (no device, a window
+// beyond the library's limits) are logged and leave the map untouched, like a call whose stop flag is set on entry.
+template <class KeyFrameT, class MapT>
+void LocalBundleAdjustment(KeyFrameT* pKF, bool* pbStopFlag, MapT* pMap) {
+  using MapPointT = std::remove_pointer_t<typename decltype(pKF->GetMapPointMatches())::value_type>;
+  LocalBAProblem<KeyFrameT, MapPointT> B;
+  LocalBundleAdjustmentMarshal(pKF, B);
+  if (pbStopFlag)
+    if (*pbStopFlag) return;   // :646
+  const int n_kf = (int)B.fixed.size(), n_points = (int)(B.points.size() / 3), n_edges = (int)B.edges.size();
+  std::vector<float> poses_out(B.poses.size()), points_out(B.points.size());
+  std::vector<uint8_t> erase((size_t)n_edges, 0);
+  orbfe_lba_result res;
+  const int rc = orbfe_local_bundle_adjustment(&B.cam, B.poses.data(), B.fixed.data(), n_kf, B.points.data(), n_points, B.edges.data(),
+                                               n_edges, 0, poses_out.data(), points_out.data(), erase.data(), &res);
+  if (rc != ORBFE_OK) {
+    fprintf(stderr, "orbfe LocalBundleAdjustment: %s (code %d)\n", orbfe_last_error(), rc);
+    return;
+  }
+  LocalBundleAdjustmentApply(B, poses_out.data(), points_out.data(), erase.data(), pMap);
 }
 
 }  // namespace orbfe_host

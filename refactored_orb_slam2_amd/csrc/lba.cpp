@@ -1,0 +1,177 @@
+// lba.cpp -- C ABI of Optimizer::LocalBundleAdjustment (include/orbfe.h: orbfe_local_bundle_adjustment,
+// orbfe_local_bundle_adjustment_batch_device, orbfe_lba_workspace_bytes).  The entry points validate, stage and launch
+// lba_kernels.hip.  No CPU fallback: without a device both forms are an error.
+#include <math.h>
+#include <string.h>
+
+#include <algorithm>
+#include <numeric>
+#include <vector>
+
+#include "host_internal.h"
+#include "lba_internal.h"
+
+static bool caps_ok(int P, int kf_cap, int point_cap, int edge_cap) {
+  if (P < 0 || P > ORBFE_LBA_MAX_PROBLEMS || kf_cap < 0 || kf_cap > ORBFE_LBA_MAX_KEYFRAMES || point_cap < 0 ||
+      point_cap > ORBFE_LBA_MAX_POINTS || edge_cap < 0 || edge_cap > ORBFE_LBA_MAX_EDGES) {
+    orbfe_set_error("local bundle adjustment: P %d (0 .. %d), kf_cap %d (0 .. %d), point_cap %d (0 .. %d), edge_cap %d (0 .. %d)", P,
+                    ORBFE_LBA_MAX_PROBLEMS, kf_cap, ORBFE_LBA_MAX_KEYFRAMES, point_cap, ORBFE_LBA_MAX_POINTS, edge_cap,
+                    ORBFE_LBA_MAX_EDGES);
+    return false;
+  }
+  return true;
+}
+
+static size_t problem_bytes(int kf_cap, int point_cap, int edge_cap) {
+  return lba_ws_bytes(std::min(kf_cap, ORBFE_LBA_MAX_FREE), point_cap, edge_cap);
+}
+
+extern "C" int orbfe_lba_workspace_bytes(int P, int kf_cap, int point_cap, int edge_cap, size_t* bytes) {
+  if (!bytes) {
+    orbfe_set_error("lba workspace bytes: bytes is required");
+    return ORBFE_ERR_INVALID;
+  }
+  if (!caps_ok(P, kf_cap, point_cap, edge_cap)) return ORBFE_ERR_INVALID;
+  *bytes = (size_t)P * problem_bytes(kf_cap, point_cap, edge_cap);
+  return ORBFE_OK;
+}
+
+extern "C" int orbfe_local_bundle_adjustment_batch_device(int P, const orbfe_pose_camera* d_camera, const orbfe_lba_problem* d_problems,
+                                                          const float* d_poses, const uint8_t* d_fixed, const uint8_t* d_points,
+                                                          int point_stride, const orbfe_lba_edge* d_edges, int kf_cap, int point_cap,
+                                                          int edge_cap, int flags, float* d_poses_out, float* d_points_out,
+                                                          uint8_t* d_erase, orbfe_lba_result* d_result, void* d_workspace,
+                                                          size_t workspace_bytes, void* stream) {
+  if (!caps_ok(P, kf_cap, point_cap, edge_cap)) return ORBFE_ERR_INVALID;
+  if (point_stride < 12 || (point_stride & 3) || (flags & ~ORBFE_LBA_FIRST_ROUND_ONLY)) {
+    orbfe_set_error("local bundle adjustment batch: point_stride %d (>= 12, a multiple of 4), flags %d", point_stride, flags);
+    return ORBFE_ERR_INVALID;
+  }
+  if (!d_camera || !d_problems || !d_result || (kf_cap > 0 && (!d_poses || !d_fixed || !d_poses_out)) ||
+      (point_cap > 0 && (!d_points || !d_points_out)) || (edge_cap > 0 && (!d_edges || !d_erase))) {
+    orbfe_set_error("local bundle adjustment batch: every pointer is required (the arrays of a cap of 0 may be null)");
+    return ORBFE_ERR_INVALID;
+  }
+  if (((uintptr_t)d_camera & 3) || ((uintptr_t)d_problems & 3) || ((uintptr_t)d_poses & 3) || ((uintptr_t)d_points & 3) ||
+      ((uintptr_t)d_edges & 3) || ((uintptr_t)d_poses_out & 3) || ((uintptr_t)d_points_out & 3) || ((uintptr_t)d_result & 7)) {
+    orbfe_set_error("local bundle adjustment batch: records must be 4-byte aligned, d_result 8-byte");
+    return ORBFE_ERR_INVALID;
+  }
+  const size_t need = (size_t)P * problem_bytes(kf_cap, point_cap, edge_cap);
+  if (need > 0 && (!d_workspace || workspace_bytes < need || ((uintptr_t)d_workspace & 255))) {
+    orbfe_set_error("local bundle adjustment batch: the workspace needs %zu bytes at a 256-byte boundary (%zu given)", need,
+                    workspace_bytes);
+    return ORBFE_ERR_INVALID;
+  }
+  if (!have_device()) return ORBFE_ERR_NO_DEVICE;
+  if (P == 0) return ORBFE_OK;
+  LbaLaunch L;
+  memset(&L, 0, sizeof(L));
+  L.camera = d_camera; L.problems = d_problems; L.poses = d_poses; L.fixed = d_fixed; L.points = d_points; L.point_stride = point_stride;
+  L.edges = d_edges; L.kf_cap = kf_cap; L.point_cap = point_cap; L.edge_cap = edge_cap; L.flags = flags; L.poses_out = d_poses_out;
+  L.points_out = d_points_out; L.erase = d_erase; L.result = d_result; L.workspace = (uint8_t*)d_workspace;
+  orbfe_launch_lba(L, P, (hipStream_t)stream);
+  const hipError_t le = hipGetLastError();
+  if (le != hipSuccess) return hip_fail("local bundle adjustment batch: kernel launch failed", le);
+  return ORBFE_OK;
+}
+
+extern "C" int orbfe_local_bundle_adjustment(const orbfe_pose_camera* camera, const float* poses, const uint8_t* fixed, int n_kf,
+                                             const float* points, int n_points, const orbfe_lba_edge* edges, int n_edges, int flags,
+                                             float* poses_out, float* points_out, uint8_t* erase, orbfe_lba_result* result) {
+  if (!camera || !result) {
+    orbfe_set_error("local bundle adjustment: camera and result are required");
+    return ORBFE_ERR_INVALID;
+  }
+  if (n_kf < 0 || n_points < 0 || n_edges < 0 || !caps_ok(1, std::max(n_kf, 0), std::max(n_points, 0), std::max(n_edges, 0)) ||
+      (flags & ~ORBFE_LBA_FIRST_ROUND_ONLY)) {
+    if (n_kf < 0 || n_points < 0 || n_edges < 0 || (flags & ~ORBFE_LBA_FIRST_ROUND_ONLY))
+      orbfe_set_error("local bundle adjustment: n_kf %d, n_points %d, n_edges %d (>= 0), flags %d", n_kf, n_points, n_edges, flags);
+    return ORBFE_ERR_INVALID;
+  }
+  if ((n_kf > 0 && (!poses || !fixed || !poses_out)) || (n_points > 0 && (!points || !points_out)) || (n_edges > 0 && (!edges || !erase))) {
+    orbfe_set_error("local bundle adjustment: the arrays of a count > 0 are required");
+    return ORBFE_ERR_INVALID;
+  }
+  int n_free = 0;
+  for (int k = 0; k < n_kf; k++) n_free += fixed[k] ? 0 : 1;
+  if (n_free > ORBFE_LBA_MAX_FREE) {
+    orbfe_set_error("local bundle adjustment: %d free keyframes (0 .. %d)", n_free, ORBFE_LBA_MAX_FREE);
+    return ORBFE_ERR_INVALID;
+  }
+  for (int i = 0; i < n_edges; i++) {
+    const orbfe_lba_edge& E = edges[i];
+    if (E.kf < 0 || E.kf >= n_kf || E.point < 0 || E.point >= n_points || !(E.inv_sigma2 > 0.0f) || !isfinite(E.inv_sigma2)) {
+      orbfe_set_error("local bundle adjustment: edge %d: kf %d (0 .. %d), point %d (0 .. %d), inv_sigma2 %g (finite, > 0)", i, E.kf,
+                      n_kf - 1, E.point, n_points - 1, (double)E.inv_sigma2);
+      return ORBFE_ERR_INVALID;
+    }
+  }
+  // the plan's order: point by point, keyframes ascending; order[j] = the caller's row of sorted edge j
+  std::vector<int32_t> order(n_edges);
+  std::iota(order.begin(), order.end(), 0);
+  std::stable_sort(order.begin(), order.end(), [edges](int32_t a, int32_t b) {
+    return edges[a].point != edges[b].point ? edges[a].point < edges[b].point : edges[a].kf < edges[b].kf;
+  });
+  for (int j = 1; j < n_edges; j++)
+    if (edges[order[j]].point == edges[order[j - 1]].point && edges[order[j]].kf == edges[order[j - 1]].kf) {
+      orbfe_set_error("local bundle adjustment: edges %d and %d join the same keyframe %d and point %d", order[j - 1], order[j],
+                      edges[order[j]].kf, edges[order[j]].point);
+      return ORBFE_ERR_INVALID;
+    }
+  if (!have_device()) return ORBFE_ERR_NO_DEVICE;
+
+  // ONE block: [input, uploaded | output, downloaded], the same offsets in device memory and in its pinned mirror
+  Layout Lo;
+  const size_t o_cam = Lo.add(sizeof(orbfe_pose_camera)), o_prob = Lo.add(sizeof(orbfe_lba_problem)),
+               o_poses = Lo.add((size_t)n_kf * 48), o_fixed = Lo.add((size_t)n_kf), o_points = Lo.add((size_t)n_points * 12),
+               o_edges = Lo.add((size_t)n_edges * sizeof(orbfe_lba_edge));
+  const size_t in_end = Lo.off;
+  const size_t o_res = Lo.add(sizeof(orbfe_lba_result)), o_pout = Lo.add((size_t)n_kf * 48), o_xout = Lo.add((size_t)n_points * 12),
+               o_erase = Lo.add((size_t)n_edges);
+  const size_t total = Lo.off;
+  const size_t ws_bytes = problem_bytes(n_kf, n_points, n_edges);
+
+  std::unique_lock<std::mutex> lk;
+  hipStream_t s = nullptr;
+  uint8_t *d = nullptr, *h = nullptr;
+  int rc;
+  if ((rc = orbfe_internal_thread_block(total, lk, &s, &d, &h))) return rc;
+  void* ws = nullptr;
+  hipError_t e = ws_bytes ? hipMalloc(&ws, ws_bytes) : hipSuccess;
+  if (e != hipSuccess) return hip_fail("local bundle adjustment: workspace", e);
+  memcpy(h + o_cam, camera, sizeof(orbfe_pose_camera));
+  const orbfe_lba_problem prob = {0, n_kf, 0, n_points, 0, n_edges};
+  memcpy(h + o_prob, &prob, sizeof(prob));
+  if (n_kf) memcpy(h + o_poses, poses, (size_t)n_kf * 48);
+  if (n_kf) memcpy(h + o_fixed, fixed, (size_t)n_kf);
+  if (n_points) memcpy(h + o_points, points, (size_t)n_points * 12);
+  orbfe_lba_edge* he = (orbfe_lba_edge*)(h + o_edges);
+  for (int j = 0; j < n_edges; j++) he[j] = edges[order[j]];
+  // from here on the stream may still read the pinned block: an error return drains it before the handle's lock is released
+  auto done = [s, ws](int code) {
+    (void)hipStreamSynchronize(s);
+    if (ws) (void)hipFree(ws);
+    return code;
+  };
+  e = hipMemcpyAsync(d, h, in_end, hipMemcpyHostToDevice, s);
+  if (e != hipSuccess) return done(hip_fail("local bundle adjustment: upload", e));
+  LbaLaunch L;
+  memset(&L, 0, sizeof(L));
+  L.camera = (const orbfe_pose_camera*)(d + o_cam); L.problems = (const orbfe_lba_problem*)(d + o_prob);
+  L.poses = (const float*)(d + o_poses); L.fixed = d + o_fixed; L.points = d + o_points; L.point_stride = 12;
+  L.edges = (const orbfe_lba_edge*)(d + o_edges); L.kf_cap = n_kf; L.point_cap = n_points; L.edge_cap = n_edges; L.flags = flags;
+  L.poses_out = (float*)(d + o_pout); L.points_out = (float*)(d + o_xout); L.erase = d + o_erase;
+  L.result = (orbfe_lba_result*)(d + o_res); L.workspace = (uint8_t*)ws;
+  orbfe_launch_lba(L, 1, s);
+  e = hipGetLastError();
+  if (e != hipSuccess) return done(hip_fail("local bundle adjustment: kernel launch failed", e));
+  e = hipMemcpyAsync(h + o_res, d + o_res, total - o_res, hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  if (e != hipSuccess) return done(hip_fail("local bundle adjustment", e));
+  memcpy(result, h + o_res, sizeof(*result));
+  if (n_kf) memcpy(poses_out, h + o_pout, (size_t)n_kf * 48);
+  if (n_points) memcpy(points_out, h + o_xout, (size_t)n_points * 12);
+  for (int j = 0; j < n_edges; j++) erase[order[j]] = h[o_erase + j];
+  return done(ORBFE_OK);
+}

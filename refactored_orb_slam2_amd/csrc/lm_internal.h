@@ -1,5 +1,5 @@
-// lm_internal.h -- the generic half of g2o's Levenberg optimiser with ONE vertex of N dimensions, once, for every back end that is
-// one (N = 6: the pose of pose_internal.h, N = 7: the similarity of optsim3_internal.h).  __host__ __device__ inline functions,
+// lm_internal.h -- the generic half of g2o's Levenberg optimiser, once, for every back end: with ONE vertex of N dimensions (N = 6:
+// the pose of pose_internal.h, N = 7: the similarity of optsim3_internal.h) and, where stated, for the many vertices of lba_internal.h.  __host__ __device__ inline functions,
 // all in double, compiled with -ffp-contract=off on both sides: the parenthesisation of an expression here is its result.  The
 // iteration and trial loop itself is not here: what a kernel hands its lanes between solve and trial differs per back end.
 //
@@ -136,16 +136,14 @@ struct LmState {
   double lambda, ni;
 };
 
-// Good / bad step bookkeeping of one trial (optimization_algorithm_levenberg.cpp:125-146).  Returns true when the step is accepted.
-template <int N>
-__host__ __device__ inline bool lm_trial(LmState& lm, bool ok2, double current_chi, double temp_chi, const double* x, const double* b,
-                                         double* rho_out) {
+// Good / bad step bookkeeping of one trial (optimization_algorithm_levenberg.cpp:125-146) with computeScale's sum over the update
+// vector handed in: the form for a system of many vertices (lba_internal.h), whose x and b are no fixed-size arrays.  `scale_sum` is
+// read only when ok2.  Returns true when the step is accepted.
+__host__ __device__ inline bool lm_trial_scaled(LmState& lm, bool ok2, double current_chi, double temp_chi, double scale_sum,
+                                                double* rho_out) {
   double scale = 1.0;
   if (ok2) {
-    scale = 0.0;
-#pragma unroll
-    for (int j = 0; j < N; j++) scale += x[j] * (lm.lambda * x[j] + b[j]);   // computeScale
-    scale = scale + 1e-3;
+    scale = scale_sum + 1e-3;
   } else {
     temp_chi = 1.7976931348623157e308;   // std::numeric_limits<double>::max()
   }
@@ -163,4 +161,16 @@ __host__ __device__ inline bool lm_trial(LmState& lm, bool ok2, double current_c
   lm.lambda *= lm.ni;
   lm.ni *= 2;
   return false;
+}
+
+// The same for ONE vertex of N dimensions: computeScale over its x and b
+template <int N>
+__host__ __device__ inline bool lm_trial(LmState& lm, bool ok2, double current_chi, double temp_chi, const double* x, const double* b,
+                                         double* rho_out) {
+  double scale = 0.0;
+  if (ok2) {
+#pragma unroll
+    for (int j = 0; j < N; j++) scale += x[j] * (lm.lambda * x[j] + b[j]);   // computeScale
+  }
+  return lm_trial_scaled(lm, ok2, current_chi, temp_chi, scale, rho_out);
 }

@@ -1,4 +1,4 @@
-// lm_reduce.h -- the workgroup reductions of the kernels that run lm_internal.h's optimiser (pose_kernels.hip, optsim3_kernels.hip).
+// lm_reduce.h -- the workgroup reductions of the kernels that run lm_internal.h's optimiser (pose_kernels.hip, optsim3_kernels.hip, lba_kernels.hip).
 // Device only: the host builds of the arithmetic (tests/cpp_*) include lm_internal.h, never this.
 //
 // Reduction order: a lane's own rows (sequential) -> xor butterfly inside the wave (a + b == b + a, so every lane holds the same
@@ -43,5 +43,19 @@ __device__ inline int lm_reduce_count(int c, int* red, int tid) {
   int s = 0;
 #pragma unroll
   for (int w = 0; w < WAVES; w++) s += red[w];
+  return s;
+}
+
+// The maximum of the workgroup, returned to every lane (max is exact in any order); red holds WAVES doubles
+template <int WAVES>
+__device__ inline double lm_reduce_max(double m, double* red, int tid) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) m = fmax(m, __shfl_xor(m, off, 64));
+  __syncthreads();
+  if ((tid & 63) == 0) red[tid >> 6] = m;
+  __syncthreads();
+  double s = red[0];
+#pragma unroll
+  for (int w = 1; w < WAVES; w++) s = fmax(s, red[w]);
   return s;
 }

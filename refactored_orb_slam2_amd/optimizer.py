@@ -1,6 +1,7 @@
-"""Optimizer::PoseOptimization and Optimizer::OptimizeSim3 over the C ABI of liborbfe.so (L/src/Optimizer.cc:233-435, :1381-1573,
-L/ = Source/Libraries/ORB_SLAM2/): the pose of a frame from its keypoint <-> map-point pairs, and which pairs were wrong; the
-similarity between two keyframes of a loop candidate from their matched map points, and which matches were wrong.
+"""Optimizer::PoseOptimization, Optimizer::OptimizeSim3 and Optimizer::LocalBundleAdjustment over the C ABI of liborbfe.so
+(L/src/Optimizer.cc:233-435, :1381-1573, :437-760, L/ = Source/Libraries/ORB_SLAM2/): the pose of a frame from its keypoint <->
+map-point pairs, and which pairs were wrong; the similarity between two keyframes of a loop candidate from their matched map points,
+and which matches were wrong; the poses of the local keyframes and the points they see, and which observations to erase.
 
 pose_optimization is the per-frame call of Tracking on host arrays; pose_optimization_batch optimises every frame of a batch in one
 launch on device tensors (pose_kernels.hip, one workgroup per frame) and reads the `assigned` array of the batched projection
@@ -8,6 +9,9 @@ searches unchanged.  Both run the same kernel; there is no CPU path.
 
 optimize_sim3 is the per-candidate call of LoopClosing::ComputeSim3 on host arrays; optimize_sim3_batch optimises every candidate of
 a batch in one launch on device tensors (optsim3_kernels.hip, one workgroup per candidate).
+
+local_bundle_adjustment is the call of LocalMapping::Run on host arrays; local_bundle_adjustment_batch optimises ragged problems that
+lie in device tensors in one launch (lba_kernels.hip, one workgroup per problem) with a workspace of lba_workspace_bytes(...) bytes.
 """
 from __future__ import annotations
 
@@ -16,10 +20,13 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
+from ._lib import (LBA_DROPPED, LBA_EDGE_DTYPE, LBA_ERASE, LBA_FIRST_ROUND_ONLY, LBA_PROBLEM_DTYPE, LBA_RESULT_DTYPE)
 from ._lib import OPTSIM3_PAIR_DTYPE, OPTSIM3_RESULT_DTYPE, POSE_CAMERA_DTYPE, POSE_DISCARD, POSE_RESULT_DTYPE, SIM3_VIEW_DTYPE
 
 __all__ = ["POSE_CAMERA_DTYPE", "POSE_RESULT_DTYPE", "POSE_DISCARD", "pose_camera", "pose_optimization", "pose_optimization_batch",
-           "OPTSIM3_PAIR_DTYPE", "OPTSIM3_RESULT_DTYPE", "sim3_view", "optimize_sim3", "optimize_sim3_batch"]
+           "OPTSIM3_PAIR_DTYPE", "OPTSIM3_RESULT_DTYPE", "sim3_view", "optimize_sim3", "optimize_sim3_batch",
+           "LBA_EDGE_DTYPE", "LBA_PROBLEM_DTYPE", "LBA_RESULT_DTYPE", "LBA_FIRST_ROUND_ONLY", "LBA_ERASE", "LBA_DROPPED",
+           "local_bundle_adjustment", "local_bundle_adjustment_batch", "lba_workspace_bytes"]
 
 
 def pose_camera(fx, fy, cx, cy, mbf, inv_level_sigma2) -> np.ndarray:
@@ -110,3 +117,50 @@ def optimize_sim3_batch(view1, view2, pairs, n, s_R_t_in, th2, fix_scale, result
                                                            _lib.ptr(s_R_t_in), _lib.ptr(th2), _lib.ptr(fix_scale), _lib.ptr(result),
                                                            _lib.ptr(bad), _lib.stream_handle(stream)),
                "orbfe_optimize_sim3_batch_device")
+
+
+def local_bundle_adjustment(camera, poses, fixed, points, edges, flags: int = 0):
+    """Optimizer::LocalBundleAdjustment of one window from its edge list on.  camera: pose_camera(...) (fx fy cx cy mbf are read);
+    poses: (n_kf, 12) float32, rows of [R | t]; fixed: (n_kf) uint8, != 0 for a keyframe of lFixedCameras or with mnId == 0; points:
+    (n_points, 3) float32; edges: LBA_EDGE_DTYPE (n_edges) in any order; flags: LBA_FIRST_ROUND_ONLY.  Returns (poses_out, points_out,
+    erase, result): erase holds the LBA_ERASE / LBA_DROPPED bits per edge, result is one LBA_RESULT_DTYPE record."""
+    cam = np.ascontiguousarray(camera, POSE_CAMERA_DTYPE).reshape(1)
+    poses = np.ascontiguousarray(np.asarray(poses, np.float32).reshape(-1, 12))
+    fixed = np.ascontiguousarray(fixed, np.uint8).reshape(-1)
+    points = np.ascontiguousarray(np.asarray(points, np.float32).reshape(-1, 3))
+    edges = np.ascontiguousarray(edges, LBA_EDGE_DTYPE).reshape(-1)
+    if len(fixed) != len(poses):
+        raise ValueError("poses and fixed must have one entry per keyframe")
+    poses_out, points_out = np.zeros_like(poses), np.zeros_like(points)
+    erase = np.zeros(len(edges), np.uint8)
+    res = np.zeros(1, LBA_RESULT_DTYPE)
+    opt = lambda a: _lib.ptr(a) if len(a) else None
+    _lib.check(_lib.lib().orbfe_local_bundle_adjustment(_lib.ptr(cam), opt(poses), opt(fixed), len(poses), opt(points), len(points),
+                                                        opt(edges), len(edges), int(flags), opt(poses_out), opt(points_out), opt(erase),
+                                                        _lib.ptr(res)), "orbfe_local_bundle_adjustment")
+    return poses_out, points_out, erase, res[0]
+
+
+def lba_workspace_bytes(P: int, kf_cap: int, point_cap: int, edge_cap: int) -> int:
+    """orbfe_lba_workspace_bytes: the workspace of a batch of P problems of at most kf_cap keyframes, point_cap points and edge_cap
+    edges each."""
+    n = C.c_size_t(0)
+    _lib.check(_lib.lib().orbfe_lba_workspace_bytes(int(P), int(kf_cap), int(point_cap), int(edge_cap), C.byref(n)),
+               "orbfe_lba_workspace_bytes")
+    return int(n.value)
+
+
+def local_bundle_adjustment_batch(camera, problems, poses, fixed, points, edges, kf_cap, point_cap, edge_cap, poses_out, points_out,
+                                  erase, result, workspace, flags: int = 0, stream=None):
+    """orbfe_local_bundle_adjustment_batch_device on torch CUDA tensors: camera (88) u8 = one POSE_CAMERA_DTYPE record, problems (P,24)
+    u8 = LBA_PROBLEM_DTYPE, poses (K,12) f32, fixed (K) u8, points (M,stride) u8 whose records start with the position (or (M,3) f32),
+    edges (E,24) u8 = LBA_EDGE_DTYPE, listed point by point with keyframes ascending; poses_out (K,12) f32, points_out (M,3) f32, erase
+    (E) u8, result (P,72) u8 = LBA_RESULT_DTYPE, workspace: u8 of at least lba_workspace_bytes(P, kf_cap, point_cap, edge_cap) bytes.
+    Rows no problem names are not written.  stream: a torch.cuda.Stream, or None for the NULL stream."""
+    P = int(problems.shape[0])
+    stride = int(points.shape[1]) * int(points.element_size()) if points.dim() == 2 else 12
+    _lib.check(_lib.lib().orbfe_local_bundle_adjustment_batch_device(
+        P, _lib.ptr(camera), _lib.ptr(problems), _lib.ptr(poses), _lib.ptr(fixed), _lib.ptr(points), stride, _lib.ptr(edges), int(kf_cap),
+        int(point_cap), int(edge_cap), int(flags), _lib.ptr(poses_out), _lib.ptr(points_out), _lib.ptr(erase), _lib.ptr(result),
+        _lib.ptr(workspace), int(workspace.numel()) * int(workspace.element_size()), _lib.stream_handle(stream)),
+        "orbfe_local_bundle_adjustment_batch_device")
