@@ -117,6 +117,9 @@ int orbfe_device_download(void* h_dst, const void* d_src, size_t bytes);
  *   keyframe database   at most 4 096 words per vector, 65 535 queries per call, 4 194 304 adds between two clears, Q x slots and
  *                       Q x cand_cap <= 67 108 864 (the ORBFE_KFDB_* constants, each with its reason; pinned by
  *                       tests/test_kfdb_cpu.py)
+ *   map-point refresh   at most 1 024 observations per point, 1 048 576 points, 16 777 216 observations and 1 048 576 keyframes per
+ *                       call, n_levels 1 .. ORBFE_MAX_LEVELS (the ORBFE_MP_MAX_* constants, each with its reason; pinned by
+ *                       tests/test_mappoint_cpu.py)
  * Each limit is pinned at its largest accepted and its first refused value by tests/test_limits_gpu.py (levels: also
  * tests/test_cabi_cpu.py; depth maps: tests/test_frames_cpu.py and tests/test_frames_gpu.py; rectification:
  * tests/test_rectify_cpu.py and tests/test_rectify_gpu.py; pose optimisation: tests/test_pose_cpu.py).
@@ -1061,6 +1064,85 @@ int orbfe_kfdb_detect_loop_device(orbfe_kfdb* db, int Q, const int32_t* d_q_offs
  * order, and the score pass only copies.  Results do not depend on it (tests/test_kfdb_gpu.py); profiles/keyframe_database.md has
  * the times. */
 int orbfe_debug_kfdb_arrangement(int arrangement);
+
+/* ---- MapPoint::ComputeDistinctiveDescriptors (L/src/MapPoint.cc:229-320) and MapPoint::UpdateNormalAndDepth (:340-381) ---------------
+ * The two calls that end every step which creates, fuses or moves map points (L/src/LocalMapping.cc:137-138, :413-415, :501-502,
+ * L/src/Optimizer.cc:759, L/src/LoopClosing.cc:474, :504, L/src/Tracking.cc:473-474, :599-600, :1010-1011), for P points in one launch
+ * sequence.  A point is an ORDERED list of observations (keyframe, keypoint index) plus a position; the order is the iteration order
+ * of the reference's std::map<KeyFrame*, size_t>, and the caller states it.  Given the list every output is decided bit for bit by a
+ * plain reading (csrc/mappoint_internal.h); no tolerance applies anywhere:
+ *   descriptor   live = the observations whose keyframe is not bad, in list order, N = |live|.  N == 0: nothing is chosen (best = -1,
+ *                desc zero).  Otherwise row i holds the N Hamming distances (0 .. 256) from live descriptor i to every live descriptor,
+ *                its own 0 included; median_i = the element (int)(0.5 * (N - 1)) of the sorted row (the floor); the winner is the first
+ *                i with the least median (strict <), so N = 1 and N = 2 always give the first live observation.  best is the winner's
+ *                position in the CALLER's list, desc its 32 bytes, n_live = N.
+ *   normal, depth   over ALL n_obs observations (the reference does not read isBad() here): d = pos - Ow in float, r = (float)(1.0 /
+ *                sqrt(sum of (double)d * (double)d in element order)), sum = sum + d * r in float in LIST ORDER from 0.0f, normal =
+ *                sum * (float)(1.0 / (double)n_obs); with PC = pos - Ow[ref]: dist = (float)sqrt(sum (double)PC^2), max_distance =
+ *                dist * scale_factors[ref_octave], min_distance = max_distance / scale_factors[n_levels - 1].  For two observations
+ *                these are the bytes orbfe_triangulate_matches writes for the pair.
+ * Taken over: both functions' arithmetic and skips.  Not taken over: the locks (the caller marshals under them), and the pointer
+ * order of the std::map, which is an input here.  An observation at zero distance from the point follows IEEE as the reference does.
+ * A point is refused by its own wave or workgroup -- status = ORBFE_MP_REFUSED, best = -1, every other selected output zero, no other
+ * point touched -- when n_obs is negative or beyond ORBFE_MP_MAX_OBS, its observations do not lie inside the observation array, an
+ * observation names a keyframe outside the table or a keypoint outside that keyframe (or a descriptor block that is not 4-byte
+ * aligned), ref is not in [0, n_obs) or ref_octave not in [0, n_levels).  n_obs == 0 (an empty or bad point): ORBFE_MP_UNCHANGED, the
+ * same outputs.  Deterministic: integer arithmetic and one sequential float sum per point, no floating-point atomics; a point's bytes
+ * do not depend on P, on its position in the batch or on the run.  No CPU fallback.
+ * Limits, each refused with ORBFE_ERR_INVALID one step past it, before any device call (pinned by tests/test_mappoint_cpu.py):
+ *   ORBFE_MP_MAX_OBS         1 024 observations of one point: its descriptors are staged in 32 KiB of LDS; the reference's own
+ *                            `float Distances[N][N]` leaves an 8 MiB stack at N = 1 448
+ *   ORBFE_MP_MAX_POINTS      1 048 576 points per call: 64 MiB of update records; point indices and grid sizes stay far inside int32
+ *   ORBFE_MP_MAX_TOTAL_OBS   16 777 216 observations per call: the host form stages 40 bytes for each (640 MiB)
+ *   ORBFE_MP_MAX_KEYFRAMES   1 048 576 rows of the keyframe table (32 MiB) */
+#define ORBFE_MP_MAX_OBS 1024
+#define ORBFE_MP_MAX_POINTS 1048576
+#define ORBFE_MP_MAX_TOTAL_OBS 16777216
+#define ORBFE_MP_MAX_KEYFRAMES 1048576
+#define ORBFE_MP_DESCRIPTOR 1             /* flags: best, n_live, desc are computed and written */
+#define ORBFE_MP_NORMAL_DEPTH 2           /* flags: normal, min_distance, max_distance are; what a flag does not select is not touched */
+enum { ORBFE_MP_UPDATED = 0, ORBFE_MP_UNCHANGED = 1, ORBFE_MP_REFUSED = 2 };   /* orbfe_mp_update.status, always written */
+typedef struct orbfe_mp_keyframe {        /* one row of the keyframe table; 32 bytes, 8-byte aligned */
+  uint64_t desc;                          /* address of mDescriptors, n_keys x 32 bytes: DEVICE memory for the device form, HOST for the host form */
+  int32_t n_keys;                         /* rows of it */
+  int32_t bad;                            /* isBad() */
+  float Ow[3];                            /* GetCameraCenter() */
+  int32_t reserved;
+} orbfe_mp_keyframe;
+typedef struct orbfe_mp_obs {             /* 8 bytes */
+  int32_t kf, idx;                        /* row of the keyframe table, keypoint index in that keyframe */
+} orbfe_mp_obs;
+typedef struct orbfe_mp_point {           /* 16 bytes */
+  int32_t obs_offset, n_obs;              /* its observations in the observation array, in map order */
+  int32_t ref;                            /* position of mpRefKF in its list */
+  int32_t ref_octave;                     /* mvKeysUn[observations[pRefKF]].octave */
+} orbfe_mp_point;
+typedef struct orbfe_mp_update {          /* 64 bytes */
+  float normal[3];                        /* mNormalVector */
+  float min_distance, max_distance;       /* mfMinDistance, mfMaxDistance */
+  int32_t best;                           /* position in the caller's list of the chosen descriptor, -1: none */
+  int32_t n_live;
+  int32_t status;                         /* ORBFE_MP_* */
+  uint8_t desc[32];                       /* mDescriptor */
+} orbfe_mp_update;
+/* P points.  HOST pointers, synchronous, on the calling thread's current device.  positions: P x 3 floats (GetWorldPos);
+ * scale_factors: n_levels floats (mvScaleFactors).  Only the descriptor rows some observation names are staged: one upload, the
+ * launches, one download.  In updates[p] the status and the halves `flags` selects are written.
+ * Limits (ORBFE_ERR_INVALID): the ORBFE_MP_MAX_* above (a point's n_obs beyond ORBFE_MP_MAX_OBS included), P, n_kf, n_obs_total >= 0,
+ * 1 <= n_levels <= ORBFE_MAX_LEVELS, flags a non-empty subset of the two, null arrays with a count > 0, null scale_factors, a keyframe
+ * with n_keys < 0 or with n_keys > 0 and no descriptors while ORBFE_MP_DESCRIPTOR is set. */
+int orbfe_refresh_map_points(const orbfe_mp_keyframe* keyframes, int n_kf, const orbfe_mp_obs* obs, int n_obs_total,
+                             const orbfe_mp_point* points, const float* positions, int P, const float* scale_factors, int n_levels,
+                             int flags, orbfe_mp_update* updates);
+/* The same with DEVICE pointers (scale_factors stays a HOST pointer, read before the call returns), asynchronous on `stream` (NULL:
+ * the NULL stream).  The keyframes' descriptor blocks are resident in device memory.  Point p's position is the first three floats of
+ * the record at d_points_pos + p * point_stride (orbfe_map_point: 72, orbfe_kf_point: 72, orbfe_new_point: 44, or 12 for bare
+ * positions).  Nothing outside the stated arrays is read or written; inputs are not modified.
+ * Limits (ORBFE_ERR_INVALID): as above, except that a point's n_obs is checked on the device; point_stride >= 12 and a multiple of 4;
+ * null pointers with a count > 0; records not 4-byte (the keyframe table: 8-byte) aligned. */
+int orbfe_refresh_map_points_batch_device(int P, const orbfe_mp_keyframe* d_keyframes, int n_kf, const orbfe_mp_obs* d_obs,
+                                          int n_obs_total, const orbfe_mp_point* d_points, const void* d_points_pos, int point_stride,
+                                          const float* scale_factors, int n_levels, int flags, orbfe_mp_update* d_updates, void* stream);
 
 /* SearchForInitialization (L/src/ORBmatcher.cc:388-492), the monocular map-initialisation matcher: level-0
  * keypoints of F1 are searched in a window of `window_size` pixels around prev_matched_xy[2*i..2*i+1] in F2; a

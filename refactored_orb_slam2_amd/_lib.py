@@ -144,6 +144,18 @@ KFDB_MAX_WORDS, KFDB_NEIGHBOURS, KFDB_MAX_QUERIES, KFDB_MAX_SLOTS, KFDB_MAX_CELL
 KFDB_SCORE_UNKNOWN = -1.0
 KFDB_L1_NORM, KFDB_L2_NORM = 0, 1
 KFDB_STRIP = 64   # slots per workgroup of the common and score passes (csrc/kfdb_internal.h)
+# orbfe_mp_keyframe / orbfe_mp_obs / orbfe_mp_point / orbfe_mp_update and the ORBFE_MP_* limits (MapPoint::ComputeDistinctiveDescriptors,
+# MapPoint::UpdateNormalAndDepth, include/orbfe.h)
+MP_KEYFRAME_DTYPE = np.dtype([("desc", "<u8"), ("n_keys", "<i4"), ("bad", "<i4"), ("Ow", "<f4", (3,)), ("reserved", "<i4")])
+MP_OBS_DTYPE = np.dtype([("kf", "<i4"), ("idx", "<i4")])
+MP_POINT_DTYPE = np.dtype([("obs_offset", "<i4"), ("n_obs", "<i4"), ("ref", "<i4"), ("ref_octave", "<i4")])
+MP_UPDATE_DTYPE = np.dtype([("normal", "<f4", (3,)), ("min_distance", "<f4"), ("max_distance", "<f4"), ("best", "<i4"), ("n_live", "<i4"),
+                            ("status", "<i4"), ("desc", "u1", (32,))])
+assert MP_KEYFRAME_DTYPE.itemsize == 32 and MP_OBS_DTYPE.itemsize == 8 and MP_POINT_DTYPE.itemsize == 16 and MP_UPDATE_DTYPE.itemsize == 64
+MP_MAX_OBS, MP_MAX_POINTS, MP_MAX_TOTAL_OBS, MP_MAX_KEYFRAMES = 1024, 1048576, 16777216, 1048576
+MP_DESCRIPTOR, MP_NORMAL_DEPTH = 1, 2
+MP_UPDATED, MP_UNCHANGED, MP_REFUSED = 0, 1, 2
+MP_SMALL_OBS = 64   # observations up to which a point is one wave's (csrc/mappoint_internal.h)
 
 
 class RectifyCamera(C.Structure):
@@ -193,6 +205,7 @@ EXPORTS = [
     "orbfe_kfdb_create", "orbfe_kfdb_destroy", "orbfe_kfdb_clear", "orbfe_kfdb_size", "orbfe_kfdb_slots", "orbfe_kfdb_add", "orbfe_kfdb_erase",
     "orbfe_kfdb_set_covisibles", "orbfe_kfdb_score", "orbfe_kfdb_detect_relocalization", "orbfe_kfdb_detect_loop",
     "orbfe_kfdb_detect_relocalization_device", "orbfe_kfdb_detect_loop_device", "orbfe_debug_kfdb_arrangement",
+    "orbfe_refresh_map_points", "orbfe_refresh_map_points_batch_device",
 ]
 
 
@@ -326,6 +339,8 @@ def lib():
     L.orbfe_kfdb_detect_loop.argtypes = [vp, ci, vp, vp, vp, vp, vp, vp, ci, vp, vp, vp, vp, vp]
     L.orbfe_kfdb_detect_relocalization_device.argtypes = [vp, ci, vp, vp, vp, ci, vp, vp, vp, vp, vp, vp]
     L.orbfe_kfdb_detect_loop_device.argtypes = [vp, ci, vp, vp, vp, vp, vp, vp, ci, vp, vp, vp, vp, vp, vp]
+    L.orbfe_refresh_map_points.argtypes = [vp, ci, vp, ci, vp, vp, ci, vp, ci, ci, vp]
+    L.orbfe_refresh_map_points_batch_device.argtypes = [ci, vp, ci, vp, ci, vp, vp, ci, vp, ci, ci, vp, vp]
     for name in EXPORTS:
         if name != "orbfe_last_error":
             getattr(L, name).restype = ci
