@@ -19,6 +19,7 @@
 #include <mutex>
 #include <vector>
 
+#include "host_internal.h"
 #include "orbfe_internal.h"
 
 void orbfe_launch_copy0(const uint8_t* src, int sstride, size_t simg, uint8_t* dst, int dpitch, size_t dimg, int w,
@@ -35,15 +36,6 @@ void orbfe_set_error(const char* fmt, ...) {
   va_end(ap);
 }
 extern "C" const char* orbfe_last_error(void) { return g_err; }
-
-#define HIPCHK(expr)                                                                              \
-  do {                                                                                            \
-    hipError_t _e = (expr);                                                                       \
-    if (_e != hipSuccess) {                                                                       \
-      orbfe_set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
-      return ORBFE_ERR_HIP;                                                                       \
-    }                                                                                             \
-  } while (0)
 
 extern "C" int orbfe_device_count(int* count) {
   if (!count) return ORBFE_ERR_INVALID;

@@ -77,7 +77,7 @@ int ensure_block(orbfe_kfdb* db, size_t bytes) {
   db->block_cap = 0;
   hipError_t e = hipMalloc((void**)&db->d_block, want);
   if (e == hipSuccess) e = hipHostMalloc((void**)&db->h_block, want, hipHostMallocDefault);
-  if (e != hipSuccess) return hip_fail("kfdb: work space", e);
+  if (e != hipSuccess) return hip_status("kfdb: work space", e);
   db->block_cap = want;
   return ORBFE_OK;
 }
@@ -184,7 +184,7 @@ int resolve_neighbours(orbfe_kfdb* db) {
       }
     }
     const hipError_t e = hipMemcpy(db->d_neigh, rows.data(), rows.size() * sizeof(int32_t), hipMemcpyHostToDevice);
-    if (e != hipSuccess) return hip_fail("kfdb: neighbour rows", e);
+    if (e != hipSuccess) return hip_status("kfdb: neighbour rows", e);
   }
   db->neigh_dirty = false;
   return ORBFE_OK;
@@ -254,7 +254,7 @@ int detect_host(orbfe_kfdb* db, int loop, int Q, const int32_t* q_off, const int
   }
   hipStream_t s = db->stream;
   hipError_t e = hipMemcpyAsync(d, h, in_end, hipMemcpyHostToDevice, s);
-  if (e != hipSuccess) return hip_fail(where, e);
+  if (e != hipSuccess) return hip_status(where, e);
   L.Q = Q; L.loop = loop; L.fused = g_arrangement.load();
   L.q_off = (const int32_t*)(d + o_qoff); L.q_ids = (const int32_t*)(d + o_qids); L.q_vals = (const double*)(d + o_qvals);
   L.min_score = (const float*)(d + o_ms); L.c_off = (const int32_t*)(d + o_coff); L.c_ids = (const int64_t*)(d + o_cids);
@@ -263,7 +263,7 @@ int detect_host(orbfe_kfdb* db, int loop, int Q, const int32_t* q_off, const int
   e = hipGetLastError();
   if (e == hipSuccess) e = hipMemcpyAsync(h + o_ncand, d + o_ncand, out_end - o_ncand, hipMemcpyDeviceToHost, s);
   const hipError_t e2 = hipStreamSynchronize(s);   // also on an error: the stream may still read the pinned block
-  if (e != hipSuccess || e2 != hipSuccess) return hip_fail(where, e != hipSuccess ? e : e2);
+  if (e != hipSuccess || e2 != hipSuccess) return hip_status(where, e != hipSuccess ? e : e2);
   const int32_t* h_n = (const int32_t*)(h + o_ncand);
   const orbfe_kfdb_query_info* h_info = (const orbfe_kfdb_query_info*)(h + o_info);
   memcpy(n_cand, h_n, (size_t)Q * 4);
@@ -328,7 +328,7 @@ int detect_device(orbfe_kfdb* db, int loop, int Q, const int32_t* q_off, const i
   L.cand = cand; L.cand_cap = cand_cap; L.n_cand = n_cand; L.info = info; L.o_words = common_words; L.o_scores = scores;
   orbfe_launch_kfdb_detect(L, (hipStream_t)stream);
   const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return hip_fail(where, e);
+  if (e != hipSuccess) return hip_status(where, e);
   return ORBFE_OK;
 }
 
@@ -375,7 +375,7 @@ extern "C" int orbfe_kfdb_create(int n_words, int scoring, int device, orbfe_kfd
   const hipError_t e = hipStreamCreateWithFlags(&db->stream, hipStreamNonBlocking);
   if (e != hipSuccess) {
     delete db;
-    return hip_fail("kfdb create: stream", e);
+    return hip_status("kfdb create: stream", e);
   }
   *out = db;
   return ORBFE_OK;
@@ -411,7 +411,7 @@ extern "C" int orbfe_kfdb_clear(orbfe_kfdb* db) {
   if (db->slot_cap) {   // the carried scores start at 0 again; everything else is rewritten by add
     hipError_t e = hipMemset(db->d_state, 0, (size_t)db->slot_cap * sizeof(float));
     if (e == hipSuccess) e = hipStreamSynchronize(nullptr);   // a memset may return before it ran; the queries use other streams
-    if (e != hipSuccess) return hip_fail("kfdb clear", e);
+    if (e != hipSuccess) return hip_status("kfdb clear", e);
   }
   db->slots.clear();
   db->live.clear();
@@ -471,7 +471,7 @@ extern "C" int orbfe_kfdb_add(orbfe_kfdb* db, int64_t kf_id, const int32_t* bow_
     e = grow(&db->d_slots, (size_t)s, (size_t)want);
     if (e == hipSuccess) e = grow(&db->d_state, (size_t)s, (size_t)want);
     if (e == hipSuccess) e = grow(&db->d_neigh, (size_t)s * KFDB_NEIGHBOURS, (size_t)want * KFDB_NEIGHBOURS);
-    if (e != hipSuccess) return hip_fail("kfdb add: growing the slot arrays", e);
+    if (e != hipSuccess) return hip_status("kfdb add: growing the slot arrays", e);
     db->slot_cap = want;
     db->neigh_dirty = true;
   }
@@ -480,7 +480,7 @@ extern "C" int orbfe_kfdb_add(orbfe_kfdb* db, int64_t kf_id, const int32_t* bow_
     while (want < db->pool_used + n) want *= 2;
     e = grow(&db->d_ids, (size_t)db->pool_used, (size_t)want);
     if (e == hipSuccess) e = grow(&db->d_vals, (size_t)db->pool_used, (size_t)want);
-    if (e != hipSuccess) return hip_fail("kfdb add: growing the pool", e);
+    if (e != hipSuccess) return hip_status("kfdb add: growing the pool", e);
     db->pool_cap = want;
   }
   KfdbSlot sl;
@@ -492,7 +492,7 @@ extern "C" int orbfe_kfdb_add(orbfe_kfdb* db, int64_t kf_id, const int32_t* bow_
   const float zero = 0.0f;   // mRelocScore starts at 0 here (the reference leaves it uninitialised)
   if (e == hipSuccess) e = hipMemcpy(db->d_state + s, &zero, sizeof(zero), hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMemcpy(db->d_slots + s, &sl, sizeof(sl), hipMemcpyHostToDevice);
-  if (e != hipSuccess) return hip_fail("kfdb add: upload", e);
+  if (e != hipSuccess) return hip_status("kfdb add: upload", e);
   db->slots.push_back(sl);
   db->live[kf_id] = s;
   db->pool_used += n;
@@ -513,7 +513,7 @@ extern "C" int orbfe_kfdb_erase(orbfe_kfdb* db, int64_t kf_id) {
   KfdbSlot sl = db->slots[s];
   sl.id = -1; sl.live = 0;
   const hipError_t e = hipMemcpy(db->d_slots + s, &sl, sizeof(sl), hipMemcpyHostToDevice);
-  if (e != hipSuccess) return hip_fail("kfdb erase", e);
+  if (e != hipSuccess) return hip_status("kfdb erase", e);
   db->slots[s] = sl;
   db->live.erase(it);
   db->neigh_dirty = true;
@@ -573,7 +573,7 @@ extern "C" int orbfe_kfdb_score(orbfe_kfdb* db, const int32_t* q_ids, const doub
   }
   hipStream_t s = db->stream;
   hipError_t e = hipMemcpyAsync(d, h, in_end, hipMemcpyHostToDevice, s);
-  if (e != hipSuccess) return hip_fail("kfdb score: upload", e);
+  if (e != hipSuccess) return hip_status("kfdb score: upload", e);
   KfdbLaunch L;
   memset(&L, 0, sizeof(L));
   fill_database(db, L);
@@ -583,7 +583,7 @@ extern "C" int orbfe_kfdb_score(orbfe_kfdb* db, const int32_t* q_ids, const doub
   e = hipGetLastError();
   if (e == hipSuccess) e = hipMemcpyAsync(h + o_out, d + o_out, (size_t)m * 4, hipMemcpyDeviceToHost, s);
   const hipError_t e2 = hipStreamSynchronize(s);
-  if (e != hipSuccess || e2 != hipSuccess) return hip_fail("kfdb score", e != hipSuccess ? e : e2);
+  if (e != hipSuccess || e2 != hipSuccess) return hip_status("kfdb score", e != hipSuccess ? e : e2);
   memcpy(out, h + o_out, (size_t)m * 4);
   return ORBFE_OK;
 }

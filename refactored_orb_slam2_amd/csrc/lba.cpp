@@ -71,9 +71,7 @@ extern "C" int orbfe_local_bundle_adjustment_batch_device(int P, const orbfe_pos
   L.edges = d_edges; L.kf_cap = kf_cap; L.point_cap = point_cap; L.edge_cap = edge_cap; L.flags = flags; L.poses_out = d_poses_out;
   L.points_out = d_points_out; L.erase = d_erase; L.result = d_result; L.workspace = (uint8_t*)d_workspace;
   orbfe_launch_lba(L, P, (hipStream_t)stream);
-  const hipError_t le = hipGetLastError();
-  if (le != hipSuccess) return hip_fail("local bundle adjustment batch: kernel launch failed", le);
-  return ORBFE_OK;
+  return hip_status("local bundle adjustment batch: kernel launch failed", hipGetLastError());
 }
 
 extern "C" int orbfe_local_bundle_adjustment(const orbfe_pose_camera* camera, const float* poses, const uint8_t* fixed, int n_kf,
@@ -121,25 +119,23 @@ extern "C" int orbfe_local_bundle_adjustment(const orbfe_pose_camera* camera, co
     }
   if (!have_device()) return ORBFE_ERR_NO_DEVICE;
 
-  // ONE block: [input, uploaded | output, downloaded], the same offsets in device memory and in its pinned mirror
-  Layout Lo;
-  const size_t o_cam = Lo.add(sizeof(orbfe_pose_camera)), o_prob = Lo.add(sizeof(orbfe_lba_problem)),
-               o_poses = Lo.add((size_t)n_kf * 48), o_fixed = Lo.add((size_t)n_kf), o_points = Lo.add((size_t)n_points * 12),
-               o_edges = Lo.add((size_t)n_edges * sizeof(orbfe_lba_edge));
-  const size_t in_end = Lo.off;
-  const size_t o_res = Lo.add(sizeof(orbfe_lba_result)), o_pout = Lo.add((size_t)n_kf * 48), o_xout = Lo.add((size_t)n_points * 12),
-               o_erase = Lo.add((size_t)n_edges);
-  const size_t total = Lo.off;
+  // the workspace is an allocation of its own; its guard is declared before the call, so it is freed after the call has drained
+  struct Workspace {
+    void* p = nullptr;
+    ~Workspace() {
+      if (p) (void)hipFree(p);
+    }
+  } ws;
+  HostCall c("local bundle adjustment");
+  const size_t o_cam = c.in(sizeof(orbfe_pose_camera)), o_prob = c.in(sizeof(orbfe_lba_problem)), o_poses = c.in((size_t)n_kf * 48),
+               o_fixed = c.in((size_t)n_kf), o_points = c.in((size_t)n_points * 12), o_edges = c.in((size_t)n_edges * sizeof(orbfe_lba_edge));
+  const size_t o_res = c.out(sizeof(orbfe_lba_result)), o_pout = c.out((size_t)n_kf * 48), o_xout = c.out((size_t)n_points * 12),
+               o_erase = c.out((size_t)n_edges);
   const size_t ws_bytes = problem_bytes(n_kf, n_points, n_edges);
-
-  std::unique_lock<std::mutex> lk;
-  hipStream_t s = nullptr;
-  uint8_t *d = nullptr, *h = nullptr;
   int rc;
-  if ((rc = orbfe_internal_thread_block(total, lk, &s, &d, &h))) return rc;
-  void* ws = nullptr;
-  hipError_t e = ws_bytes ? hipMalloc(&ws, ws_bytes) : hipSuccess;
-  if (e != hipSuccess) return hip_fail("local bundle adjustment: workspace", e);
+  if ((rc = c.open())) return rc;
+  if (ws_bytes && (rc = hip_status("local bundle adjustment: workspace", hipMalloc(&ws.p, ws_bytes)))) return rc;
+  uint8_t *const h = c.host(0), *const d = c.dev(0);
   memcpy(h + o_cam, camera, sizeof(orbfe_pose_camera));
   const orbfe_lba_problem prob = {0, n_kf, 0, n_points, 0, n_edges};
   memcpy(h + o_prob, &prob, sizeof(prob));
@@ -148,30 +144,19 @@ extern "C" int orbfe_local_bundle_adjustment(const orbfe_pose_camera* camera, co
   if (n_points) memcpy(h + o_points, points, (size_t)n_points * 12);
   orbfe_lba_edge* he = (orbfe_lba_edge*)(h + o_edges);
   for (int j = 0; j < n_edges; j++) he[j] = edges[order[j]];
-  // from here on the stream may still read the pinned block: an error return drains it before the handle's lock is released
-  auto done = [s, ws](int code) {
-    (void)hipStreamSynchronize(s);
-    if (ws) (void)hipFree(ws);
-    return code;
-  };
-  e = hipMemcpyAsync(d, h, in_end, hipMemcpyHostToDevice, s);
-  if (e != hipSuccess) return done(hip_fail("local bundle adjustment: upload", e));
+  if ((rc = c.upload())) return rc;
   LbaLaunch L;
   memset(&L, 0, sizeof(L));
   L.camera = (const orbfe_pose_camera*)(d + o_cam); L.problems = (const orbfe_lba_problem*)(d + o_prob);
   L.poses = (const float*)(d + o_poses); L.fixed = d + o_fixed; L.points = d + o_points; L.point_stride = 12;
   L.edges = (const orbfe_lba_edge*)(d + o_edges); L.kf_cap = n_kf; L.point_cap = n_points; L.edge_cap = n_edges; L.flags = flags;
   L.poses_out = (float*)(d + o_pout); L.points_out = (float*)(d + o_xout); L.erase = d + o_erase;
-  L.result = (orbfe_lba_result*)(d + o_res); L.workspace = (uint8_t*)ws;
-  orbfe_launch_lba(L, 1, s);
-  e = hipGetLastError();
-  if (e != hipSuccess) return done(hip_fail("local bundle adjustment: kernel launch failed", e));
-  e = hipMemcpyAsync(h + o_res, d + o_res, total - o_res, hipMemcpyDeviceToHost, s);
-  if (e == hipSuccess) e = hipStreamSynchronize(s);
-  if (e != hipSuccess) return done(hip_fail("local bundle adjustment", e));
+  L.result = (orbfe_lba_result*)(d + o_res); L.workspace = (uint8_t*)ws.p;
+  orbfe_launch_lba(L, 1, c.stream);
+  if ((rc = c.finish(c.out_bytes()))) return rc;
   memcpy(result, h + o_res, sizeof(*result));
   if (n_kf) memcpy(poses_out, h + o_pout, (size_t)n_kf * 48);
   if (n_points) memcpy(points_out, h + o_xout, (size_t)n_points * 12);
   for (int j = 0; j < n_edges; j++) erase[order[j]] = h[o_erase + j];
-  return done(ORBFE_OK);
+  return ORBFE_OK;
 }

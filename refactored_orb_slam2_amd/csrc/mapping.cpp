@@ -53,20 +53,8 @@ extern "C" int orbfe_triangulate_matches_batch_device(int K, const orbfe_tri_vie
   t.matchA = d_matchA; t.out = d_out;
   orbfe_launch_triangulate(t, K, (hipStream_t)stream);
   orbfe_launch_triangulate_count(d_out, d_nA, 0, capA, d_n_new, nullptr, 0, nullptr, K, (hipStream_t)stream);
-  const hipError_t le = hipGetLastError();
-  if (le != hipSuccess) return hip_fail("triangulation batch: kernel launch failed", le);
-  return ORBFE_OK;
+  return hip_status("triangulation batch: kernel launch failed", hipGetLastError());
 }
-
-namespace {
-// one device allocation, released on every path
-struct Staging {
-  uint8_t* base = nullptr;
-  ~Staging() {
-    if (base) (void)hipFree(base);
-  }
-};
-}  // namespace
 
 extern "C" int orbfe_triangulate_matches(const orbfe_tri_view* view1, const orbfe_keypoint* keys1, const float* u_right1,
                                          const float* depth1, int nA, const orbfe_tri_view* view2, const orbfe_keypoint* keys2,
@@ -93,46 +81,43 @@ extern "C" int orbfe_triangulate_matches(const orbfe_tri_view* view1, const orbf
   *n_new = 0;
   if (nA == 0) return ORBFE_OK;
   const int capB = nB > 0 ? nB : 1;
-  Layout L;
-  const size_t o_v1 = L.add(sizeof(orbfe_tri_view)), o_v2 = L.add(sizeof(orbfe_tri_view)), o_k1 = L.add((size_t)nA * sizeof(orbfe_keypoint)),
-               o_u1 = L.add((size_t)nA * 4), o_d1 = L.add((size_t)nA * 4), o_k2 = L.add((size_t)capB * sizeof(orbfe_keypoint)),
-               o_u2 = L.add((size_t)capB * 4), o_d2 = L.add((size_t)capB * 4), o_m = L.add((size_t)nA * 4),
-               o_out = L.add((size_t)nA * sizeof(orbfe_new_point)), o_n = L.add(4);
-  Staging st;
-  hipError_t e = hipMalloc((void**)&st.base, L.off);
-  if (e != hipSuccess) {
-    st.base = nullptr;
-    return hip_fail("triangulation: device allocation failed", e);
+  // [input, uploaded | output, downloaded]; u_right / depth have regions only when given, and reach the kernel as NULL otherwise
+  const size_t b_u2 = u_right2 ? (size_t)capB * 4 : 0;
+  HostCall c("triangulation");
+  const size_t o_v1 = c.in(sizeof(orbfe_tri_view)), o_v2 = c.in(sizeof(orbfe_tri_view)), o_k1 = c.in((size_t)nA * sizeof(orbfe_keypoint)),
+               o_u1 = c.in(u_right1 ? (size_t)nA * 4 : 0), o_d1 = c.in(u_right1 ? (size_t)nA * 4 : 0),
+               o_k2 = c.in((size_t)capB * sizeof(orbfe_keypoint)), o_u2 = c.in(b_u2), o_d2 = c.in(b_u2), o_m = c.in((size_t)nA * 4);
+  const size_t o_out = c.out((size_t)nA * sizeof(orbfe_new_point)), o_n = c.out(4);
+  int rc;
+  if ((rc = c.open())) return rc;
+  memcpy(c.host(o_v1), view1, sizeof(orbfe_tri_view));
+  memcpy(c.host(o_v2), view2, sizeof(orbfe_tri_view));
+  memcpy(c.host(o_k1), keys1, (size_t)nA * sizeof(orbfe_keypoint));
+  if (u_right1) {
+    memcpy(c.host(o_u1), u_right1, (size_t)nA * 4);
+    memcpy(c.host(o_d1), depth1, (size_t)nA * 4);
   }
-  uint8_t* d = st.base;
-  e = hipMemcpy(d + o_v1, view1, sizeof(orbfe_tri_view), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(d + o_v2, view2, sizeof(orbfe_tri_view), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(d + o_k1, keys1, (size_t)nA * sizeof(orbfe_keypoint), hipMemcpyHostToDevice);
-  if (e == hipSuccess && u_right1) e = hipMemcpy(d + o_u1, u_right1, (size_t)nA * 4, hipMemcpyHostToDevice);
-  if (e == hipSuccess && u_right1) e = hipMemcpy(d + o_d1, depth1, (size_t)nA * 4, hipMemcpyHostToDevice);
-  if (e == hipSuccess && nB > 0) e = hipMemcpy(d + o_k2, keys2, (size_t)nB * sizeof(orbfe_keypoint), hipMemcpyHostToDevice);
-  if (e == hipSuccess && nB > 0 && u_right2) e = hipMemcpy(d + o_u2, u_right2, (size_t)nB * 4, hipMemcpyHostToDevice);
-  if (e == hipSuccess && nB > 0 && u_right2) e = hipMemcpy(d + o_d2, depth2, (size_t)nB * 4, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(d + o_m, matchA, (size_t)nA * 4, hipMemcpyHostToDevice);
-  if (e == hipSuccess) {
-    TriLaunch t;
-    memset(&t, 0, sizeof(t));
-    t.view1 = (const orbfe_tri_view*)(d + o_v1); t.keys1 = (const orbfe_keypoint*)(d + o_k1);
-    t.u_right1 = u_right1 ? (const float*)(d + o_u1) : nullptr; t.depth1 = u_right1 ? (const float*)(d + o_d1) : nullptr;
-    t.nA_host = nA; t.capA = nA;
-    t.view2 = (const orbfe_tri_view*)(d + o_v2); t.keys2 = (const orbfe_keypoint*)(d + o_k2);
-    t.u_right2 = u_right2 ? (const float*)(d + o_u2) : nullptr; t.depth2 = u_right2 ? (const float*)(d + o_d2) : nullptr;
-    t.nB_host = nB; t.capB = capB;
-    t.matchA = (const int32_t*)(d + o_m); t.out = (orbfe_new_point*)(d + o_out);
-    orbfe_launch_triangulate(t, 1, (hipStream_t) nullptr);
-    orbfe_launch_triangulate_count(t.out, nullptr, nA, nA, (int32_t*)(d + o_n), nullptr, 0, nullptr, 1, (hipStream_t) nullptr);
-    e = hipGetLastError();
+  if (nB > 0) memcpy(c.host(o_k2), keys2, (size_t)nB * sizeof(orbfe_keypoint));
+  if (nB > 0 && u_right2) {
+    memcpy(c.host(o_u2), u_right2, (size_t)nB * 4);
+    memcpy(c.host(o_d2), depth2, (size_t)nB * 4);
   }
-  int32_t hn = 0;
-  if (e == hipSuccess) e = hipMemcpy(out, d + o_out, (size_t)nA * sizeof(orbfe_new_point), hipMemcpyDeviceToHost);   // waits for the kernels
-  if (e == hipSuccess) e = hipMemcpy(&hn, d + o_n, 4, hipMemcpyDeviceToHost);
-  if (e != hipSuccess) return hip_fail("triangulation", e);
-  *n_new = hn;
+  memcpy(c.host(o_m), matchA, (size_t)nA * 4);
+  if ((rc = c.upload())) return rc;
+  TriLaunch t;
+  memset(&t, 0, sizeof(t));
+  t.view1 = c.dev<const orbfe_tri_view>(o_v1); t.keys1 = c.dev<const orbfe_keypoint>(o_k1);
+  t.u_right1 = u_right1 ? c.dev<const float>(o_u1) : nullptr; t.depth1 = u_right1 ? c.dev<const float>(o_d1) : nullptr;
+  t.nA_host = nA; t.capA = nA;
+  t.view2 = c.dev<const orbfe_tri_view>(o_v2); t.keys2 = c.dev<const orbfe_keypoint>(o_k2);
+  t.u_right2 = u_right2 ? c.dev<const float>(o_u2) : nullptr; t.depth2 = u_right2 ? c.dev<const float>(o_d2) : nullptr;
+  t.nB_host = nB; t.capB = capB;
+  t.matchA = c.dev<const int32_t>(o_m); t.out = c.dev<orbfe_new_point>(o_out);
+  orbfe_launch_triangulate(t, 1, c.stream);
+  orbfe_launch_triangulate_count(t.out, nullptr, nA, nA, c.dev<int32_t>(o_n), nullptr, 0, nullptr, 1, c.stream);
+  if ((rc = c.finish(c.out_bytes()))) return rc;
+  memcpy(out, c.host(o_out), (size_t)nA * sizeof(orbfe_new_point));
+  *n_new = *c.host<const int32_t>(o_n);
   return ORBFE_OK;
 }
 
@@ -190,38 +175,33 @@ extern "C" int orbfe_create_new_map_points(const orbfe_keypoint* keysA, const ui
     active[k] = !plans[k].pairs.empty();
   }
 
-  // ONE block: [input, uploaded | scratch | output, downloaded], the same offsets in device memory and in its pinned mirror
   const size_t push_n = (size_t)std::max(totA, nA);
-  Layout L;
-  const size_t o_vw1 = L.add(sizeof(orbfe_tri_view)), o_kA = L.add((size_t)nA * sizeof(orbfe_keypoint)), o_dA = L.add((size_t)nA * 32),
-               o_uA = L.add((size_t)nA * 4), o_zA = L.add((size_t)nA * 4), o_iA = L.add((size_t)totA * 4), o_vA = L.add((size_t)nA),
-               o_sA = L.add((size_t)nA), o_vw2 = L.add((size_t)K * sizeof(orbfe_tri_view)), o_mA = L.add((size_t)K * nA * 4),
-               o_cnt = L.add((size_t)K * 256);
+  HostCall c("create new map points");
+  const size_t o_vw1 = c.in(sizeof(orbfe_tri_view)), o_kA = c.in((size_t)nA * sizeof(orbfe_keypoint)), o_dA = c.in((size_t)nA * 32),
+               o_uA = c.in((size_t)nA * 4), o_zA = c.in((size_t)nA * 4), o_iA = c.in((size_t)totA * 4), o_vA = c.in((size_t)nA),
+               o_sA = c.in((size_t)nA), o_vw2 = c.in((size_t)K * sizeof(orbfe_tri_view)), o_mA = c.in((size_t)K * nA * 4),
+               o_cnt = c.in((size_t)K * 256);
   struct NbOff { size_t pairs, keys, desc, ur, z, idx, valid, stereo; };
   std::vector<NbOff> nb((size_t)K);
   for (int k = 0; k < K; k++) {
     const orbfe_tri_neighbor& N = neighbors[k];
     const size_t n = (size_t)std::max(N.n, 1);
-    nb[k].keys = L.add(n * sizeof(orbfe_keypoint));
-    nb[k].ur = L.add(n * 4);
-    nb[k].z = L.add(n * 4);
+    nb[k].keys = c.in(n * sizeof(orbfe_keypoint));
+    nb[k].ur = c.in(n * 4);
+    nb[k].z = c.in(n * 4);
     if (!active[k]) continue;
-    nb[k].pairs = L.add(plans[k].pairs.size() * sizeof(BowPair));
-    nb[k].desc = L.add(n * 32);
-    nb[k].idx = L.add((size_t)plans[k].totB * 4);
-    nb[k].valid = L.add(n);
-    nb[k].stereo = L.add(n);
+    nb[k].pairs = c.in(plans[k].pairs.size() * sizeof(BowPair));
+    nb[k].desc = c.in(n * 32);
+    nb[k].idx = c.in((size_t)plans[k].totB * 4);
+    nb[k].valid = c.in(n);
+    nb[k].stereo = c.in(n);
   }
-  const size_t in_end = L.off;
-  const size_t o_pi = L.add(push_n * 4), o_pb = L.add(push_n);
-  const size_t o_out = L.add((size_t)K * nA * sizeof(orbfe_new_point)), o_nn = L.add((size_t)K * 4), o_nm = L.add((size_t)K * 4);
-  const size_t total = L.off;
-
-  std::unique_lock<std::mutex> lk;
-  hipStream_t s = nullptr;
-  uint8_t *d = nullptr, *h = nullptr;
+  const size_t o_pi = c.scratch(push_n * 4), o_pb = c.scratch(push_n);
+  const size_t o_out = c.out((size_t)K * nA * sizeof(orbfe_new_point)), o_nn = c.out((size_t)K * 4), o_nm = c.out((size_t)K * 4);
   int rc;
-  if ((rc = orbfe_internal_thread_block(total, lk, &s, &d, &h))) return rc;
+  if ((rc = c.open())) return rc;
+  uint8_t *const h = c.host(0), *const d = c.dev(0);
+  const hipStream_t s = c.stream;
   // pKF1, once
   memcpy(h + o_vw1, viewA, sizeof(orbfe_tri_view));
   memcpy(h + o_kA, keysA, (size_t)nA * sizeof(orbfe_keypoint));
@@ -256,13 +236,7 @@ extern "C" int orbfe_create_new_map_points(const orbfe_keypoint* keysA, const ui
       h[nb[k].valid + j] = !N.has_mp[j] && (!only_stereo || st);
     }
   }
-  hipError_t e = hipMemcpyAsync(d, h, in_end, hipMemcpyHostToDevice, s);
-  if (e != hipSuccess) return hip_fail("create new map points: upload", e);
-  // from here on the stream may still read the pinned block: an error return drains it before the handle's lock is released
-  auto drained = [s](int code) {
-    (void)hipStreamSynchronize(s);
-    return code;
-  };
+  if ((rc = c.upload())) return rc;
   for (int k = 0; k < K; k++) {
     const orbfe_tri_neighbor& N = neighbors[k];
     int32_t* d_match = (int32_t*)(d + o_mA) + (size_t)k * nA;
@@ -275,7 +249,7 @@ extern "C" int orbfe_create_new_map_points(const orbfe_keypoint* keysA, const ui
       b.validA = d + o_vA; b.validB = d + nb[k].valid; b.stereoA = d + o_sA; b.stereoB = d + nb[k].stereo;
       b.matchA = d_match; b.counters = (int32_t*)(d + o_cnt + (size_t)k * 256);
       b.push_idx = (int32_t*)(d + o_pi); b.push_bin = d + o_pb;
-      if ((rc = orbfe_tri_search_enqueue(b, &N.ep, check_orientation, plans[k].sequential, s))) return drained(rc);
+      if ((rc = orbfe_tri_search_enqueue(b, &N.ep, check_orientation, plans[k].sequential, s))) return rc;
     }
     // a neighbour without a search still gets its rows written (all "no match"): its matchA is the uploaded -1
     TriLaunch t;
@@ -292,11 +266,7 @@ extern "C" int orbfe_create_new_map_points(const orbfe_keypoint* keysA, const ui
   }
   orbfe_launch_triangulate_count((const orbfe_new_point*)(d + o_out), nullptr, nA, nA, (int32_t*)(d + o_nn), (const int32_t*)(d + o_cnt), 64,
                                  (int32_t*)(d + o_nm), K, s);
-  e = hipGetLastError();
-  if (e != hipSuccess) return drained(hip_fail("create new map points: kernel launch failed", e));
-  e = hipMemcpyAsync(h + o_out, d + o_out, total - o_out, hipMemcpyDeviceToHost, s);
-  if (e == hipSuccess) e = hipStreamSynchronize(s);
-  if (e != hipSuccess) return drained(hip_fail("create new map points", e));
+  if ((rc = c.finish(c.out_bytes()))) return rc;
   memcpy(points, h + o_out, (size_t)K * nA * sizeof(orbfe_new_point));
   memcpy(n_new, h + o_nn, (size_t)K * 4);
   memcpy(n_matches, h + o_nm, (size_t)K * 4);

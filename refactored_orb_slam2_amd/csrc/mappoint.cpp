@@ -62,7 +62,7 @@ extern "C" int orbfe_refresh_map_points_batch_device(int P, const orbfe_mp_keyfr
   L.out = d_updates;
   orbfe_launch_refresh_map_points(L, (hipStream_t)stream);
   const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return hip_fail("refresh map points batch: kernel launch failed", e);
+  if (e != hipSuccess) return hip_status("refresh map points batch: kernel launch failed", e);
   return ORBFE_OK;
 }
 
@@ -90,18 +90,14 @@ extern "C" int orbfe_refresh_map_points(const orbfe_mp_keyframe* keyframes, int 
     }
   if (!have_device()) return ORBFE_ERR_NO_DEVICE;
 
-  // ONE block: [input, uploaded | output, downloaded], the same offsets in device memory and in its pinned mirror
-  Layout Lo;
-  const size_t o_kf = Lo.add((size_t)n_kf * sizeof(orbfe_mp_keyframe)), o_obs = Lo.add((size_t)n_obs_total * sizeof(orbfe_mp_obs)),
-               o_pts = Lo.add((size_t)P * sizeof(orbfe_mp_point)), o_pos = Lo.add((size_t)P * 12),
-               o_desc = Lo.add(want_desc ? (size_t)n_obs_total * 32 : 0);
-  const size_t in_end = Lo.off;
-  const size_t o_out = Lo.add((size_t)P * sizeof(orbfe_mp_update));
-  std::unique_lock<std::mutex> lk;
-  hipStream_t s = nullptr;
-  uint8_t *d = nullptr, *h = nullptr;
+  HostCall c(where);
+  const size_t o_kf = c.in((size_t)n_kf * sizeof(orbfe_mp_keyframe)), o_obs = c.in((size_t)n_obs_total * sizeof(orbfe_mp_obs)),
+               o_pts = c.in((size_t)P * sizeof(orbfe_mp_point)), o_pos = c.in((size_t)P * 12),
+               o_desc = c.in(want_desc ? (size_t)n_obs_total * 32 : 0);
+  const size_t o_out = c.out((size_t)P * sizeof(orbfe_mp_update));
   int rc;
-  if ((rc = orbfe_internal_thread_block(Lo.off, lk, &s, &d, &h))) return rc;
+  if ((rc = c.open())) return rc;
+  uint8_t *const h = c.host(0), *const d = c.dev(0);
   if (n_kf) memcpy(h + o_kf, keyframes, (size_t)n_kf * sizeof(orbfe_mp_keyframe));
   if (n_obs_total) memcpy(h + o_obs, obs, (size_t)n_obs_total * sizeof(orbfe_mp_obs));
   memcpy(h + o_pts, points, (size_t)P * sizeof(orbfe_mp_point));
@@ -115,19 +111,15 @@ extern "C" int orbfe_refresh_map_points(const orbfe_mp_keyframe* keyframes, int 
       else
         memset(row, 0, 32);
     }
-  hipError_t e = hipMemcpyAsync(d, h, in_end, hipMemcpyHostToDevice, s);
-  if (e != hipSuccess) return hip_fail("refresh map points: upload", e);
+  if ((rc = c.upload())) return rc;
   MpLaunch L;
   fill(L, P, n_kf, n_obs_total, scale_factors, n_levels, flags);
   L.kfs = (const orbfe_mp_keyframe*)(d + o_kf); L.obs = (const orbfe_mp_obs*)(d + o_obs); L.points = (const orbfe_mp_point*)(d + o_pts);
   L.pos = d + o_pos; L.pos_stride = 12;
   L.staged = d + o_desc;   // also without the descriptor half: the table's addresses are the host's and are never read
   L.out = (orbfe_mp_update*)(d + o_out);
-  orbfe_launch_refresh_map_points(L, s);
-  e = hipGetLastError();
-  if (e == hipSuccess) e = hipMemcpyAsync(h + o_out, d + o_out, (size_t)P * sizeof(orbfe_mp_update), hipMemcpyDeviceToHost, s);
-  const hipError_t e2 = hipStreamSynchronize(s);   // also on an error: the stream may still read the pinned block
-  if (e != hipSuccess || e2 != hipSuccess) return hip_fail(where, e != hipSuccess ? e : e2);
+  orbfe_launch_refresh_map_points(L, c.stream);
+  if ((rc = c.finish((size_t)P * sizeof(orbfe_mp_update)))) return rc;
   const orbfe_mp_update* r = (const orbfe_mp_update*)(h + o_out);
   for (int p = 0; p < P; p++) {   // the status and the selected halves
     orbfe_mp_update& U = updates[p];

@@ -21,15 +21,6 @@
 int orbfe_internal_pyr_view(const orbfe_extractor* e, PyrView* v, int* n_images);
 int orbfe_internal_tables(const orbfe_extractor* e, float* scale, float* inv_scale, int* n_levels, int* device);
 
-#define HIPCHK(expr)                                                                              \
-  do {                                                                                            \
-    hipError_t _e = (expr);                                                                       \
-    if (_e != hipSuccess) {                                                                       \
-      orbfe_set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
-      return ORBFE_ERR_HIP;                                                                       \
-    }                                                                                             \
-  } while (0)
-
 #define ORBFE_MAX_CAND 64  // stored candidates per query; longer lists are re-enumerated by the resolver
 
 struct MBuf {
@@ -57,37 +48,16 @@ static int pin_alloc(void*& p, size_t& have, size_t bytes) {
   have = bytes;
   return ORBFE_OK;
 }
-// Results of the one-frame host entry points (stereo association, projection searches) leave the device staging block for its
-// pinned mirror by a copy kernel of four workgroups (pipeline_kernels.hip) instead of hipMemcpyAsync: the runtime's device-to-host
-// path costs ~8 us more per call (ComputeStereoMatches 0.088 -> 0.080 ms, SearchByProjection(cur, last) 0.181 -> 0.179 per frame;
-// the same kernel for the packed INPUT -- reads over the link -- measured no gain and stays a DMA copy).  Both blocks are 256-byte granular.
-#ifndef HOST_D2H_KERNEL
-#define HOST_D2H_KERNEL 1
-#endif
-static hipError_t packed_h2d(void* d, const void* h, size_t bytes, hipStream_t s) {
-  return hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, s);
-}
-static hipError_t packed_d2h(void* h, const void* d, size_t bytes, hipStream_t s) {
-#if HOST_D2H_KERNEL
-  orbfe_launch_copy_block(d, h, bytes, 4, s);
-  return hipGetLastError();
-#else
-  return hipMemcpyAsync(h, d, bytes, hipMemcpyDeviceToHost, s);
-#endif
-}
 
 struct orbfe_matcher {
   int device = 0;
   hipStream_t stream = nullptr;
   // scratch
   MBuf cell_start, cell_idx, cell_rec, cand, n_cand, push_idx, push_bin, sad, bucket_start, bucket_idx;
-  // staging for the host-pointer entry points
-  MBuf h_keys, h_desc, h_ur, h_q, h_n, h_nq, h_blocked, h_assigned, h_nm;
-  // SearchLocalPoints: generated queries (device) and staging of the host entry point
-  MBuf lp_q, lp_pts, lp_fr, lp_track, lp_cnt;
-  // the per-frame host-pointer entry points (orbfe_stereo_match, the SearchByProjection family): ONE packed upload and ONE packed
-  // download per call through a pinned host mirror of a device staging buffer -- every hipMemcpyAsync costs 5-10 us of latency
-  MBuf st_in, st_out;
+  // SearchLocalPoints / the keyframe searches: generated queries
+  MBuf lp_q;
+  // the one-problem host entry points (HostCall): a device staging block and its pinned host mirror
+  MBuf st_in;
   void* h_pin = nullptr;
   size_t h_pin_bytes = 0;
   std::mutex mu;
@@ -120,9 +90,8 @@ extern "C" int orbfe_matcher_destroy(orbfe_matcher* m) {
   if (!m) return ORBFE_OK;
   (void)hipSetDevice(m->device);
   if (m->stream) (void)hipStreamSynchronize(m->stream);
-  MBuf* bufs[] = {&m->cell_start, &m->cell_idx, &m->cell_rec, &m->cand, &m->n_cand, &m->push_idx, &m->push_bin, &m->sad, &m->bucket_start, &m->bucket_idx, &m->h_keys,
-                  &m->h_desc, &m->h_ur, &m->h_q, &m->h_n, &m->h_nq, &m->h_blocked, &m->h_assigned, &m->h_nm,
-                  &m->lp_q, &m->lp_pts, &m->lp_fr, &m->lp_track, &m->lp_cnt, &m->st_in, &m->st_out};
+  MBuf* bufs[] = {&m->cell_start, &m->cell_idx, &m->cell_rec, &m->cand, &m->n_cand, &m->push_idx, &m->push_bin, &m->sad, &m->bucket_start, &m->bucket_idx,
+                  &m->lp_q, &m->st_in};
   for (auto b : bufs)
     if (b->p) (void)hipFree(b->p);
   if (m->h_pin) (void)hipHostFree(m->h_pin);
@@ -137,15 +106,6 @@ extern "C" int orbfe_matcher_sync(orbfe_matcher* m) {
   return ORBFE_OK;
 }
 
-static int launch_ok() {
-  hipError_t le = hipGetLastError();
-  if (le != hipSuccess) {
-    orbfe_set_error("kernel launch failed: %s", hipGetErrorString(le));
-    return ORBFE_ERR_HIP;
-  }
-  return ORBFE_OK;
-}
-
 // ------------------------------------------------------------------------------------------------ Hamming
 extern "C" int orbfe_hamming_matrix_device(const uint8_t* d_A, int nA, const uint8_t* d_B, int nB, uint16_t* d_dist,
                                            void* stream) {
@@ -155,7 +115,7 @@ extern "C" int orbfe_hamming_matrix_device(const uint8_t* d_A, int nA, const uin
     return ORBFE_ERR_INVALID;
   }
   orbfe_launch_hamming_matrix(d_A, nA, d_B, nB, d_dist, (hipStream_t)stream);
-  return launch_ok();
+  return hip_status("kernel launch failed", hipGetLastError());
 }
 
 extern "C" int orbfe_hamming_bf_device(const uint8_t* d_A, const int32_t* d_nA, int strideA, int max_nA,
@@ -173,7 +133,7 @@ extern "C" int orbfe_hamming_bf_device(const uint8_t* d_A, const int32_t* d_nA, 
   }
   HammingBfParams p{d_A, d_nA, strideA, d_B, d_nB, strideB, d_groupA, d_groupB, d_maskB, d_out};
   orbfe_launch_hamming_bf(p, max_nA, n_sets, (hipStream_t)stream);
-  return launch_ok();
+  return hip_status("kernel launch failed", hipGetLastError());
 }
 
 // ------------------------------------------------------------------------------------------------ projection
@@ -232,7 +192,7 @@ static int proj_enqueue(orbfe_matcher* m, int n_frames, const orbfe_keypoint* d_
     orbfe_launch_proj_resolve(fb, qb, (const orbfe_cand*)m->cand.p, (const int32_t*)m->n_cand.p, ORBFE_MAX_CAND, mode,
                               th_high, nnratio, check_ori, d_blocked, d_assigned, d_nm, (int32_t*)m->push_idx.p,
                               (uint8_t*)m->push_bin.p, n_frames, s);
-  return launch_ok();
+  return hip_status("kernel launch failed", hipGetLastError());
 }
 
 extern "C" int orbfe_proj_match_batch_device(orbfe_matcher* m, int n_frames, const orbfe_keypoint* d_kps,
@@ -276,31 +236,73 @@ extern "C" int orbfe_thread_release(void) {
   return orbfe_matcher_destroy(m);
 }
 
-// uploads one host frame + queries; returns device pointers inside the handle's staging buffers
-static int stage_host(orbfe_matcher* m, const orbfe_frame_view* f, const orbfe_query* q, int nq, hipStream_t s) {
+// ------------------------------------------------------------------------------------------------ HostCall (host_internal.h)
+int HostCall::open() {
   int rc;
-  const int n = std::max(f->n, 1), nqq = std::max(nq, 1);
-  if ((rc = mb_alloc(m->h_keys, sizeof(orbfe_keypoint) * n))) return rc;
-  if ((rc = mb_alloc(m->h_desc, (size_t)32 * n))) return rc;
-  if ((rc = mb_alloc(m->h_ur, sizeof(float) * n))) return rc;
-  if ((rc = mb_alloc(m->h_q, sizeof(orbfe_query) * nqq))) return rc;
-  if ((rc = mb_alloc(m->h_n, 16))) return rc;
-  if ((rc = mb_alloc(m->h_nq, 16))) return rc;
-  if ((rc = mb_alloc(m->h_blocked, (size_t)n + 16))) return rc;
-  if ((rc = mb_alloc(m->h_assigned, sizeof(int32_t) * n))) return rc;
-  if ((rc = mb_alloc(m->h_nm, 16))) return rc;
-  if (f->n > 0) {
-    HIPCHK(hipMemcpyAsync(m->h_keys.p, f->keys_un, sizeof(orbfe_keypoint) * f->n, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(m->h_desc.p, f->desc, (size_t)32 * f->n, hipMemcpyHostToDevice, s));
-    if (f->u_right) HIPCHK(hipMemcpyAsync(m->h_ur.p, f->u_right, sizeof(float) * f->n, hipMemcpyHostToDevice, s));
-  }
-  if (nq > 0) HIPCHK(hipMemcpyAsync(m->h_q.p, q, sizeof(orbfe_query) * nq, hipMemcpyHostToDevice, s));
-  int32_t nn = f->n, nnq = nq;
-  HIPCHK(hipMemcpyAsync(m->h_n.p, &nn, 4, hipMemcpyHostToDevice, s));
-  HIPCHK(hipMemcpyAsync(m->h_nq.p, &nnq, 4, hipMemcpyHostToDevice, s));
-  HIPCHK(hipStreamSynchronize(s));  // nn / nnq live on this stack frame
+  if ((rc = tls_matcher(&m))) return rc;
+  lk = std::unique_lock<std::mutex>(m->mu);
+  HIPCHK(hipSetDevice(m->device));
+  if ((rc = mb_alloc(m->st_in, total())) || (rc = pin_alloc(m->h_pin, m->h_pin_bytes, total()))) return rc;
+  stream = m->stream;
+  d = (uint8_t*)m->st_in.p;
+  h = (uint8_t*)m->h_pin;
   return ORBFE_OK;
 }
+
+int HostCall::upload(bool through_output) {
+  in_flight = true;
+  return status(hipMemcpyAsync(d, h, through_output ? total() : in_end(), hipMemcpyHostToDevice, stream));
+}
+
+// HOST_COPY_KERNEL: the runtime's device-to-host path costs ~8 us more per call than a copy kernel of four workgroups writing the
+// pinned mirror (ComputeStereoMatches 0.088 -> 0.080 ms, SearchByProjection(cur, last) 0.181 -> 0.179 per frame; the same kernel for
+// the packed INPUT -- reads over the link -- measured no gain, so the upload is always a DMA copy).
+int HostCall::finish(size_t bytes, HostDownload how) {
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess && bytes) {
+    if (how == HOST_COPY_KERNEL) {
+      orbfe_launch_copy_block(d + out_begin(), h + out_begin(), bytes, 4, stream);
+      e = hipGetLastError();
+    } else {
+      e = hipMemcpyAsync(h + out_begin(), d + out_begin(), bytes, hipMemcpyDeviceToHost, stream);
+    }
+  }
+  const hipError_t e2 = hipStreamSynchronize(stream);   // also on an error: the stream may still read the pinned block
+  in_flight = false;
+  return status(e != hipSuccess ? e : e2);
+}
+
+HostCall::~HostCall() {
+  if (in_flight) (void)hipStreamSynchronize(stream);
+}
+
+// The input regions of one host frame in front of a projection search: [n, nq | keys | desc | mvuRight], sized for at least one
+// keypoint so that an empty frame still hands the kernels addresses inside the block.
+struct FrameRegions {
+  size_t hdr, keys, desc, ur;
+  int cap;
+  bool has_ur;
+};
+static FrameRegions frame_regions(HostCall& c, const orbfe_frame_view* f, bool with_ur) {
+  FrameRegions r;
+  r.cap = std::max(f->n, 1);
+  r.has_ur = with_ur && f->u_right;
+  r.hdr = c.in(16);
+  r.keys = c.in(sizeof(orbfe_keypoint) * (size_t)r.cap);
+  r.desc = c.in((size_t)32 * r.cap);
+  r.ur = c.in(r.has_ur ? sizeof(float) * (size_t)r.cap : 0);
+  return r;
+}
+static void frame_fill(const HostCall& c, const FrameRegions& r, const orbfe_frame_view* f, int nq) {
+  c.host<int32_t>(r.hdr)[0] = f->n;
+  c.host<int32_t>(r.hdr)[1] = nq;
+  if (f->n == 0) return;
+  memcpy(c.host(r.keys), f->keys_un, sizeof(orbfe_keypoint) * (size_t)f->n);
+  memcpy(c.host(r.desc), f->desc, (size_t)32 * f->n);
+  if (r.has_ur) memcpy(c.host(r.ur), f->u_right, sizeof(float) * (size_t)f->n);
+}
+static const int32_t* frame_n(const HostCall& c, const FrameRegions& r) { return c.dev<const int32_t>(r.hdr); }
+static const int32_t* frame_nq(const HostCall& c, const FrameRegions& r) { return c.dev<const int32_t>(r.hdr) + 1; }
 
 static bool frame_ok(const orbfe_frame_view* f) {
   if (f && f->n > 65535) {   // keypoint indices travel as 16-bit fields next to the distance
@@ -314,27 +316,24 @@ extern "C" int orbfe_proj_candidates(const orbfe_frame_view* f, const orbfe_quer
                                      int32_t* n_cand, int max_cand) {
   if (!frame_ok(f) || nq < 0 || (nq > 0 && (!q || !cand || !n_cand)) || max_cand < 1) return ORBFE_ERR_INVALID;
   if (nq == 0) return ORBFE_OK;
-  orbfe_matcher* m;
+  HostCall c("orbfe_proj_candidates");
+  const FrameRegions fr = frame_regions(c, f, true);
+  const size_t b_cand = sizeof(orbfe_cand) * (size_t)nq * max_cand;
+  const size_t o_q = c.in(sizeof(orbfe_query) * (size_t)nq), o_cand = c.out(b_cand), o_nc = c.out(sizeof(int32_t) * (size_t)nq);
   int rc;
-  if ((rc = tls_matcher(&m))) return rc;
-  std::lock_guard<std::mutex> lk(m->mu);
-  HIPCHK(hipSetDevice(m->device));
-  hipStream_t s = m->stream;
-  if ((rc = stage_host(m, f, q, nq, s))) return rc;
-  const int cap = std::max(f->n, 1);
-  if ((rc = ensure_proj_scratch(m, 1, cap, nq))) return rc;
-  // a caller-chosen max_cand needs its own candidate buffer size
-  if ((rc = mb_alloc(m->cand, (size_t)nq * std::max(max_cand, ORBFE_MAX_CAND) * sizeof(orbfe_cand)))) return rc;
+  if ((rc = c.open()) || (rc = ensure_proj_scratch(c.m, 1, fr.cap, nq))) return rc;
+  frame_fill(c, fr, f, nq);
+  memcpy(c.host(o_q), q, sizeof(orbfe_query) * (size_t)nq);
+  if ((rc = c.upload())) return rc;
   FrameBatch fb;
-  fill_frame_batch(m, fb, (const orbfe_keypoint*)m->h_keys.p, (const uint8_t*)m->h_desc.p, (const int32_t*)m->h_n.p,
-                   f->u_right ? (const float*)m->h_ur.p : nullptr, cap, f->min_x, f->max_x, f->min_y, f->max_y);
-  QueryBatch qb{(const orbfe_query*)m->h_q.p, (const int32_t*)m->h_nq.p, nq};
-  orbfe_launch_grid_build(fb, 1, s);
-  orbfe_launch_proj_candidates(fb, qb, (orbfe_cand*)m->cand.p, (int32_t*)m->n_cand.p, max_cand, 1, s);
-  if ((rc = launch_ok())) return rc;
-  HIPCHK(hipMemcpyAsync(cand, m->cand.p, sizeof(orbfe_cand) * (size_t)nq * max_cand, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipMemcpyAsync(n_cand, m->n_cand.p, sizeof(int32_t) * nq, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
+  fill_frame_batch(c.m, fb, c.dev<const orbfe_keypoint>(fr.keys), c.dev(fr.desc), frame_n(c, fr), fr.has_ur ? c.dev<const float>(fr.ur) : nullptr,
+                   fr.cap, f->min_x, f->max_x, f->min_y, f->max_y);
+  QueryBatch qb{c.dev<const orbfe_query>(o_q), frame_nq(c, fr), nq};
+  orbfe_launch_grid_build(fb, 1, c.stream);
+  orbfe_launch_proj_candidates(fb, qb, c.dev<orbfe_cand>(o_cand), c.dev<int32_t>(o_nc), max_cand, 1, c.stream);
+  if ((rc = c.finish(c.out_bytes()))) return rc;
+  memcpy(cand, c.host(o_cand), b_cand);
+  memcpy(n_cand, c.host(o_nc), sizeof(int32_t) * (size_t)nq);
   // the kernel keeps the candidate's octave in bits 16..19 of dist for the resolver; the public field is the distance
   for (int i = 0; i < nq; i++)
     for (int c = 0; c < std::min(n_cand[i], max_cand); c++) cand[(size_t)i * max_cand + c].dist &= 0xffff;
@@ -347,44 +346,28 @@ static int search_host(const orbfe_frame_view* f, const orbfe_query* q, int nq, 
   if (!frame_ok(f) || nq < 0 || (nq > 0 && !q) || !blocked || !assigned || !n_matches) return ORBFE_ERR_INVALID;
   *n_matches = 0;
   if (nq == 0 || f->n == 0) return ORBFE_OK;
-  orbfe_matcher* m;
-  int rc;
-  if ((rc = tls_matcher(&m))) return rc;
-  std::lock_guard<std::mutex> lk(m->mu);
-  HIPCHK(hipSetDevice(m->device));
-  hipStream_t s = m->stream;
   // one packed upload [n, nq | keys | desc | mvuRight | queries | blocked | assigned | n_matches], the three kernels, one packed
   // download of the tail [blocked | assigned | n_matches]
   const size_t n = (size_t)f->n;
-  const bool ur = f->u_right && stereo_gate;
-  Layout L;
-  const size_t o_hdr = L.add(16), o_keys = L.add(sizeof(orbfe_keypoint) * n), o_desc = L.add(32 * n);
-  const size_t o_ur = L.add(ur ? sizeof(float) * n : 0), o_q = L.add(sizeof(orbfe_query) * (size_t)nq);
-  const size_t o_out = L.off;
-  const size_t o_blocked = L.add(n), o_assigned = L.add(sizeof(int32_t) * n), o_nm = L.add(16);
-  if ((rc = pin_alloc(m->h_pin, m->h_pin_bytes, L.off)) || (rc = mb_alloc(m->st_in, L.off))) return rc;
-  uint8_t* h = (uint8_t*)m->h_pin;
-  uint8_t* d = (uint8_t*)m->st_in.p;
-  ((int32_t*)(h + o_hdr))[0] = f->n;
-  ((int32_t*)(h + o_hdr))[1] = nq;
-  memcpy(h + o_keys, f->keys_un, sizeof(orbfe_keypoint) * n);
-  memcpy(h + o_desc, f->desc, 32 * n);
-  if (ur) memcpy(h + o_ur, f->u_right, sizeof(float) * n);
-  memcpy(h + o_q, q, sizeof(orbfe_query) * (size_t)nq);
-  memcpy(h + o_blocked, blocked, n);
-  memcpy(h + o_assigned, assigned, sizeof(int32_t) * n);
-  *(int32_t*)(h + o_nm) = 0;
-  HIPCHK(packed_h2d(d, h, L.off, s));
-  rc = proj_enqueue(m, 1, (const orbfe_keypoint*)(d + o_keys), d + o_desc, (const int32_t*)(d + o_hdr),
-                    ur ? (const float*)(d + o_ur) : nullptr, f->n, f->min_x, f->max_x, f->min_y, f->max_y,
-                    (const orbfe_query*)(d + o_q), (const int32_t*)(d + o_hdr) + 1, nq, mode, nnratio, check_ori, d + o_blocked,
-                    (int32_t*)(d + o_assigned), (int32_t*)(d + o_nm), true, s, th_high);
-  if (rc) { (void)hipStreamSynchronize(s); return rc; }
-  HIPCHK(packed_d2h(h + o_out, d + o_out, L.off - o_out, s));
-  HIPCHK(hipStreamSynchronize(s));
-  memcpy(blocked, h + o_blocked, n);
-  memcpy(assigned, h + o_assigned, sizeof(int32_t) * n);
-  *n_matches = *(const int32_t*)(h + o_nm);
+  HostCall c("search by projection");
+  const FrameRegions fr = frame_regions(c, f, stereo_gate);
+  const size_t o_q = c.in(sizeof(orbfe_query) * (size_t)nq);
+  const size_t o_blocked = c.out(n), o_assigned = c.out(sizeof(int32_t) * n), o_nm = c.out(16);
+  int rc;
+  if ((rc = c.open())) return rc;
+  frame_fill(c, fr, f, nq);
+  memcpy(c.host(o_q), q, sizeof(orbfe_query) * (size_t)nq);
+  memcpy(c.host(o_blocked), blocked, n);
+  memcpy(c.host(o_assigned), assigned, sizeof(int32_t) * n);
+  *c.host<int32_t>(o_nm) = 0;
+  if ((rc = c.upload(true))) return rc;
+  rc = proj_enqueue(c.m, 1, c.dev<const orbfe_keypoint>(fr.keys), c.dev(fr.desc), frame_n(c, fr), fr.has_ur ? c.dev<const float>(fr.ur) : nullptr,
+                    f->n, f->min_x, f->max_x, f->min_y, f->max_y, c.dev<const orbfe_query>(o_q), frame_nq(c, fr), nq, mode, nnratio, check_ori,
+                    c.dev(o_blocked), c.dev<int32_t>(o_assigned), c.dev<int32_t>(o_nm), true, c.stream, th_high);
+  if (rc || (rc = c.finish(c.out_bytes(), HOST_COPY_KERNEL))) return rc;
+  memcpy(blocked, c.host(o_blocked), n);
+  memcpy(assigned, c.host(o_assigned), sizeof(int32_t) * n);
+  *n_matches = *c.host<const int32_t>(o_nm);
   return ORBFE_OK;
 }
 
@@ -409,7 +392,7 @@ extern "C" int orbfe_unproject_stereo_device(int n_frames, const orbfe_keypoint*
     return ORBFE_ERR_INVALID;
   }
   orbfe_launch_unproject_stereo(d_kps, d_desc, d_n, d_depth, cap, d_cam, observed, d_points, n_frames, (hipStream_t)stream);
-  return launch_ok();
+  return hip_status("kernel launch failed", hipGetLastError());
 }
 
 extern "C" int orbfe_track_queries_device(int n_frames, const orbfe_track_pose* d_pose, const orbfe_last_point* d_points,
@@ -418,7 +401,7 @@ extern "C" int orbfe_track_queries_device(int n_frames, const orbfe_track_pose* 
   if (!d_pose || !d_points || !d_n_points || !d_queries || !d_nq || n_frames < 1 || p_cap < 1) return ORBFE_ERR_INVALID;
   if (((uintptr_t)d_pose & 3) || ((uintptr_t)d_points & 3) || ((uintptr_t)d_queries & 3)) return ORBFE_ERR_INVALID;
   orbfe_launch_track_queries(d_pose, d_points, d_n_points, p_cap, frame_shift, d_queries, d_nq, n_frames, (hipStream_t)stream);
-  return launch_ok();
+  return hip_status("kernel launch failed", hipGetLastError());
 }
 
 extern "C" int orbfe_track_queries_stereo_device(int n_frames, const orbfe_keypoint* d_kps, const uint8_t* d_desc, const int32_t* d_n,
@@ -445,7 +428,7 @@ extern "C" int orbfe_track_queries_stereo_device(int n_frames, const orbfe_keypo
   }
   orbfe_launch_track_queries_stereo(d_kps, d_desc, d_n, d_depth, cap, d_cam, observed, d_carry_kps, d_carry_desc, d_carry_n, d_carry_depth,
                                     d_carry_cam, d_pose, frame_shift, d_queries, d_nq, n_frames, (hipStream_t)stream);
-  return launch_ok();
+  return hip_status("kernel launch failed", hipGetLastError());
 }
 
 // ---- Tracking::SearchLocalPoints (L/src/Tracking.cc:1050-1078): isInFrustum -> queries (in HBM) -> SearchByProjection
@@ -490,43 +473,34 @@ extern "C" int orbfe_search_local_points(const orbfe_frame_view* f, const orbfe_
   *n_to_match = 0;
   *n_matches = 0;
   if (n_points == 0) return ORBFE_OK;
-  orbfe_matcher* m;
+  // one packed upload [frame | points | frustum | blocked | assigned], one packed download [blocked | assigned | track | counts]
+  HostCall c("orbfe_search_local_points");
+  const FrameRegions r = frame_regions(c, f, true);
+  const size_t o_pts = c.in(sizeof(orbfe_map_point) * (size_t)n_points), o_fr = c.in(sizeof(orbfe_frustum));
+  const size_t o_blocked = c.out((size_t)r.cap), o_assigned = c.out(sizeof(int32_t) * (size_t)r.cap),
+               o_track = c.out(sizeof(orbfe_track) * (size_t)n_points), o_cnt = c.out(16);   // n_matches, n_to_match
   int rc;
-  if ((rc = tls_matcher(&m))) return rc;
-  std::lock_guard<std::mutex> lk(m->mu);
-  HIPCHK(hipSetDevice(m->device));
-  hipStream_t s = m->stream;
-  if ((rc = mb_alloc(m->lp_pts, sizeof(orbfe_map_point) * (size_t)n_points))) return rc;
-  if ((rc = mb_alloc(m->lp_track, sizeof(orbfe_track) * (size_t)n_points))) return rc;
-  if ((rc = mb_alloc(m->lp_fr, sizeof(orbfe_frustum)))) return rc;
-  if ((rc = mb_alloc(m->lp_cnt, 16))) return rc;
-  HIPCHK(hipMemcpyAsync(m->lp_pts.p, mp, sizeof(orbfe_map_point) * (size_t)n_points, hipMemcpyHostToDevice, s));
-  HIPCHK(hipMemcpyAsync(m->lp_fr.p, fr, sizeof(orbfe_frustum), hipMemcpyHostToDevice, s));
-  if ((rc = stage_host(m, f, nullptr, 0, s))) return rc;
-  const int32_t np = n_points;
-  HIPCHK(hipMemcpyAsync(m->h_nq.p, &np, 4, hipMemcpyHostToDevice, s));
-  const int cap = std::max(f->n, 1);
+  if ((rc = c.open())) return rc;
+  frame_fill(c, r, f, n_points);
+  memcpy(c.host(o_pts), mp, sizeof(orbfe_map_point) * (size_t)n_points);
+  memcpy(c.host(o_fr), fr, sizeof(orbfe_frustum));
   if (f->n > 0) {
-    HIPCHK(hipMemcpyAsync(m->h_blocked.p, blocked, f->n, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(m->h_assigned.p, assigned, sizeof(int32_t) * f->n, hipMemcpyHostToDevice, s));
+    memcpy(c.host(o_blocked), blocked, (size_t)f->n);
+    memcpy(c.host(o_assigned), assigned, sizeof(int32_t) * (size_t)f->n);
   }
-  rc = local_points_enqueue(m, 1, (const orbfe_keypoint*)m->h_keys.p, (const uint8_t*)m->h_desc.p, (const int32_t*)m->h_n.p,
-                            f->u_right ? (const float*)m->h_ur.p : nullptr, cap, f->min_x, f->max_x, f->min_y, f->max_y,
-                            (const orbfe_frustum*)m->lp_fr.p, (const orbfe_map_point*)m->lp_pts.p, (const int32_t*)m->h_nq.p,
-                            n_points, th, nnratio, (orbfe_track*)m->lp_track.p, (uint8_t*)m->h_blocked.p,
-                            (int32_t*)m->h_assigned.p, (int32_t*)m->lp_cnt.p, (int32_t*)m->h_nm.p, s);
-  if (rc) return rc;
-  int32_t nm = 0, ntm = 0;
-  HIPCHK(hipMemcpyAsync(track, m->lp_track.p, sizeof(orbfe_track) * (size_t)n_points, hipMemcpyDeviceToHost, s));
+  if ((rc = c.upload(true))) return rc;
+  rc = local_points_enqueue(c.m, 1, c.dev<const orbfe_keypoint>(r.keys), c.dev(r.desc), frame_n(c, r), r.has_ur ? c.dev<const float>(r.ur) : nullptr,
+                            r.cap, f->min_x, f->max_x, f->min_y, f->max_y, c.dev<const orbfe_frustum>(o_fr), c.dev<const orbfe_map_point>(o_pts),
+                            frame_nq(c, r), n_points, th, nnratio, c.dev<orbfe_track>(o_track), c.dev(o_blocked), c.dev<int32_t>(o_assigned),
+                            c.dev<int32_t>(o_cnt) + 1, c.dev<int32_t>(o_cnt), c.stream);
+  if (rc || (rc = c.finish(c.out_bytes()))) return rc;
+  memcpy(track, c.host(o_track), sizeof(orbfe_track) * (size_t)n_points);
   if (f->n > 0) {
-    HIPCHK(hipMemcpyAsync(blocked, m->h_blocked.p, f->n, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(assigned, m->h_assigned.p, sizeof(int32_t) * f->n, hipMemcpyDeviceToHost, s));
+    memcpy(blocked, c.host(o_blocked), (size_t)f->n);
+    memcpy(assigned, c.host(o_assigned), sizeof(int32_t) * (size_t)f->n);
   }
-  HIPCHK(hipMemcpyAsync(&nm, m->h_nm.p, 4, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipMemcpyAsync(&ntm, m->lp_cnt.p, 4, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
-  *n_matches = nm;
-  *n_to_match = ntm;
+  *n_matches = c.host<const int32_t>(o_cnt)[0];
+  *n_to_match = c.host<const int32_t>(o_cnt)[1];
   return ORBFE_OK;
 }
 
@@ -586,52 +560,44 @@ static int bow_impl(const uint8_t* descA, const float* angleA, const uint8_t* va
       }
     }
   }
-  orbfe_matcher* m;
+  // one packed upload [pairs | descA | descB | angleA | angleB | idxA | idxB | validA | validB | scratch | counters | matchB | matchA]
+  // (the match tables go up filled with -1, the counters zero), one packed download of the tail from the counters on
+  const size_t b_pairs = pairs.size() * sizeof(BowPair);
+  HostCall c(kf_mode ? "orbfe_search_by_bow_kf" : "orbfe_search_by_bow");
+  const size_t o_pairs = c.in(b_pairs), o_dA = c.in((size_t)nA * 32), o_dB = c.in((size_t)nB * 32), o_aA = c.in((size_t)nA * 4),
+               o_aB = c.in((size_t)nB * 4), o_iA = c.in((size_t)totA * 4), o_iB = c.in((size_t)totB * 4), o_vA = c.in((size_t)nA),
+               o_vB = c.in(kf_mode ? (size_t)nB : 0);
+  const size_t o_pi = c.scratch((size_t)nA * 4), o_pb = c.scratch((size_t)nA);
+  const size_t o_cnt = c.out(256), o_mB = c.out((size_t)nB * 4), o_mA = c.out(kf_mode ? (size_t)nA * 4 : 0);
   int rc;
-  if ((rc = tls_matcher(&m))) return rc;
-  std::lock_guard<std::mutex> lk(m->mu);
-  HIPCHK(hipSetDevice(m->device));
-  hipStream_t s = m->stream;
-  // one packed upload: [pairs | descA | descB | angleA | angleB | idxA | idxB | validA]
-  auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-  const size_t o_pairs = 0, o_dA = al(pairs.size() * sizeof(BowPair)), o_dB = o_dA + al((size_t)nA * 32),
-               o_aA = o_dB + al((size_t)nB * 32), o_aB = o_aA + al((size_t)nA * 4), o_iA = o_aB + al((size_t)nB * 4),
-               o_iB = o_iA + al((size_t)totA * 4), o_vA = o_iB + al((size_t)totB * 4), o_mB = o_vA + al((size_t)nA),
-               o_cnt = o_mB + al((size_t)nB * 4), o_pi = o_cnt + 256, o_pb = o_pi + al((size_t)nA * 4),
-               o_vB = o_pb + al((size_t)nA), o_mA = o_vB + al((size_t)nB), total = o_mA + al((size_t)nA * 4);
-  if ((rc = mb_alloc(m->h_q, total))) return rc;
-  uint8_t* d = (uint8_t*)m->h_q.p;
-  HIPCHK(hipMemcpyAsync(d + o_pairs, pairs.data(), pairs.size() * sizeof(BowPair), hipMemcpyHostToDevice, s));
-  HIPCHK(hipMemcpyAsync(d + o_dA, descA, (size_t)nA * 32, hipMemcpyHostToDevice, s));
-  HIPCHK(hipMemcpyAsync(d + o_dB, descB, (size_t)nB * 32, hipMemcpyHostToDevice, s));
-  HIPCHK(hipMemcpyAsync(d + o_aA, angleA, (size_t)nA * 4, hipMemcpyHostToDevice, s));
-  HIPCHK(hipMemcpyAsync(d + o_aB, angleB, (size_t)nB * 4, hipMemcpyHostToDevice, s));
-  HIPCHK(hipMemcpyAsync(d + o_iA, idxA, (size_t)totA * 4, hipMemcpyHostToDevice, s));
-  HIPCHK(hipMemcpyAsync(d + o_iB, idxB, (size_t)totB * 4, hipMemcpyHostToDevice, s));
-  HIPCHK(hipMemcpyAsync(d + o_vA, validA, (size_t)nA, hipMemcpyHostToDevice, s));
-  HIPCHK(hipMemsetAsync(d + o_mB, 0xff, (size_t)nB * 4, s));
-  HIPCHK(hipMemsetAsync(d + o_cnt, 0, 256, s));
-  if (kf_mode) {
-    HIPCHK(hipMemcpyAsync(d + o_vB, validB, (size_t)nB, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemsetAsync(d + o_mA, 0xff, (size_t)nA * 4, s));
-  }
+  if ((rc = c.open())) return rc;
+  memcpy(c.host(o_pairs), pairs.data(), b_pairs);
+  memcpy(c.host(o_dA), descA, (size_t)nA * 32);
+  memcpy(c.host(o_dB), descB, (size_t)nB * 32);
+  memcpy(c.host(o_aA), angleA, (size_t)nA * 4);
+  memcpy(c.host(o_aB), angleB, (size_t)nB * 4);
+  memcpy(c.host(o_iA), idxA, (size_t)totA * 4);
+  memcpy(c.host(o_iB), idxB, (size_t)totB * 4);
+  memcpy(c.host(o_vA), validA, (size_t)nA);
+  if (kf_mode) memcpy(c.host(o_vB), validB, (size_t)nB);
+  memset(c.host(o_cnt), 0, 256);
+  memset(c.host(o_mB), 0xff, (size_t)nB * 4);
+  if (kf_mode) memset(c.host(o_mA), 0xff, (size_t)nA * 4);
+  if ((rc = c.upload(true))) return rc;
   BowParams p;
-  p.pairs = (const BowPair*)(d + o_pairs);
-  p.descA = d + o_dA; p.angleA = (const float*)(d + o_aA); p.validA = d + o_vA; p.idxA = (const int32_t*)(d + o_iA);
-  p.descB = d + o_dB; p.angleB = (const float*)(d + o_aB); p.idxB = (const int32_t*)(d + o_iB);
+  p.pairs = c.dev<const BowPair>(o_pairs);
+  p.descA = c.dev(o_dA); p.angleA = c.dev<const float>(o_aA); p.validA = c.dev(o_vA); p.idxA = c.dev<const int32_t>(o_iA);
+  p.descB = c.dev(o_dB); p.angleB = c.dev<const float>(o_aB); p.idxB = c.dev<const int32_t>(o_iB);
   p.nnratio = nnratio; p.check_ori = check_orientation;
   p.sequential = sequential; p.n_pairs = (int)pairs.size();
-  p.kf_mode = kf_mode; p.validB = kf_mode ? d + o_vB : nullptr; p.matchA = (int32_t*)(d + o_mA);
-  p.matchB = (int32_t*)(d + o_mB); p.counters = (int32_t*)(d + o_cnt);
-  p.push_idx = (int32_t*)(d + o_pi); p.push_bin = d + o_pb;
-  orbfe_launch_bow(p, (int)pairs.size(), maxB, s);
-  if ((rc = launch_ok())) return rc;
-  int32_t cnt[2] = {0, 0};
-  HIPCHK(hipMemcpyAsync(matchB, d + o_mB, (size_t)nB * 4, hipMemcpyDeviceToHost, s));
-  if (kf_mode) HIPCHK(hipMemcpyAsync(matchA_out, d + o_mA, (size_t)nA * 4, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipMemcpyAsync(cnt, d + o_cnt, 8, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
-  *n_matches = cnt[1];
+  p.kf_mode = kf_mode; p.validB = kf_mode ? c.dev(o_vB) : nullptr; p.matchA = kf_mode ? c.dev<int32_t>(o_mA) : nullptr;
+  p.matchB = c.dev<int32_t>(o_mB); p.counters = c.dev<int32_t>(o_cnt);
+  p.push_idx = c.dev<int32_t>(o_pi); p.push_bin = c.dev(o_pb);
+  orbfe_launch_bow(p, (int)pairs.size(), maxB, c.stream);
+  if ((rc = c.finish(c.out_bytes()))) return rc;
+  memcpy(matchB, c.host(o_mB), (size_t)nB * 4);
+  if (kf_mode) memcpy(matchA_out, c.host(o_mA), (size_t)nA * 4);
+  *n_matches = c.host<const int32_t>(o_cnt)[1];
   return ORBFE_OK;
 }
 
@@ -665,31 +631,26 @@ extern "C" int orbfe_proj_best(const orbfe_frame_view* f, const orbfe_query* q, 
     return ORBFE_ERR_INVALID;
   for (int i = 0; i < nq; i++) { best_idx[i] = -1; best_dist[i] = 256; }
   if (nq == 0 || f->n == 0) return ORBFE_OK;
-  orbfe_matcher* m;
+  HostCall c("orbfe_proj_best");
+  const FrameRegions fr = frame_regions(c, f, true);
+  const size_t o_q = c.in(sizeof(orbfe_query) * (size_t)nq), o_inv = c.in(sizeof(float) * ORBFE_MAX_LEVELS);
+  const size_t o_bi = c.out(sizeof(int32_t) * (size_t)nq), o_bd = c.out(sizeof(int32_t) * (size_t)nq);
   int rc;
-  if ((rc = tls_matcher(&m))) return rc;
-  std::lock_guard<std::mutex> lk(m->mu);
-  HIPCHK(hipSetDevice(m->device));
-  hipStream_t s = m->stream;
-  if ((rc = stage_host(m, f, q, nq, s))) return rc;
-  if ((rc = ensure_proj_scratch(m, 1, f->n, nq))) return rc;
-  if ((rc = mb_alloc(m->lp_cnt, 64))) return rc;
-  float inv16[ORBFE_MAX_LEVELS] = {0};
-  if (gate == ORBFE_GATE_FUSE_CHI2) {
-    memcpy(inv16, inv_level_sigma2, sizeof(float) * n_levels);
-    HIPCHK(hipMemcpyAsync(m->lp_cnt.p, inv16, sizeof(inv16), hipMemcpyHostToDevice, s));
-  }
+  if ((rc = c.open()) || (rc = ensure_proj_scratch(c.m, 1, fr.cap, nq))) return rc;
+  frame_fill(c, fr, f, nq);
+  memcpy(c.host(o_q), q, sizeof(orbfe_query) * (size_t)nq);
+  memset(c.host(o_inv), 0, sizeof(float) * ORBFE_MAX_LEVELS);
+  if (gate == ORBFE_GATE_FUSE_CHI2) memcpy(c.host(o_inv), inv_level_sigma2, sizeof(float) * n_levels);
+  if ((rc = c.upload())) return rc;
   FrameBatch fb;
-  fill_frame_batch(m, fb, (const orbfe_keypoint*)m->h_keys.p, (const uint8_t*)m->h_desc.p, (const int32_t*)m->h_n.p,
-                   f->u_right ? (const float*)m->h_ur.p : nullptr, f->n, f->min_x, f->max_x, f->min_y, f->max_y);
-  QueryBatch qb{(const orbfe_query*)m->h_q.p, (const int32_t*)m->h_nq.p, nq};
-  orbfe_launch_grid_build(fb, 1, s);
-  // results land in the (otherwise unused here) n_cand / push_idx scratch: nq ints each
-  orbfe_launch_proj_best(fb, qb, gate, (const float*)m->lp_cnt.p, (int32_t*)m->n_cand.p, (int32_t*)m->push_idx.p, 1, s);
-  if ((rc = launch_ok())) return rc;
-  HIPCHK(hipMemcpyAsync(best_idx, m->n_cand.p, sizeof(int32_t) * nq, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipMemcpyAsync(best_dist, m->push_idx.p, sizeof(int32_t) * nq, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
+  fill_frame_batch(c.m, fb, c.dev<const orbfe_keypoint>(fr.keys), c.dev(fr.desc), frame_n(c, fr), fr.has_ur ? c.dev<const float>(fr.ur) : nullptr,
+                   fr.cap, f->min_x, f->max_x, f->min_y, f->max_y);
+  QueryBatch qb{c.dev<const orbfe_query>(o_q), frame_nq(c, fr), nq};
+  orbfe_launch_grid_build(fb, 1, c.stream);
+  orbfe_launch_proj_best(fb, qb, gate, c.dev<const float>(o_inv), c.dev<int32_t>(o_bi), c.dev<int32_t>(o_bd), 1, c.stream);
+  if ((rc = c.finish(c.out_bytes()))) return rc;
+  memcpy(best_idx, c.host(o_bi), sizeof(int32_t) * (size_t)nq);
+  memcpy(best_dist, c.host(o_bd), sizeof(int32_t) * (size_t)nq);
   return ORBFE_OK;
 }
 
@@ -709,50 +670,49 @@ extern "C" int orbfe_kf_search(const orbfe_frame_view* f, const float* inv_level
     results[i].u = results[i].v = results[i].u_r = 0.f;
   }
   if (n_points == 0) return ORBFE_OK;
-  orbfe_matcher* m;
+  // one packed upload [frame | points | camera | 1 / sigma2], the prologue and the search, one packed download: the prologue's results
+  // (no later kernel writes them), then [best_idx | best_dist] of the independent searches or, for the sequential modes, the
+  // greedy resolver's [blocked | assigned | n_matches], which also go up
+  const int gate = mode == ORBFE_KF_FUSE ? ORBFE_GATE_FUSE_CHI2 : ORBFE_GATE_NONE;
+  const size_t b_res = sizeof(orbfe_kf_result) * (size_t)n_points, b_int = sizeof(int32_t) * (size_t)n_points;
+  HostCall c("orbfe_kf_search");
+  const FrameRegions fr = frame_regions(c, f, !seq && gate == ORBFE_GATE_FUSE_CHI2);
+  const int cap = fr.cap;
+  const size_t o_pts = c.in(sizeof(orbfe_kf_point) * (size_t)n_points), o_cam = c.in(sizeof(orbfe_kf_camera)),
+               o_inv = c.in(sizeof(float) * ORBFE_MAX_LEVELS);
+  const size_t o_res = c.out(b_res), o_bi = c.out(seq ? 0 : b_int), o_bd = c.out(seq ? 0 : b_int), o_blocked = c.out(seq ? (size_t)cap : 0),
+               o_assigned = c.out(seq ? sizeof(int32_t) * (size_t)cap : 0), o_nm = c.out(seq ? 16 : 0);
   int rc;
-  if ((rc = tls_matcher(&m))) return rc;
-  std::lock_guard<std::mutex> lk(m->mu);
-  HIPCHK(hipSetDevice(m->device));
-  hipStream_t s = m->stream;
-  if ((rc = mb_alloc(m->lp_pts, sizeof(orbfe_kf_point) * (size_t)n_points))) return rc;
-  if ((rc = mb_alloc(m->lp_track, sizeof(orbfe_kf_result) * (size_t)n_points))) return rc;
-  if ((rc = mb_alloc(m->lp_fr, sizeof(orbfe_kf_camera)))) return rc;
-  if ((rc = mb_alloc(m->lp_q, sizeof(orbfe_query) * (size_t)n_points))) return rc;
-  if ((rc = mb_alloc(m->lp_cnt, 64))) return rc;
-  HIPCHK(hipMemcpyAsync(m->lp_pts.p, points, sizeof(orbfe_kf_point) * (size_t)n_points, hipMemcpyHostToDevice, s));
-  HIPCHK(hipMemcpyAsync(m->lp_fr.p, cam, sizeof(orbfe_kf_camera), hipMemcpyHostToDevice, s));
-  if ((rc = stage_host(m, f, nullptr, 0, s))) return rc;
-  const int32_t np = n_points;
-  HIPCHK(hipMemcpyAsync(m->h_nq.p, &np, 4, hipMemcpyHostToDevice, s));
-  orbfe_launch_kf_queries((const orbfe_kf_camera*)m->lp_fr.p, (const orbfe_kf_point*)m->lp_pts.p, n_points, mode,
-                          (orbfe_query*)m->lp_q.p, (orbfe_kf_result*)m->lp_track.p, s);
-  HIPCHK(hipMemcpyAsync(results, m->lp_track.p, sizeof(orbfe_kf_result) * (size_t)n_points, hipMemcpyDeviceToHost, s));
-  if (f->n == 0) {
-    HIPCHK(hipStreamSynchronize(s));
-    return launch_ok();
+  if ((rc = c.open()) || (rc = mb_alloc(c.m->lp_q, sizeof(orbfe_query) * (size_t)n_points))) return rc;
+  frame_fill(c, fr, f, n_points);
+  memcpy(c.host(o_pts), points, sizeof(orbfe_kf_point) * (size_t)n_points);
+  memcpy(c.host(o_cam), cam, sizeof(orbfe_kf_camera));
+  memset(c.host(o_inv), 0, sizeof(float) * ORBFE_MAX_LEVELS);
+  if (gate == ORBFE_GATE_FUSE_CHI2) memcpy(c.host(o_inv), inv_level_sigma2, sizeof(float) * cam->n_levels);
+  if (seq && f->n > 0) {
+    memcpy(c.host(o_blocked), blocked, (size_t)cap);
+    std::fill_n(c.host<int32_t>(o_assigned), cap, -2);
   }
-  const int cap = f->n;
+  if ((rc = c.upload(seq))) return rc;
+  const orbfe_query* d_q = (const orbfe_query*)c.m->lp_q.p;
+  orbfe_launch_kf_queries(c.dev<const orbfe_kf_camera>(o_cam), c.dev<const orbfe_kf_point>(o_pts), n_points, mode, (orbfe_query*)c.m->lp_q.p,
+                          c.dev<orbfe_kf_result>(o_res), c.stream);
+  if (f->n == 0) {
+    if ((rc = c.finish(b_res))) return rc;
+    memcpy(results, c.host(o_res), b_res);
+    return ORBFE_OK;
+  }
   if (!seq) {
-    if ((rc = ensure_proj_scratch(m, 1, cap, n_points))) return rc;
-    float inv16[ORBFE_MAX_LEVELS] = {0};
-    const int gate = mode == ORBFE_KF_FUSE ? ORBFE_GATE_FUSE_CHI2 : ORBFE_GATE_NONE;
-    if (gate == ORBFE_GATE_FUSE_CHI2) {
-      memcpy(inv16, inv_level_sigma2, sizeof(float) * cam->n_levels);
-      HIPCHK(hipMemcpyAsync(m->lp_cnt.p, inv16, sizeof(inv16), hipMemcpyHostToDevice, s));
-    }
+    if ((rc = ensure_proj_scratch(c.m, 1, cap, n_points))) return rc;
     FrameBatch fb;
-    fill_frame_batch(m, fb, (const orbfe_keypoint*)m->h_keys.p, (const uint8_t*)m->h_desc.p, (const int32_t*)m->h_n.p,
-                     (f->u_right && gate == ORBFE_GATE_FUSE_CHI2) ? (const float*)m->h_ur.p : nullptr, cap, f->min_x, f->max_x,
-                     f->min_y, f->max_y);
-    QueryBatch qb{(const orbfe_query*)m->lp_q.p, (const int32_t*)m->h_nq.p, n_points};
-    orbfe_launch_grid_build(fb, 1, s);
-    orbfe_launch_proj_best(fb, qb, gate, (const float*)m->lp_cnt.p, (int32_t*)m->n_cand.p, (int32_t*)m->push_idx.p, 1, s);
-    if ((rc = launch_ok())) return rc;
-    std::vector<int32_t> bi((size_t)n_points), bd((size_t)n_points);
-    HIPCHK(hipMemcpyAsync(bi.data(), m->n_cand.p, sizeof(int32_t) * n_points, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(bd.data(), m->push_idx.p, sizeof(int32_t) * n_points, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
+    fill_frame_batch(c.m, fb, c.dev<const orbfe_keypoint>(fr.keys), c.dev(fr.desc), frame_n(c, fr), fr.has_ur ? c.dev<const float>(fr.ur) : nullptr,
+                     cap, f->min_x, f->max_x, f->min_y, f->max_y);
+    QueryBatch qb{d_q, frame_nq(c, fr), n_points};
+    orbfe_launch_grid_build(fb, 1, c.stream);
+    orbfe_launch_proj_best(fb, qb, gate, c.dev<const float>(o_inv), c.dev<int32_t>(o_bi), c.dev<int32_t>(o_bd), 1, c.stream);
+    if ((rc = c.finish(c.out_bytes()))) return rc;
+    memcpy(results, c.host(o_res), b_res);
+    const int32_t *bi = c.host<const int32_t>(o_bi), *bd = c.host<const int32_t>(o_bd);
     int cnt = 0;
     for (int i = 0; i < n_points; i++) {
       results[i].best_idx = bi[i];
@@ -763,22 +723,16 @@ extern "C" int orbfe_kf_search(const orbfe_frame_view* f, const float* inv_level
     return ORBFE_OK;
   }
   // sequential modes: the greedy resolver of SearchByProjection(cur, last) with the caller's distance bound, no stereo gate
-  std::vector<int32_t> assigned((size_t)cap, -2);
-  HIPCHK(hipMemcpyAsync(m->h_blocked.p, blocked, cap, hipMemcpyHostToDevice, s));
-  HIPCHK(hipMemcpyAsync(m->h_assigned.p, assigned.data(), sizeof(int32_t) * cap, hipMemcpyHostToDevice, s));
-  rc = proj_enqueue(m, 1, (const orbfe_keypoint*)m->h_keys.p, (const uint8_t*)m->h_desc.p, (const int32_t*)m->h_n.p, nullptr, cap,
-                    f->min_x, f->max_x, f->min_y, f->max_y, (const orbfe_query*)m->lp_q.p, (const int32_t*)m->h_nq.p, n_points, 1,
-                    0.f, mode == ORBFE_KF_RELOC ? check_orientation : 0, (uint8_t*)m->h_blocked.p, (int32_t*)m->h_assigned.p,
-                    (int32_t*)m->h_nm.p, true, s, max_dist);
-  if (rc) return rc;
-  int32_t nm = 0;
-  HIPCHK(hipMemcpyAsync(blocked, m->h_blocked.p, cap, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipMemcpyAsync(assigned.data(), m->h_assigned.p, sizeof(int32_t) * cap, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipMemcpyAsync(&nm, m->h_nm.p, 4, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
+  rc = proj_enqueue(c.m, 1, c.dev<const orbfe_keypoint>(fr.keys), c.dev(fr.desc), frame_n(c, fr), nullptr, cap, f->min_x, f->max_x, f->min_y,
+                    f->max_y, d_q, frame_nq(c, fr), n_points, 1, 0.f, mode == ORBFE_KF_RELOC ? check_orientation : 0, c.dev(o_blocked),
+                    c.dev<int32_t>(o_assigned), c.dev<int32_t>(o_nm), true, c.stream, max_dist);
+  if (rc || (rc = c.finish(c.out_bytes()))) return rc;
+  memcpy(results, c.host(o_res), b_res);
+  memcpy(blocked, c.host(o_blocked), (size_t)cap);
+  const int32_t* assigned = c.host<const int32_t>(o_assigned);
   for (int j = 0; j < cap; j++)
     if (assigned[j] >= 0 && assigned[j] < n_points) results[assigned[j]].best_idx = j;
-  *n_matches = nm;
+  *n_matches = *c.host<const int32_t>(o_nm);
   return ORBFE_OK;
 }
 
@@ -831,23 +785,7 @@ int orbfe_tri_search_enqueue(const TriSearchBuffers& b, const orbfe_epipolar* ep
   t.stereoA = b.stereoA; t.stereoB = b.stereoB;
   t.ep = *ep;
   orbfe_launch_triangulation(t, b.n_pairs, s);
-  return launch_ok();
-}
-
-// The calling thread's handle for another translation unit (mapping.cpp): its stream, and a device block with a pinned host mirror of
-// at least `bytes` each.  lk holds the handle until the caller lets go of it.
-int orbfe_internal_thread_block(size_t bytes, std::unique_lock<std::mutex>& lk, hipStream_t* s, uint8_t** dev, uint8_t** pinned) {
-  orbfe_matcher* m;
-  int rc;
-  if ((rc = tls_matcher(&m))) return rc;
-  lk = std::unique_lock<std::mutex>(m->mu);
-  HIPCHK(hipSetDevice(m->device));
-  if ((rc = mb_alloc(m->st_in, bytes))) return rc;
-  if ((rc = pin_alloc(m->h_pin, m->h_pin_bytes, bytes))) return rc;
-  *s = m->stream;
-  *dev = (uint8_t*)m->st_in.p;
-  *pinned = (uint8_t*)m->h_pin;
-  return ORBFE_OK;
+  return hip_status("kernel launch failed", hipGetLastError());
 }
 
 // SearchForTriangulation (L/src/ORBmatcher.cc:614-764), host pointers, synchronous
@@ -869,51 +807,41 @@ extern "C" int orbfe_search_for_triangulation(const orbfe_keypoint* keysA, const
   const std::vector<BowPair>& pairs = plan.pairs;
   const int totA = plan.totA, totB = plan.totB;
   if (pairs.empty()) return ORBFE_OK;
+  // one packed upload [pairs | descA | descB | keysA | keysB | idxA | idxB | validA | validB | stereoA | stereoB | scratch | matchA | counters]
+  // (matchA goes up filled with -1, the counters zero), one packed download of [matchA | counters]
+  const size_t b_pairs = pairs.size() * sizeof(BowPair), push_n = (size_t)std::max(totA, nA);
+  HostCall c("orbfe_search_for_triangulation");
+  const size_t o_pairs = c.in(b_pairs), o_dA = c.in((size_t)nA * 32), o_dB = c.in((size_t)nB * 32), o_kA = c.in((size_t)nA * sizeof(orbfe_keypoint)),
+               o_kB = c.in((size_t)nB * sizeof(orbfe_keypoint)), o_iA = c.in((size_t)totA * 4), o_iB = c.in((size_t)totB * 4),
+               o_vA = c.in((size_t)nA), o_vB = c.in((size_t)nB), o_sA = c.in((size_t)nA), o_sB = c.in((size_t)nB);
+  const size_t o_pi = c.scratch(push_n * 4), o_pb = c.scratch(push_n);
+  const size_t o_mA = c.out((size_t)nA * 4), o_cnt = c.out(256);
+  if ((rc = c.open())) return rc;
+  memcpy(c.host(o_pairs), pairs.data(), b_pairs);
+  memcpy(c.host(o_dA), descA, (size_t)nA * 32);
+  memcpy(c.host(o_dB), descB, (size_t)nB * 32);
+  memcpy(c.host(o_kA), keysA, (size_t)nA * sizeof(orbfe_keypoint));
+  memcpy(c.host(o_kB), keysB, (size_t)nB * sizeof(orbfe_keypoint));
+  memcpy(c.host(o_iA), idxA, (size_t)totA * 4);
+  memcpy(c.host(o_iB), idxB, (size_t)totB * 4);
   // candidate masks and stereo flags (:655-664, 677-686)
-  std::vector<uint8_t> vA((size_t)nA), vB((size_t)nB), sA((size_t)nA), sB((size_t)nB);
+  uint8_t *vA = c.host(o_vA), *vB = c.host(o_vB), *sA = c.host(o_sA), *sB = c.host(o_sB);
   for (int i = 0; i < nA; i++) { sA[i] = u_rightA && u_rightA[i] >= 0; vA[i] = !has_mpA[i] && (!only_stereo || sA[i]); }
   for (int i = 0; i < nB; i++) { sB[i] = u_rightB && u_rightB[i] >= 0; vB[i] = !has_mpB[i] && (!only_stereo || sB[i]); }
-  orbfe_matcher* m;
-  if ((rc = tls_matcher(&m))) return rc;
-  std::lock_guard<std::mutex> lk(m->mu);
-  HIPCHK(hipSetDevice(m->device));
-  hipStream_t s = m->stream;
-  auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-  const size_t o_pairs = 0, o_dA = al(pairs.size() * sizeof(BowPair)), o_dB = o_dA + al((size_t)nA * 32),
-               o_kA = o_dB + al((size_t)nB * 32), o_kB = o_kA + al((size_t)nA * sizeof(orbfe_keypoint)),
-               o_iA = o_kB + al((size_t)nB * sizeof(orbfe_keypoint)), o_iB = o_iA + al((size_t)totA * 4),
-               o_vA = o_iB + al((size_t)totB * 4), o_vB = o_vA + al((size_t)nA), o_sA = o_vB + al((size_t)nB),
-               o_sB = o_sA + al((size_t)nA), o_mA = o_sB + al((size_t)nB), o_cnt = o_mA + al((size_t)nA * 4), o_pi = o_cnt + 256,
-               o_pb = o_pi + al((size_t)std::max(totA, nA) * 4), total = o_pb + al((size_t)std::max(totA, nA));
-  if ((rc = mb_alloc(m->h_q, total))) return rc;
-  uint8_t* d = (uint8_t*)m->h_q.p;
-  HIPCHK(hipMemcpyAsync(d + o_pairs, pairs.data(), pairs.size() * sizeof(BowPair), hipMemcpyHostToDevice, s));
-  HIPCHK(hipMemcpyAsync(d + o_dA, descA, (size_t)nA * 32, hipMemcpyHostToDevice, s));
-  HIPCHK(hipMemcpyAsync(d + o_dB, descB, (size_t)nB * 32, hipMemcpyHostToDevice, s));
-  HIPCHK(hipMemcpyAsync(d + o_kA, keysA, (size_t)nA * sizeof(orbfe_keypoint), hipMemcpyHostToDevice, s));
-  HIPCHK(hipMemcpyAsync(d + o_kB, keysB, (size_t)nB * sizeof(orbfe_keypoint), hipMemcpyHostToDevice, s));
-  HIPCHK(hipMemcpyAsync(d + o_iA, idxA, (size_t)totA * 4, hipMemcpyHostToDevice, s));
-  HIPCHK(hipMemcpyAsync(d + o_iB, idxB, (size_t)totB * 4, hipMemcpyHostToDevice, s));
-  HIPCHK(hipMemcpyAsync(d + o_vA, vA.data(), (size_t)nA, hipMemcpyHostToDevice, s));
-  HIPCHK(hipMemcpyAsync(d + o_vB, vB.data(), (size_t)nB, hipMemcpyHostToDevice, s));
-  HIPCHK(hipMemcpyAsync(d + o_sA, sA.data(), (size_t)nA, hipMemcpyHostToDevice, s));
-  HIPCHK(hipMemcpyAsync(d + o_sB, sB.data(), (size_t)nB, hipMemcpyHostToDevice, s));
-  HIPCHK(hipMemsetAsync(d + o_mA, 0xff, (size_t)nA * 4, s));
-  HIPCHK(hipMemsetAsync(d + o_cnt, 0, 256, s));
+  memset(c.host(o_mA), 0xff, (size_t)nA * 4);
+  memset(c.host(o_cnt), 0, 256);
+  if ((rc = c.upload(true))) return rc;
   TriSearchBuffers b;
-  b.pairs = (const BowPair*)(d + o_pairs); b.n_pairs = (int)pairs.size();
-  b.descA = d + o_dA; b.descB = d + o_dB;
-  b.keysA = (const orbfe_keypoint*)(d + o_kA); b.keysB = (const orbfe_keypoint*)(d + o_kB);
-  b.idxA = (const int32_t*)(d + o_iA); b.idxB = (const int32_t*)(d + o_iB);
-  b.validA = d + o_vA; b.validB = d + o_vB; b.stereoA = d + o_sA; b.stereoB = d + o_sB;
-  b.matchA = (int32_t*)(d + o_mA); b.counters = (int32_t*)(d + o_cnt);
-  b.push_idx = (int32_t*)(d + o_pi); b.push_bin = d + o_pb;
-  if ((rc = orbfe_tri_search_enqueue(b, ep, check_orientation, plan.sequential, s))) return rc;
-  int32_t cnt[2] = {0, 0};
-  HIPCHK(hipMemcpyAsync(matchA, d + o_mA, (size_t)nA * 4, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipMemcpyAsync(cnt, d + o_cnt, 8, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
-  *n_matches = cnt[1];
+  b.pairs = c.dev<const BowPair>(o_pairs); b.n_pairs = (int)pairs.size();
+  b.descA = c.dev(o_dA); b.descB = c.dev(o_dB);
+  b.keysA = c.dev<const orbfe_keypoint>(o_kA); b.keysB = c.dev<const orbfe_keypoint>(o_kB);
+  b.idxA = c.dev<const int32_t>(o_iA); b.idxB = c.dev<const int32_t>(o_iB);
+  b.validA = c.dev(o_vA); b.validB = c.dev(o_vB); b.stereoA = c.dev(o_sA); b.stereoB = c.dev(o_sB);
+  b.matchA = c.dev<int32_t>(o_mA); b.counters = c.dev<int32_t>(o_cnt);
+  b.push_idx = c.dev<int32_t>(o_pi); b.push_bin = c.dev(o_pb);
+  if ((rc = orbfe_tri_search_enqueue(b, ep, check_orientation, plan.sequential, c.stream)) || (rc = c.finish(c.out_bytes()))) return rc;
+  memcpy(matchA, c.host(o_mA), (size_t)nA * 4);
+  *n_matches = c.host<const int32_t>(o_cnt)[1];
   return ORBFE_OK;
 }
 
@@ -928,8 +856,21 @@ extern "C" int orbfe_search_for_initialization(const orbfe_frame_view* f1, const
   const int n1 = f1->n;
   for (int i = 0; i < n1; i++) matches12[i] = -1;
   if (n1 == 0 || f2->n == 0) return ORBFE_OK;
+  // one packed upload [F2 | queries | vbPrevMatched], one packed download [vbPrevMatched | matches12 | n_matches]
+  HostCall c("orbfe_search_for_initialization");
+  const FrameRegions fr = frame_regions(c, f2, false);   // no stereo gate in this search
+  const int cap = f2->n;
+  const size_t o_q = c.in(sizeof(orbfe_query) * (size_t)n1);
+  const size_t o_prev = c.out(sizeof(float) * 2 * (size_t)n1), o_m12 = c.out(sizeof(int32_t) * (size_t)n1), o_nm = c.out(16);
+  int rc;
+  if ((rc = c.open()) || (rc = ensure_proj_scratch(c.m, 1, cap, n1))) return rc;
+  if ((size_t)cap * 8 > 60 * 1024) {
+    orbfe_set_error("SearchForInitialization: frame with %d keypoints exceeds the LDS-resident tables", cap);
+    return ORBFE_ERR_INVALID;
+  }
+  frame_fill(c, fr, f2, n1);
   // one query per F1 keypoint: window around vbPrevMatched[i1], level filter (level1, level1) (:403-410)
-  std::vector<orbfe_query> q((size_t)n1);
+  orbfe_query* q = c.host<orbfe_query>(o_q);
   for (int i = 0; i < n1; i++) {
     orbfe_query& e = q[i];
     memset(&e, 0, sizeof(e));
@@ -944,40 +885,21 @@ extern "C" int orbfe_search_for_initialization(const orbfe_frame_view* f1, const
     e.angle = f1->keys_un[i].angle;
     memcpy(e.desc, f1->desc + (size_t)i * 32, 32);
   }
-  orbfe_matcher* m;
-  int rc;
-  if ((rc = tls_matcher(&m))) return rc;
-  std::lock_guard<std::mutex> lk(m->mu);
-  HIPCHK(hipSetDevice(m->device));
-  hipStream_t s = m->stream;
-  orbfe_frame_view f2n = *f2;
-  f2n.u_right = nullptr;  // no stereo gate in this search
-  if ((rc = stage_host(m, &f2n, q.data(), n1, s))) return rc;
-  const int cap = f2->n;
-  if ((rc = ensure_proj_scratch(m, 1, cap, n1))) return rc;
-  if ((rc = mb_alloc(m->h_assigned, sizeof(int32_t) * (size_t)std::max(n1, cap)))) return rc;
-  if ((rc = mb_alloc(m->h_ur, sizeof(float) * 2 * (size_t)std::max(n1, cap)))) return rc;  // prev_matched staging
-  if ((size_t)cap * 8 > 60 * 1024) {
-    orbfe_set_error("SearchForInitialization: frame with %d keypoints exceeds the LDS-resident tables", cap);
-    return ORBFE_ERR_INVALID;
-  }
-  HIPCHK(hipMemcpyAsync(m->h_ur.p, prev_matched_xy, sizeof(float) * 2 * n1, hipMemcpyHostToDevice, s));
+  memcpy(c.host(o_prev), prev_matched_xy, sizeof(float) * 2 * (size_t)n1);
+  if ((rc = c.upload(true))) return rc;
   FrameBatch fb;
-  fill_frame_batch(m, fb, (const orbfe_keypoint*)m->h_keys.p, (const uint8_t*)m->h_desc.p, (const int32_t*)m->h_n.p, nullptr,
-                   cap, f2->min_x, f2->max_x, f2->min_y, f2->max_y);
-  QueryBatch qb{(const orbfe_query*)m->h_q.p, (const int32_t*)m->h_nq.p, n1};
-  orbfe_launch_grid_build(fb, 1, s);
-  orbfe_launch_proj_candidates(fb, qb, (orbfe_cand*)m->cand.p, (int32_t*)m->n_cand.p, ORBFE_MAX_CAND, 1, s);
-  orbfe_launch_init_resolve(fb, qb, (const orbfe_cand*)m->cand.p, (const int32_t*)m->n_cand.p, ORBFE_MAX_CAND, nnratio,
-                            check_orientation, (int32_t*)m->h_assigned.p, (float*)m->h_ur.p, (int32_t*)m->h_nm.p,
-                            (int32_t*)m->push_idx.p, (uint8_t*)m->push_bin.p, s);
-  if ((rc = launch_ok())) return rc;
-  int32_t nm = 0;
-  HIPCHK(hipMemcpyAsync(matches12, m->h_assigned.p, sizeof(int32_t) * n1, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipMemcpyAsync(prev_matched_xy, m->h_ur.p, sizeof(float) * 2 * n1, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipMemcpyAsync(&nm, m->h_nm.p, 4, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
-  *n_matches = nm;
+  fill_frame_batch(c.m, fb, c.dev<const orbfe_keypoint>(fr.keys), c.dev(fr.desc), frame_n(c, fr), nullptr, cap, f2->min_x, f2->max_x, f2->min_y,
+                   f2->max_y);
+  QueryBatch qb{c.dev<const orbfe_query>(o_q), frame_nq(c, fr), n1};
+  orbfe_launch_grid_build(fb, 1, c.stream);
+  orbfe_launch_proj_candidates(fb, qb, (orbfe_cand*)c.m->cand.p, (int32_t*)c.m->n_cand.p, ORBFE_MAX_CAND, 1, c.stream);
+  orbfe_launch_init_resolve(fb, qb, (const orbfe_cand*)c.m->cand.p, (const int32_t*)c.m->n_cand.p, ORBFE_MAX_CAND, nnratio, check_orientation,
+                            c.dev<int32_t>(o_m12), c.dev<float>(o_prev), c.dev<int32_t>(o_nm), (int32_t*)c.m->push_idx.p,
+                            (uint8_t*)c.m->push_bin.p, c.stream);
+  if ((rc = c.finish(c.out_bytes()))) return rc;
+  memcpy(matches12, c.host(o_m12), sizeof(int32_t) * (size_t)n1);
+  memcpy(prev_matched_xy, c.host(o_prev), sizeof(float) * 2 * (size_t)n1);
+  *n_matches = *c.host<const int32_t>(o_nm);
   return ORBFE_OK;
 }
 
@@ -1034,7 +956,7 @@ static int stereo_enqueue(orbfe_matcher* m, orbfe_extractor* left, orbfe_extract
   p.sad = (int32_t*)m->sad.p;
   p.n_matched = d_n_matched;
   orbfe_launch_stereo(p, n_pairs, stream);
-  return launch_ok();
+  return hip_status("kernel launch failed", hipGetLastError());
 }
 
 extern "C" int orbfe_stereo_match_device(orbfe_matcher* m, orbfe_extractor* left, orbfe_extractor* right, int n_pairs,
@@ -1067,38 +989,27 @@ extern "C" int orbfe_stereo_match(orbfe_extractor* left, orbfe_extractor* right,
   if (n_matched) *n_matched = 0;
   for (int i = 0; i < n_l; i++) u_right[i] = depth[i] = -1.0f;   // L/src/Frame.cc:478-479
   if (n_l == 0 || n_r == 0) return ORBFE_OK;
-  orbfe_matcher* m;
-  int rc;
-  if ((rc = tls_matcher(&m))) return rc;
-  std::lock_guard<std::mutex> lk(m->mu);
-  HIPCHK(hipSetDevice(m->device));
-  hipStream_t s = m->stream;
-  const int cap = std::max(n_l, n_r);
+  const size_t cap = (size_t)std::max(n_l, n_r);
   // one packed upload [n_l, n_r | keys_l | keys_r | desc_l | desc_r], three kernels, one packed download [u_right | depth | n]
-  Layout L;
-  const size_t o_hdr = L.add(16), o_kl = L.add(sizeof(orbfe_keypoint) * (size_t)cap), o_kr = L.add(sizeof(orbfe_keypoint) * (size_t)cap);
-  const size_t o_dl = L.add((size_t)32 * cap), o_dr = L.add((size_t)32 * cap);
-  const size_t o_out = L.off;
-  const size_t o_ur = L.add(sizeof(float) * (size_t)cap), o_dp = L.add(sizeof(float) * (size_t)cap), o_nm = L.add(16);
-  if ((rc = pin_alloc(m->h_pin, m->h_pin_bytes, L.off)) || (rc = mb_alloc(m->st_in, L.off))) return rc;
-  uint8_t* h = (uint8_t*)m->h_pin;
-  uint8_t* d = (uint8_t*)m->st_in.p;
-  ((int32_t*)(h + o_hdr))[0] = n_l;
-  ((int32_t*)(h + o_hdr))[1] = n_r;
-  memcpy(h + o_kl, kps_l, sizeof(orbfe_keypoint) * (size_t)n_l);
-  memcpy(h + o_kr, kps_r, sizeof(orbfe_keypoint) * (size_t)n_r);
-  memcpy(h + o_dl, desc_l, (size_t)32 * n_l);
-  memcpy(h + o_dr, desc_r, (size_t)32 * n_r);
-  HIPCHK(packed_h2d(d, h, o_out, s));
-  rc = stereo_enqueue(m, left, right, 1, (const orbfe_keypoint*)(d + o_kl), d + o_dl, (const int32_t*)(d + o_hdr),
-                      (const orbfe_keypoint*)(d + o_kr), d + o_dr, (const int32_t*)(d + o_hdr) + 1, cap, mbf, mb, (float*)(d + o_ur),
-                      (float*)(d + o_dp), (int32_t*)(d + o_nm), s);
-  if (rc) { (void)hipStreamSynchronize(s); return rc; }
-  HIPCHK(packed_d2h(h + o_out, d + o_out, L.off - o_out, s));
-  HIPCHK(hipStreamSynchronize(s));
-  memcpy(u_right, h + o_ur, sizeof(float) * (size_t)n_l);
-  memcpy(depth, h + o_dp, sizeof(float) * (size_t)n_l);
-  const int32_t nm = *(const int32_t*)(h + o_nm);
-  if (n_matched) *n_matched = nm;
+  HostCall c("orbfe_stereo_match");
+  const size_t o_hdr = c.in(16), o_kl = c.in(sizeof(orbfe_keypoint) * cap), o_kr = c.in(sizeof(orbfe_keypoint) * cap), o_dl = c.in(32 * cap),
+               o_dr = c.in(32 * cap);
+  const size_t o_ur = c.out(sizeof(float) * cap), o_dp = c.out(sizeof(float) * cap), o_nm = c.out(16);
+  int rc;
+  if ((rc = c.open())) return rc;
+  c.host<int32_t>(o_hdr)[0] = n_l;
+  c.host<int32_t>(o_hdr)[1] = n_r;
+  memcpy(c.host(o_kl), kps_l, sizeof(orbfe_keypoint) * (size_t)n_l);
+  memcpy(c.host(o_kr), kps_r, sizeof(orbfe_keypoint) * (size_t)n_r);
+  memcpy(c.host(o_dl), desc_l, (size_t)32 * n_l);
+  memcpy(c.host(o_dr), desc_r, (size_t)32 * n_r);
+  if ((rc = c.upload())) return rc;
+  rc = stereo_enqueue(c.m, left, right, 1, c.dev<const orbfe_keypoint>(o_kl), c.dev(o_dl), c.dev<const int32_t>(o_hdr),
+                      c.dev<const orbfe_keypoint>(o_kr), c.dev(o_dr), c.dev<const int32_t>(o_hdr) + 1, (int)cap, mbf, mb, c.dev<float>(o_ur),
+                      c.dev<float>(o_dp), c.dev<int32_t>(o_nm), c.stream);
+  if (rc || (rc = c.finish(c.out_bytes(), HOST_COPY_KERNEL))) return rc;
+  memcpy(u_right, c.host(o_ur), sizeof(float) * (size_t)n_l);
+  memcpy(depth, c.host(o_dp), sizeof(float) * (size_t)n_l);
+  if (n_matched) *n_matched = *c.host<const int32_t>(o_nm);
   return ORBFE_OK;
 }

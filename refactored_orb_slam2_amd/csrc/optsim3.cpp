@@ -31,9 +31,7 @@ extern "C" int orbfe_optimize_sim3_batch_device(int P, const orbfe_sim3_view* d_
   L.view1 = d_view1; L.view2 = d_view2; L.pairs = d_pairs; L.n = d_n; L.cap = cap; L.s_R_t_in = d_s_R_t_in; L.th2 = d_th2;
   L.fix_scale = d_fix_scale; L.result = d_result; L.bad = d_bad;
   orbfe_launch_optimize_sim3(L, P, (hipStream_t)stream);
-  const hipError_t le = hipGetLastError();
-  if (le != hipSuccess) return hip_fail("optimize sim3 batch: kernel launch failed", le);
-  return ORBFE_OK;
+  return hip_status("optimize sim3 batch: kernel launch failed", hipGetLastError());
 }
 
 extern "C" int orbfe_optimize_sim3(const orbfe_sim3_view* view1, const orbfe_sim3_view* view2, const orbfe_optsim3_pair* pairs, int n,
@@ -58,19 +56,13 @@ extern "C" int orbfe_optimize_sim3(const orbfe_sim3_view* view1, const orbfe_sim
     memcpy(result->t, s_R_t_in + 10, sizeof(result->t));
     return ORBFE_OK;
   }
-  // ONE block: [input, uploaded | output, downloaded], the same offsets in device memory and in its pinned mirror
-  Layout Lo;
-  const size_t o_v1 = Lo.add(sizeof(orbfe_sim3_view)), o_v2 = Lo.add(sizeof(orbfe_sim3_view)), o_scal = Lo.add(64),
-               o_pairs = Lo.add((size_t)n * sizeof(orbfe_optsim3_pair));
-  const size_t in_end = Lo.off;
-  const size_t o_res = Lo.add(sizeof(orbfe_optsim3_result)), o_bad = Lo.add((size_t)n);
-  const size_t total = Lo.off;
-
-  std::unique_lock<std::mutex> lk;
-  hipStream_t s = nullptr;
-  uint8_t *d = nullptr, *h = nullptr;
+  HostCall c("optimize sim3");
+  const size_t o_v1 = c.in(sizeof(orbfe_sim3_view)), o_v2 = c.in(sizeof(orbfe_sim3_view)), o_scal = c.in(64),
+               o_pairs = c.in((size_t)n * sizeof(orbfe_optsim3_pair));
+  const size_t o_res = c.out(sizeof(orbfe_optsim3_result)), o_bad = c.out((size_t)n);
   int rc;
-  if ((rc = orbfe_internal_thread_block(total, lk, &s, &d, &h))) return rc;
+  if ((rc = c.open())) return rc;
+  uint8_t *const h = c.host(0), *const d = c.dev(0);
   memcpy(h + o_v1, view1, sizeof(orbfe_sim3_view));
   memcpy(h + o_v2, view2, sizeof(orbfe_sim3_view));
   // the scalars of the problem: 13 floats of the transform, th2, then n and fix_scale as int32
@@ -79,25 +71,15 @@ extern "C" int orbfe_optimize_sim3(const orbfe_sim3_view* view1, const orbfe_sim
   const int32_t scal[2] = {n, fix_scale != 0};
   memcpy(h + o_scal + 56, scal, sizeof(scal));
   memcpy(h + o_pairs, pairs, (size_t)n * sizeof(orbfe_optsim3_pair));
-  hipError_t e = hipMemcpyAsync(d, h, in_end, hipMemcpyHostToDevice, s);
-  if (e != hipSuccess) return hip_fail("optimize sim3: upload", e);
-  // from here on the stream may still read the pinned block: an error return drains it before the handle's lock is released
-  auto drained = [s](int code) {
-    (void)hipStreamSynchronize(s);
-    return code;
-  };
+  if ((rc = c.upload())) return rc;
   OsLaunch L;
   memset(&L, 0, sizeof(L));
   L.view1 = (const orbfe_sim3_view*)(d + o_v1); L.view2 = (const orbfe_sim3_view*)(d + o_v2);
   L.pairs = (const orbfe_optsim3_pair*)(d + o_pairs); L.n = (const int32_t*)(d + o_scal + 56); L.cap = n;
   L.s_R_t_in = (const float*)(d + o_scal); L.th2 = (const float*)(d + o_scal + 52); L.fix_scale = (const int32_t*)(d + o_scal + 60);
   L.result = (orbfe_optsim3_result*)(d + o_res); L.bad = d + o_bad;
-  orbfe_launch_optimize_sim3(L, 1, s);
-  e = hipGetLastError();
-  if (e != hipSuccess) return drained(hip_fail("optimize sim3: kernel launch failed", e));
-  e = hipMemcpyAsync(h + o_res, d + o_res, total - o_res, hipMemcpyDeviceToHost, s);
-  if (e == hipSuccess) e = hipStreamSynchronize(s);
-  if (e != hipSuccess) return drained(hip_fail("optimize sim3", e));
+  orbfe_launch_optimize_sim3(L, 1, c.stream);
+  if ((rc = c.finish(c.out_bytes()))) return rc;
   memcpy(result, h + o_res, sizeof(*result));
   memcpy(bad, h + o_bad, (size_t)n);
   return ORBFE_OK;

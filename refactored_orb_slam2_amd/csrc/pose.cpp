@@ -1,6 +1,8 @@
 // pose.cpp -- C ABI of Optimizer::PoseOptimization (include/orbfe.h: orbfe_pose_optimization*).  Both entry points validate and
 // launch pose_kernels.hip; the host form stages one frame through device memory around the same launch.  No CPU fallback: without
 // a device both are an error.
+#include <string.h>
+
 #include "host_internal.h"
 #include "pose_internal.h"
 
@@ -44,31 +46,8 @@ extern "C" int orbfe_pose_optimization_batch_device(int n_frames, const orbfe_ke
   if (n_frames == 0) return ORBFE_OK;
   orbfe_launch_pose_optimize(n_frames, d_keys_un, d_u_right, d_n, cap, d_assigned, (const uint8_t*)d_points, point_stride, d_n_points,
                              p_cap, frame_shift, d_camera, d_Tcw_in, d_result, d_outlier, flags, (hipStream_t)stream);
-  const hipError_t le = hipGetLastError();
-  if (le != hipSuccess) {
-    orbfe_set_error("kernel launch failed: %s", hipGetErrorString(le));
-    return ORBFE_ERR_HIP;
-  }
-  return ORBFE_OK;
+  return hip_status("kernel launch failed", hipGetLastError());
 }
-
-namespace {
-// one device allocation holding every array of the host form, released on every path
-struct Staging {
-  uint8_t* base = nullptr;
-  size_t used = 0;
-  ~Staging() {
-    if (base) (void)hipFree(base);
-  }
-  static size_t pad(size_t b) { return (b + 255) & ~(size_t)255; }
-  template <class T>
-  T* take(size_t bytes) {
-    T* p = reinterpret_cast<T*>(base + used);
-    used += pad(bytes);
-    return p;
-  }
-};
-}  // namespace
 
 extern "C" int orbfe_pose_optimization(const orbfe_frame_view* frame, const int32_t* assigned, const void* points, int point_stride,
                                        int n_points, const orbfe_pose_camera* camera, const float* Tcw_in, orbfe_pose_result* result,
@@ -93,46 +72,31 @@ extern "C" int orbfe_pose_optimization(const orbfe_frame_view* frame, const int3
   }
   if (!have_device()) return ORBFE_ERR_NO_DEVICE;
   const int cap = n > 0 ? n : 1, p_cap = n_points > 0 ? n_points : 1;
-  const size_t b_kps = (size_t)cap * sizeof(orbfe_keypoint), b_f = (size_t)cap * sizeof(float), b_pts = (size_t)p_cap * point_stride;
-  Staging st;
-  const size_t total = Staging::pad(b_kps) + 2 * Staging::pad(b_f) + Staging::pad(b_pts) + Staging::pad((size_t)cap) + 5 * 256;
-  hipError_t e = hipMalloc((void**)&st.base, total);
-  if (e != hipSuccess) {
-    st.base = nullptr;
-    orbfe_set_error("pose optimisation: device allocation of %zu bytes failed: %s", total, hipGetErrorString(e));
-    return ORBFE_ERR_HIP;
-  }
-  orbfe_keypoint* d_kps = st.take<orbfe_keypoint>(b_kps);
-  float* d_ur = st.take<float>(b_f);
-  int32_t* d_assigned = st.take<int32_t>(b_f);
-  uint8_t* d_pts = st.take<uint8_t>(b_pts);
-  uint8_t* d_out = st.take<uint8_t>((size_t)cap);
-  int32_t* d_n = st.take<int32_t>(4);
-  int32_t* d_np = st.take<int32_t>(4);
-  orbfe_pose_camera* d_cam = st.take<orbfe_pose_camera>(sizeof(orbfe_pose_camera));
-  float* d_T = st.take<float>(12 * sizeof(float));
-  orbfe_pose_result* d_res = st.take<orbfe_pose_result>(sizeof(orbfe_pose_result));
-  const int32_t hn = n, hnp = n_points;
+  // [input, uploaded | output, downloaded]; mvuRight has a region only when the frame has it, and reaches the kernel as NULL otherwise
+  HostCall c("pose optimisation");
+  const size_t o_hdr = c.in(16), o_cam = c.in(sizeof(orbfe_pose_camera)), o_T = c.in(12 * sizeof(float)),
+               o_kps = c.in((size_t)cap * sizeof(orbfe_keypoint)), o_ur = c.in(frame->u_right ? (size_t)cap * sizeof(float) : 0),
+               o_assigned = c.in((size_t)cap * sizeof(int32_t)), o_pts = c.in((size_t)p_cap * point_stride);
+  const size_t o_res = c.out(sizeof(orbfe_pose_result)), o_out = c.out((size_t)cap);
+  int rc;
+  if ((rc = c.open())) return rc;
+  c.host<int32_t>(o_hdr)[0] = n;
+  c.host<int32_t>(o_hdr)[1] = n_points;
+  memcpy(c.host(o_cam), camera, sizeof(orbfe_pose_camera));
+  memcpy(c.host(o_T), Tcw_in, 12 * sizeof(float));
   if (n > 0) {
-    e = hipMemcpy(d_kps, frame->keys_un, (size_t)n * sizeof(orbfe_keypoint), hipMemcpyHostToDevice);
-    if (e == hipSuccess && frame->u_right) e = hipMemcpy(d_ur, frame->u_right, (size_t)n * sizeof(float), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_assigned, assigned, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice);
+    memcpy(c.host(o_kps), frame->keys_un, (size_t)n * sizeof(orbfe_keypoint));
+    if (frame->u_right) memcpy(c.host(o_ur), frame->u_right, (size_t)n * sizeof(float));
+    memcpy(c.host(o_assigned), assigned, (size_t)n * sizeof(int32_t));
   }
-  if (e == hipSuccess && n_points > 0) e = hipMemcpy(d_pts, points, (size_t)n_points * point_stride, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(d_n, &hn, 4, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(d_np, &hnp, 4, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(d_cam, camera, sizeof(orbfe_pose_camera), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(d_T, Tcw_in, 12 * sizeof(float), hipMemcpyHostToDevice);
-  if (e == hipSuccess) {
-    orbfe_launch_pose_optimize(1, d_kps, frame->u_right ? d_ur : nullptr, d_n, cap, d_assigned, d_pts, point_stride, d_np, p_cap, 0, d_cam,
-                               d_T, d_res, d_out, 0, (hipStream_t) nullptr);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) e = hipMemcpy(result, d_res, sizeof(orbfe_pose_result), hipMemcpyDeviceToHost);   // waits for the kernel
-  if (e == hipSuccess && n > 0) e = hipMemcpy(outlier, d_out, (size_t)n, hipMemcpyDeviceToHost);
-  if (e != hipSuccess) {
-    orbfe_set_error("pose optimisation: %s", hipGetErrorString(e));
-    return ORBFE_ERR_HIP;
-  }
+  if (n_points > 0) memcpy(c.host(o_pts), points, (size_t)n_points * point_stride);
+  if ((rc = c.upload())) return rc;
+  orbfe_launch_pose_optimize(1, c.dev<const orbfe_keypoint>(o_kps), frame->u_right ? c.dev<const float>(o_ur) : nullptr, c.dev<const int32_t>(o_hdr),
+                             cap, c.dev<int32_t>(o_assigned), c.dev(o_pts), point_stride, c.dev<const int32_t>(o_hdr) + 1, p_cap, 0,
+                             c.dev<const orbfe_pose_camera>(o_cam), c.dev<const float>(o_T), c.dev<orbfe_pose_result>(o_res), c.dev(o_out), 0,
+                             c.stream);
+  if ((rc = c.finish(c.out_bytes()))) return rc;
+  memcpy(result, c.host(o_res), sizeof(orbfe_pose_result));
+  if (n > 0) memcpy(outlier, c.host(o_out), (size_t)n);
   return ORBFE_OK;
 }

@@ -59,9 +59,7 @@ extern "C" int orbfe_sim3_solve_batch_device(int P, const orbfe_sim3_view* d_vie
   L.hyps = d_hyps; L.words = d_words; L.result = d_result; L.mask = d_result_mask;
   orbfe_launch_sim3_hypotheses(L, P, (hipStream_t)stream);
   orbfe_launch_sim3_select(L, P, (hipStream_t)stream);
-  const hipError_t le = hipGetLastError();
-  if (le != hipSuccess) return hip_fail("sim3 batch: kernel launch failed", le);
-  return ORBFE_OK;
+  return hip_status("sim3 batch: kernel launch failed", hipGetLastError());
 }
 
 extern "C" int orbfe_sim3_solve(const orbfe_sim3_view* view1, const orbfe_sim3_view* view2, const orbfe_sim3_pair* pairs, int n,
@@ -96,35 +94,23 @@ extern "C" int orbfe_sim3_solve(const orbfe_sim3_view* view1, const orbfe_sim3_v
     if (words && H > 0) memset(words, 0, (size_t)H * n_words * 8);
     return ORBFE_OK;
   }
-  // ONE block: [input, uploaded | output, downloaded], the same offsets in device memory and in its pinned mirror; the optional
-  // outputs sit behind the result so that a caller who skips them also skips their bytes in the download
-  Layout Lo;
-  const size_t o_v1 = Lo.add(sizeof(orbfe_sim3_view)), o_v2 = Lo.add(sizeof(orbfe_sim3_view)), o_scal = Lo.add(16),
-               o_pairs = Lo.add((size_t)n * sizeof(orbfe_sim3_pair)), o_tri = Lo.add((size_t)H * 12);
-  const size_t in_end = Lo.off;
-  const size_t o_res = Lo.add(sizeof(orbfe_sim3_result)), o_mask = Lo.add(n_words * 8), o_words = Lo.add((size_t)H * n_words * 8),
-               o_hyps = Lo.add((size_t)H * sizeof(orbfe_sim3_hypothesis));
-  const size_t total = Lo.off;
-  const size_t out_end = hyps ? total : (words ? o_hyps : o_words);
-
-  std::unique_lock<std::mutex> lk;
-  hipStream_t s = nullptr;
-  uint8_t *d = nullptr, *h = nullptr;
+  // the optional outputs sit behind the result so that a caller who skips them also skips their bytes in the download
+  HostCall c("sim3 solve");
+  const size_t o_v1 = c.in(sizeof(orbfe_sim3_view)), o_v2 = c.in(sizeof(orbfe_sim3_view)), o_scal = c.in(16),
+               o_pairs = c.in((size_t)n * sizeof(orbfe_sim3_pair)), o_tri = c.in((size_t)H * 12);
+  const size_t o_res = c.out(sizeof(orbfe_sim3_result)), o_mask = c.out(n_words * 8), o_words = c.out((size_t)H * n_words * 8),
+               o_hyps = c.out((size_t)H * sizeof(orbfe_sim3_hypothesis));
+  const size_t out_end = hyps ? c.total() : (words ? o_hyps : o_words);
   int rc;
-  if ((rc = orbfe_internal_thread_block(total, lk, &s, &d, &h))) return rc;
+  if ((rc = c.open())) return rc;
+  uint8_t *const h = c.host(0), *const d = c.dev(0);
   memcpy(h + o_v1, view1, sizeof(orbfe_sim3_view));
   memcpy(h + o_v2, view2, sizeof(orbfe_sim3_view));
   const int32_t scal[4] = {n, H, fix_scale != 0, min_inliers};
   memcpy(h + o_scal, scal, sizeof(scal));
   memcpy(h + o_pairs, pairs, (size_t)n * sizeof(orbfe_sim3_pair));
   memcpy(h + o_tri, triples, (size_t)H * 12);
-  hipError_t e = hipMemcpyAsync(d, h, in_end, hipMemcpyHostToDevice, s);
-  if (e != hipSuccess) return hip_fail("sim3 solve: upload", e);
-  // from here on the stream may still read the pinned block: an error return drains it before the handle's lock is released
-  auto drained = [s](int code) {
-    (void)hipStreamSynchronize(s);
-    return code;
-  };
+  if ((rc = c.upload())) return rc;
   Sim3Launch L;
   memset(&L, 0, sizeof(L));
   const int32_t* d_scal = (const int32_t*)(d + o_scal);
@@ -133,13 +119,9 @@ extern "C" int orbfe_sim3_solve(const orbfe_sim3_view* view1, const orbfe_sim3_v
   L.triples = (const int32_t*)(d + o_tri); L.H = d_scal + 1; L.h_cap = H; L.fix_scale = d_scal + 2; L.min_inliers = d_scal + 3;
   L.hyps = (orbfe_sim3_hypothesis*)(d + o_hyps); L.words = (uint64_t*)(d + o_words);
   L.result = (orbfe_sim3_result*)(d + o_res); L.mask = (uint64_t*)(d + o_mask);
-  orbfe_launch_sim3_hypotheses(L, 1, s);
-  orbfe_launch_sim3_select(L, 1, s);
-  e = hipGetLastError();
-  if (e != hipSuccess) return drained(hip_fail("sim3 solve: kernel launch failed", e));
-  e = hipMemcpyAsync(h + o_res, d + o_res, out_end - o_res, hipMemcpyDeviceToHost, s);
-  if (e == hipSuccess) e = hipStreamSynchronize(s);
-  if (e != hipSuccess) return drained(hip_fail("sim3 solve", e));
+  orbfe_launch_sim3_hypotheses(L, 1, c.stream);
+  orbfe_launch_sim3_select(L, 1, c.stream);
+  if ((rc = c.finish(out_end - o_res))) return rc;
   memcpy(result, h + o_res, sizeof(*result));
   memcpy(result_mask, h + o_mask, n_words * 8);
   if (words) memcpy(words, h + o_words, (size_t)H * n_words * 8);

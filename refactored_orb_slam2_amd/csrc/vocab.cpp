@@ -12,18 +12,8 @@
 #include <mutex>
 #include <vector>
 
+#include "host_internal.h"
 #include "vocab_internal.h"
-
-void orbfe_set_error(const char* fmt, ...);
-
-#define HIPCHK(expr)                                                                              \
-  do {                                                                                            \
-    hipError_t _e = (expr);                                                                       \
-    if (_e != hipSuccess) {                                                                       \
-      orbfe_set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
-      return ORBFE_ERR_HIP;                                                                       \
-    }                                                                                             \
-  } while (0)
 
 struct orbfe_vocabulary {
   int device = 0;

@@ -14,6 +14,8 @@ Host times are host clocks around the synchronous calls; the ctypes arguments ar
 records are checked against the K searches + triangulations of the first neighbour before anything is timed.
 profiles/create_new_map_points.md.
 
+A/B builds: ORBFE_AB_LIB=<name> (refactored_orb_slam2_amd/csrc/_ab/liborbfe_<name>.so).
+
 usage: python tools/mapping_rate.py [--keypoints 2000] [--neighbors 10] [--reps 40] [--warmup 5]
 """
 from __future__ import annotations
@@ -28,7 +30,9 @@ import time
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from refactored_orb_slam2_amd import _lib, mapping  # noqa: E402
+from refactored_orb_slam2_amd import _lib  # noqa: E402
+if os.environ.get("ORBFE_AB_LIB"): _lib.LIB_PATH = os.path.join(_lib.CSRC, "_ab", "liborbfe_%s.so" % os.environ["ORBFE_AB_LIB"])
+from refactored_orb_slam2_amd import mapping  # noqa: E402
 from refactored_orb_slam2_amd.matcher import featvec_arrays  # noqa: E402
 
 
