@@ -796,12 +796,25 @@ def ref_search_for_initialization(keys1, desc1, F2, prev_matched, window, nnrati
     return nmatches, vnMatches12, prev
 
 
-def ref_compute_stereo_matches(keysL, descL, keysR, descR, pyrL, pyrR, scale_factors, inv_scale_factors, mbf, mb):
-    """Frame::ComputeStereoMatches (L/src/Frame.cc:477-646), second reading (per-row Python lists, numpy windows).  pyrL / pyrR:
-    lists of the level images of the two extractors' mvImagePyramid.  Returns (mvuRight, mvDepth) as float32 arrays.  Where the
-    reference would index out of range (rows outside the image, windows leaving a level) the keypoint gets no match."""
+# the ways a left keypoint leaves Frame::ComputeStereoMatches, in the order the walk below meets them
+(SX_OUTSIDE, SX_ROW_EMPTY, SX_NO_CANDIDATE, SX_HAMMING, SX_LEFT_WINDOW, SX_RIGHT_SPAN, SX_RIGHT_WINDOW, SX_END_SHIFT, SX_DELTA,
+ SX_DISPARITY, SX_CLAMPED, SX_MATCHED, SX_MEDIAN) = range(13)
+
+
+def stereo_walk(keysL, descL, keysR, descR, pyrL, pyrR, scale_factors, inv_scale_factors, mbf, mb):
+    """The one body of the second reading of Frame::ComputeStereoMatches (L/src/Frame.cc:477-646).  Returns (mvuRight, mvDepth,
+    exits, facts): `exits` holds one SX_* code per left keypoint (SX_MEDIAN replaces SX_MATCHED / SX_CLAMPED where the median rule
+    removed the match), `facts` what the walk saw on its way (tests/np_stereo.py names the entries).  ref_compute_stereo_matches
+    keeps the first two; tests/np_stereo.stereo_exits hands out all four."""
     N = len(keysL)
     mvuRight = np.full(N, -1.0, np.float32); mvDepth = np.full(N, -1.0, np.float32)
+    exits = np.full(N, SX_OUTSIDE, np.int32)
+    facts = dict(run=np.zeros(N, np.int32), hamming_ties=np.zeros(N, np.int32), hamming_ties_dx=np.zeros(N, bool),
+                 best_dist=np.full(N, -1, np.int32), best_idx=np.full(N, -1, np.int32), sad_ties=np.zeros(N, np.int32),
+                 sad=np.full(N, -1, np.int32), best_inc=np.zeros(N, np.int32), delta=np.full(N, np.nan, np.float32),
+                 touches=np.zeros(N, bool), at_min_u=np.zeros(N, np.int32), at_max_u=np.zeros(N, np.int32),
+                 clamped=np.zeros(N, bool), clipped_top=np.zeros(len(keysR), bool), clipped_bottom=np.zeros(len(keysR), bool),
+                 median_in=[], median=None)
     thOrbDist = (TH_HIGH + TH_LOW) // 2
     nRows = pyrL[0].shape[0]
     vRowIndices = [[] for _ in range(nRows)]
@@ -809,6 +822,7 @@ def ref_compute_stereo_matches(keysL, descL, keysR, descR, pyrL, pyrR, scale_fac
         kpY = _f32(keysR["y"][iR])
         r = _f32(2.0) * _f32(scale_factors[int(keysR["octave"][iR])])
         maxr = int(math.ceil(kpY + r)); minr = int(math.floor(kpY - r))
+        facts["clipped_top"][iR] = minr < 0; facts["clipped_bottom"][iR] = maxr >= nRows
         for yi in range(minr, maxr + 1):
             if 0 <= yi < nRows:
                 vRowIndices[yi].append(iR)
@@ -821,39 +835,58 @@ def ref_compute_stereo_matches(keysL, descL, keysR, descR, pyrL, pyrR, scale_fac
         if row < 0 or row >= nRows:
             continue
         vCandidates = vRowIndices[row]
+        exits[iL] = SX_ROW_EMPTY
         if not vCandidates:
             continue
         minU = uL - maxD; maxU = uL - minD
+        exits[iL] = SX_OUTSIDE
         if maxU < 0:
             continue
         bestDist = TH_HIGH; bestIdxR = 0
+        nCand = 0; tied = []
         for iR in vCandidates:
             oR = int(keysR["octave"][iR])
             if oR < levelL - 1 or oR > levelL + 1:
                 continue
+            facts["run"][iL] += 1
             uR = _f32(keysR["x"][iR])
             if uR >= minU and uR <= maxU:
+                nCand += 1
+                facts["at_min_u"][iL] += int(uR == minU); facts["at_max_u"][iL] += int(uR == maxU)
                 dist = descriptor_distance(descL[iL], descR[iR])
                 if dist < bestDist:
-                    bestDist = dist; bestIdxR = iR
+                    bestDist = dist; bestIdxR = iR; tied = [iR]
+                elif dist == bestDist:
+                    tied.append(iR)
+        exits[iL] = SX_HAMMING if nCand else SX_NO_CANDIDATE
+        if nCand:
+            facts["best_dist"][iL] = bestDist
         if not (bestDist < thOrbDist):
             continue
+        facts["best_idx"][iL] = bestIdxR
+        facts["hamming_ties"][iL] = len(tied) - 1
+        facts["hamming_ties_dx"][iL] = any(keysR["x"][j] != keysR["x"][bestIdxR] for j in tied)
         uR0 = _f32(keysR["x"][bestIdxR])
         scaleFactor = _f32(inv_scale_factors[levelL])
         scaleduL = _f32(c_round(uL * scaleFactor)); scaledvL = _f32(c_round(vL * scaleFactor)); scaleduR0 = _f32(c_round(uR0 * scaleFactor))
         w = 5; L = 5
         imL, imR = pyrL[levelL], pyrR[levelL]
         y0, x0 = int(scaledvL - w), int(scaleduL - w)
+        exits[iL] = SX_LEFT_WINDOW
         if y0 < 0 or y0 + 2 * w + 1 > imL.shape[0] or x0 < 0 or x0 + 2 * w + 1 > imL.shape[1]:
             continue      # cv::Mat::rowRange / colRange would throw
         IL = imL[y0:y0 + 2 * w + 1, x0:x0 + 2 * w + 1].astype(np.float32)
         IL = IL - IL[w, w]
         iniu = scaleduR0 + _f32(L) - _f32(w); endu = scaleduR0 + _f32(L) + _f32(w) + _f32(1)
+        exits[iL] = SX_RIGHT_SPAN
         if iniu < 0 or endu >= imR.shape[1]:
             continue
         xr = int(scaleduR0)
+        exits[iL] = SX_RIGHT_WINDOW
         if xr - L - w < 0 or xr + L + w + 1 > imR.shape[1] or y0 + 2 * w + 1 > imR.shape[0]:
             continue
+        facts["touches"][iL] = (y0 == 0 or y0 + 2 * w + 1 == imL.shape[0] or x0 == 0 or x0 + 2 * w + 1 == imL.shape[1] or
+                                xr - L - w == 0 or xr + L + w + 1 == imR.shape[1])
         bestD = 2 ** 31 - 1; bestincR = 0
         vDists = [0.0] * (2 * L + 1)
         for incR in range(-L, L + 1):
@@ -863,32 +896,50 @@ def ref_compute_stereo_matches(keysL, descL, keysR, descR, pyrL, pyrR, scale_fac
             if dist < bestD:
                 bestD = int(dist); bestincR = incR
             vDists[L + incR] = dist
+        facts["sad_ties"][iL] = sum(1 for d in vDists if d == bestD) - 1
+        facts["sad"][iL] = bestD; facts["best_inc"][iL] = bestincR
+        exits[iL] = SX_END_SHIFT
         if bestincR == -L or bestincR == L:
             continue
         dist1, dist2, dist3 = _f32(vDists[L + bestincR - 1]), _f32(vDists[L + bestincR]), _f32(vDists[L + bestincR + 1])
         den = _f32(2.0) * (dist1 + dist3 - _f32(2.0) * dist2)
         with np.errstate(divide="ignore", invalid="ignore"):
             deltaR = (dist1 - dist3) / den
+        facts["delta"][iL] = deltaR
+        exits[iL] = SX_DELTA
         if deltaR < -1 or deltaR > 1:
             continue
         bestuR = _f32(scale_factors[levelL]) * (scaleduR0 + _f32(bestincR) + deltaR)
         disparity = uL - bestuR
+        exits[iL] = SX_DISPARITY
         if disparity >= minD and disparity < maxD:
+            exits[iL] = SX_MATCHED
             if disparity <= 0:
                 disparity = _f32(0.01)
                 bestuR = _f32(float(uL) - 0.01)
+                exits[iL] = SX_CLAMPED; facts["clamped"][iL] = True
             mvDepth[iL] = _f32(mbf) / disparity
             mvuRight[iL] = bestuR
             vDistIdx.append((bestD, iL))
     if vDistIdx:
         vDistIdx.sort()
+        facts["median_in"] = [d for d, _ in vDistIdx]
         median = _f32(vDistIdx[len(vDistIdx) // 2][0])
+        facts["median"] = int(median)
         thDist = _f32(1.5) * _f32(1.4) * median
         for i in range(len(vDistIdx) - 1, -1, -1):
             if vDistIdx[i][0] < thDist:
                 break
             mvuRight[vDistIdx[i][1]] = -1; mvDepth[vDistIdx[i][1]] = -1
-    return mvuRight, mvDepth
+            exits[vDistIdx[i][1]] = SX_MEDIAN
+    return mvuRight, mvDepth, exits, facts
+
+
+def ref_compute_stereo_matches(keysL, descL, keysR, descR, pyrL, pyrR, scale_factors, inv_scale_factors, mbf, mb):
+    """Frame::ComputeStereoMatches (L/src/Frame.cc:477-646), second reading (per-row Python lists, numpy windows).  pyrL / pyrR:
+    lists of the level images of the two extractors' mvImagePyramid.  Returns (mvuRight, mvDepth) as float32 arrays.  Where the
+    reference would index out of range (rows outside the image, windows leaving a level) the keypoint gets no match."""
+    return stereo_walk(keysL, descL, keysR, descR, pyrL, pyrR, scale_factors, inv_scale_factors, mbf, mb)[:2]
 
 
 # ------------------------------------------------------------------------------------------------------------------------------
