@@ -120,6 +120,9 @@ int orbfe_device_download(void* h_dst, const void* d_src, size_t bytes);
  *   map-point refresh   at most 1 024 observations per point, 1 048 576 points, 16 777 216 observations and 1 048 576 keyframes per
  *                       call, n_levels 1 .. ORBFE_MAX_LEVELS (the ORBFE_MP_MAX_* constants, each with its reason; pinned by
  *                       tests/test_mappoint_cpu.py)
+ *   covisibility graph  at most 32 768 keyframe rows, 2 048 entries per subject (conn_cap), 65 535 subjects or problems per launch,
+ *                       16 777 216 slots and 1 048 576 local keyframes per call, the point and observation limits of the map-point
+ *                       refresh (the ORBFE_COV_MAX_* constants, each with its reason; pinned by tests/test_covis_cpu.py)
  * Each limit is pinned at its largest accepted and its first refused value by tests/test_limits_gpu.py (levels: also
  * tests/test_cabi_cpu.py; depth maps: tests/test_frames_cpu.py and tests/test_frames_gpu.py; rectification:
  * tests/test_rectify_cpu.py and tests/test_rectify_gpu.py; pose optimisation: tests/test_pose_cpu.py).
@@ -1143,6 +1146,159 @@ int orbfe_refresh_map_points(const orbfe_mp_keyframe* keyframes, int n_kf, const
 int orbfe_refresh_map_points_batch_device(int P, const orbfe_mp_keyframe* d_keyframes, int n_kf, const orbfe_mp_obs* d_obs,
                                           int n_obs_total, const orbfe_mp_point* d_points, const void* d_points_pos, int point_stride,
                                           const float* scale_factors, int n_levels, int flags, orbfe_mp_update* d_updates, void* stream);
+
+/* ---- The covisibility graph: KeyFrame::UpdateConnections (L/src/KeyFrame.cc:268-354), the vote of Tracking::UpdateLocalKeyFrames
+ * (L/src/Tracking.cc:1115-1159) and LocalMapping::KeyFrameCulling (L/src/LocalMapping.cc:595-655) ---------------------------------------
+ * Both operations read the tables of orbfe_refresh_map_points*: the observation array orbfe_mp_obs[] and, of orbfe_mp_point, obs_offset
+ * and n_obs (ref and ref_octave are not read).  Beside them: point_bad[p] (one byte per point, MapPoint::isBad()), and per keyframe ROW
+ * of the table kf_order[row] and kf_bad[row] (KeyFrame::isBad()).  kf_order is the row's position in the iteration order of the
+ * reference's std::map<KeyFrame*, ...> over the table's keyframes: the caller sorts the pointers and states the positions, which are
+ * DISTINCT values in [0, n_kf).  With that order an input, every output is decided to the bit by a plain reading
+ * (csrc/covis_internal.h); no tolerance applies.
+ *
+ * 1. Counts.  A subject is a slice of the slot array (int32 point indices, -1 = an empty slot: mvpMapPoints of a keyframe or of a
+ *    frame), a keyframe row `self` or -1, and a mode.  Every non-empty slot whose point is not bad adds 1 to the counter of each
+ *    keyframe row in that point's observation list, except the row `self`.  The reference compares mnId (:295); the rows of the table
+ *    are distinct keyframes, so row equality is the same test.  Per subject one orbfe_cov_header and up to conn_cap orbfe_cov_entry
+ *    (kf, weight) at entries[s * conn_cap ..]:
+ *      ORBFE_COV_CONNECTIONS  all n_counted rows with a counter > 0 (mConnectedKeyFrameWeights), sorted by weight descending and among
+ *                 equal weights by kf_order descending: sort(vPairs) on pair<int, KeyFrame*> followed by push_front (:332-338).
+ *                 n_ordered = the entries with weight >= 15, which are the first n_ordered of the list and the reference's
+ *                 mvpOrderedConnectedKeyFrames / mvOrderedWeights.  kf_max / w_max: the first row in ascending kf_order that holds the
+ *                 strict maximum (:317-320).  n_ordered == 0 with n_counted > 0: the reference's ordered list is the one pair (kf_max,
+ *                 w_max); header.single = 1 says so and the entry list stays the full counter.  n_counted == 0: status EMPTY (the
+ *                 early return :302-303).
+ *      ORBFE_COV_VOTES  `self` is not read.  The entries are the counted rows whose keyframe is not bad, in ascending kf_order: the order
+ *                 in which mvpLocalKeyFrames is filled (Tracking.cc:1144-1159).  n_ordered = their number; kf_max / w_max the first
+ *                 strict maximum among them (-1 / 0 when there is none); n_counted counts the bad rows too and n_counted == 0 is EMPTY.
+ *    Status: OK; EMPTY; OVERFLOW -- more than conn_cap entries exist: the header is exact, the first conn_cap entries of the stated
+ *    order are written and nothing beyond them is touched; REFUSED -- decided by the subject's own workgroup, header zero but for the
+ *    status and kf_max = -1, no entry written, no other subject touched: an unknown mode, a slice outside the slot array, self outside
+ *    [-1, n_kf) (CONNECTIONS), a slot < -1 or >= n_points, a good point whose list lies outside the observation array, an observation
+ *    whose kf is outside [0, n_kf), or a kf_order outside [0, n_kf) on an observed row.  Entries behind n_written are never written.
+ *    With the caller stay: the reciprocal AddConnection calls, UpdateBestCovisibles of the other keyframes, the spanning-tree parent,
+ *    the neighbour / child / parent expansion of UpdateLocalKeyFrames up to 80 keyframes, and clearing bad points out of the frame;
+ *    csrc/host/Covisibility_hip.h replays them in the reference's order.
+ *
+ * 2. Keyframe culling, one problem per current keyframe: an ordered list of DISTINCT local keyframe rows
+ *    (GetVectorCovisibleKeyFrames()) and `monocular`.  Each point also carries n_obs_weighted = MapPoint::Observations() (a stereo
+ *    observation counts 2, so it is not the list length).  :603-654 read literally, with the sequential side effects: rows flagged
+ *    IS_ID0 are skipped; for every other row the slots are walked: an empty slot or a bad point is passed over; unless monocular the
+ *    slot is passed over when `depth > th_depth || depth < 0` (float); nMPs++; if Observations() > 3 the observations of the point in
+ *    OTHER rows with `octave_i <= octave + 1` are counted up to 3, and 3 make the slot redundant.  The row is redundant when
+ *    `nRedundant > 0.9 * nMPs` in double.  A redundant row without NOT_ERASE is CULLED before the next row is examined
+ *    (KeyFrame::SetBadFlag :416-434): each point that holds an observation of it loses that observation, its Observations() drops by 2
+ *    if the culled row's mvuRight[idx] >= 0 and by 1 otherwise, and it becomes bad when the result is <= 2
+ *    (MapPoint::EraseObservation, L/src/MapPoint.cc:112-136).  A redundant row with NOT_ERASE is MARKED and changes nothing.
+ *    No input is modified: with the set of rows culled so far, removed = the sum of 1 or 2 over a point's observations of culled rows,
+ *    Observations() = n_obs_weighted - removed, bad = bad_in || (removed > 0 && n_obs_weighted - removed <= 2), and observations of
+ *    culled rows are passed over; tests/np_covis.py states both readings and shows them equal.
+ *    Stated input domain: slot i of row k holds point p exactly when the list of p holds (k, i); bad points have empty lists; the
+ *    local rows of a problem are distinct.  Outside it only memory safety is promised.  A row is REFUSED (n_mps = n_redundant = 0,
+ *    nothing culled) when it lies outside the table, has n_keys < 0, lacks the slot or keypoint array with n_keys > 0 or the depth
+ *    array when not monocular, or one of its slots names a point, a list, a keyframe row or a keypoint index outside its table.  A null
+ *    u_right reads as -1 everywhere (a monocular keyframe).  A problem whose local range lies outside the local array writes nothing.
+ *
+ * Deterministic: integer LDS atomics only, whose order does not reach the result; the output order comes from the sort keys alone;
+ * a subject's or problem's bytes do not depend on S or Q, on its position in the batch or on the run.  No CPU fallback.
+ * Limits, each refused with ORBFE_ERR_INVALID one step past it, before any device call (pinned by tests/test_covis_cpu.py):
+ *   ORBFE_COV_MAX_KEYFRAMES    32 768 rows of the keyframe table: the counters are 32-bit words in LDS, 128 KiB of the 160 KiB; the
+ *                              culled set is one bit per row, 4 KiB
+ *   ORBFE_COV_MAX_CONN         conn_cap 1 .. 2 048: the entries are ordered in LDS beside the counters, 12 bytes each (24 KiB)
+ *   ORBFE_COV_MAX_POINTS       1 048 576 points and
+ *   ORBFE_COV_MAX_TOTAL_OBS    16 777 216 observations per call: the limits of the tables orbfe_refresh_map_points* defines
+ *   ORBFE_COV_MAX_TOTAL_SLOTS  16 777 216 slots per call (64 MiB of indices; offsets stay far inside int32)
+ *   ORBFE_COV_MAX_SUBJECTS     65 535 subjects and
+ *   ORBFE_COV_MAX_PROBLEMS     65 535 problems per launch: one workgroup each, the grid limit the other batch forms use
+ *   ORBFE_COV_MAX_TOTAL_LOCAL  1 048 576 local keyframes over all problems of a call (16 MiB of verdicts)
+ *   ORBFE_COV_MAX_KEYS         65 535 keypoints per keyframe (host form; the descriptor limit of the searches that fill the slots)
+ *   ORBFE_COV_MAX_TOTAL_KEYS   4 194 304 keypoints over all rows of the table (host culling form: it stages 40 bytes for each, 160 MiB;
+ *                              2 048 keyframes of 2 048 keypoints)
+ *   ORBFE_COV_MAX_TOTAL_ENTRIES  S x conn_cap <= 4 194 304 (host counting form: the entry block, 32 MiB, comes back in one copy) */
+#define ORBFE_COV_MAX_KEYFRAMES 32768
+#define ORBFE_COV_MAX_CONN 2048
+#define ORBFE_COV_MAX_POINTS 1048576
+#define ORBFE_COV_MAX_TOTAL_OBS 16777216
+#define ORBFE_COV_MAX_TOTAL_SLOTS 16777216
+#define ORBFE_COV_MAX_SUBJECTS 65535
+#define ORBFE_COV_MAX_PROBLEMS 65535
+#define ORBFE_COV_MAX_TOTAL_LOCAL 1048576
+#define ORBFE_COV_MAX_KEYS 65535
+#define ORBFE_COV_MAX_TOTAL_KEYS 4194304
+#define ORBFE_COV_MAX_TOTAL_ENTRIES 4194304
+#define ORBFE_COV_TH 15                   /* `int th = 15`, KeyFrame.cc:310 */
+enum { ORBFE_COV_CONNECTIONS = 0, ORBFE_COV_VOTES = 1 };                                               /* orbfe_cov_subject.mode */
+enum { ORBFE_COV_OK = 0, ORBFE_COV_EMPTY = 1, ORBFE_COV_OVERFLOW = 2, ORBFE_COV_REFUSED = 3 };         /* orbfe_cov_header.status */
+enum { ORBFE_COV_KEPT = 0, ORBFE_COV_CULLED = 1, ORBFE_COV_MARKED = 2, ORBFE_COV_SKIPPED_ID0 = 3, ORBFE_COV_ROW_REFUSED = 4 };   /* verdict */
+#define ORBFE_COV_IS_ID0 1                /* orbfe_cov_keyframe.flags: mnId == 0 */
+#define ORBFE_COV_NOT_ERASE 2             /* mbNotErase */
+typedef struct orbfe_cov_subject {        /* 16 bytes */
+  int32_t slot_offset, n_slots;           /* its slice of the slot array */
+  int32_t self;                           /* its own keyframe row, or -1 (a frame) */
+  int32_t mode;                           /* ORBFE_COV_CONNECTIONS or ORBFE_COV_VOTES */
+} orbfe_cov_subject;
+typedef struct orbfe_cov_header {         /* 32 bytes */
+  int32_t n_counted;                      /* rows with a counter > 0 */
+  int32_t n_ordered;                      /* CONNECTIONS: entries with weight >= 15; VOTES: entries (keyframe not bad) */
+  int32_t kf_max, w_max;                  /* pKFmax, nmax; -1, 0 when nothing is eligible */
+  int32_t status;                         /* ORBFE_COV_OK .. ORBFE_COV_REFUSED */
+  int32_t n_written;                      /* entries written: min(entries that exist, conn_cap) */
+  int32_t single;                         /* CONNECTIONS, n_ordered == 0 < n_counted: the ordered list is the pair (kf_max, w_max) */
+  int32_t reserved;                       /* 0 */
+} orbfe_cov_header;
+typedef struct orbfe_cov_entry {          /* 8 bytes */
+  int32_t kf, weight;                     /* row of the keyframe table, its counter */
+} orbfe_cov_entry;
+typedef struct orbfe_cov_keyframe {       /* one row of the culling table; 48 bytes, 8-byte aligned */
+  uint64_t keys_un;                       /* address of mvKeysUn, n_keys orbfe_keypoint (only octave is read) */
+  uint64_t u_right;                       /* address of mvuRight, n_keys floats; 0: every value reads as -1 */
+  uint64_t depth;                         /* address of mvDepth, n_keys floats; 0 is accepted only when monocular */
+  uint64_t slots;                         /* address of n_keys int32: the point index of mvpMapPoints[i], or -1 */
+  int32_t n_keys;                         /* DEVICE addresses for the device form, HOST addresses for the host form */
+  float th_depth;                         /* mThDepth */
+  int32_t flags;                          /* ORBFE_COV_IS_ID0 | ORBFE_COV_NOT_ERASE */
+  int32_t reserved;
+} orbfe_cov_keyframe;
+typedef struct orbfe_cov_problem {        /* 16 bytes */
+  int32_t local_offset, n_local;          /* its rows in the local array, in GetVectorCovisibleKeyFrames() order */
+  int32_t monocular;                      /* mbMonocular */
+  int32_t reserved;
+} orbfe_cov_problem;
+typedef struct orbfe_cov_verdict {        /* 16 bytes, one per element of the local array */
+  int32_t n_mps, n_redundant;             /* nMPs, nRedundantObservations */
+  int32_t verdict;                        /* ORBFE_COV_KEPT .. ORBFE_COV_ROW_REFUSED */
+  int32_t reserved;                       /* 0 */
+} orbfe_cov_verdict;
+/* S subjects.  HOST pointers, synchronous, on the calling thread's current device: one upload, one launch, one download.  headers: S
+ * records, all written; entries: S x conn_cap records, of which the first headers[s].n_written of each subject are written.
+ * Limits (ORBFE_ERR_INVALID): the ORBFE_COV_MAX_* above, every count >= 0, 1 <= conn_cap <= ORBFE_COV_MAX_CONN, null arrays with a
+ * count > 0, S x conn_cap <= ORBFE_COV_MAX_TOTAL_ENTRIES.  S == 0: nothing is launched and nothing behind a pointer is read. */
+int orbfe_covis_count(const orbfe_mp_obs* obs, int n_obs_total, const orbfe_mp_point* points, const uint8_t* point_bad, int n_points,
+                      const int32_t* kf_order, const uint8_t* kf_bad, int n_kf, const int32_t* slots, int n_slots_total,
+                      const orbfe_cov_subject* subjects, int S, int conn_cap, orbfe_cov_header* headers, orbfe_cov_entry* entries);
+/* The same with DEVICE pointers, asynchronous on `stream` (NULL: the NULL stream), S subjects in one launch.  Nothing outside the
+ * stated arrays is read or written; inputs are not modified.  Limits: as above; records not 4-byte aligned. */
+int orbfe_covis_count_batch_device(int S, const orbfe_mp_obs* d_obs, int n_obs_total, const orbfe_mp_point* d_points,
+                                   const uint8_t* d_point_bad, int n_points, const int32_t* d_kf_order, const uint8_t* d_kf_bad, int n_kf,
+                                   const int32_t* d_slots, int n_slots_total, const orbfe_cov_subject* d_subjects, int conn_cap,
+                                   orbfe_cov_header* d_headers, orbfe_cov_entry* d_entries, void* stream);
+/* Q culling problems.  HOST pointers (the table's addresses too: every keyframe's four arrays are staged with the tables), synchronous:
+ * one upload, one launch, one download.  verdicts: n_local_total records, one per element of `local`; those of a problem's range
+ * are written.  A row's slot array is needed only when a problem lists the row; without it that row is REFUSED.
+ * Limits (ORBFE_ERR_INVALID): the ORBFE_COV_MAX_* above; every count >= 0; null arrays with a count > 0; a row with n_keys outside
+ * 0 .. ORBFE_COV_MAX_KEYS, or with n_keys > 0 and no keypoint array; the n_keys of all rows summing to more than
+ * ORBFE_COV_MAX_TOTAL_KEYS; a problem whose range lies outside the local array.  Q == 0: nothing is launched and nothing behind a
+ * pointer is read. */
+int orbfe_covis_cull_keyframes(const orbfe_mp_obs* obs, int n_obs_total, const orbfe_mp_point* points, const uint8_t* point_bad,
+                               const int32_t* n_obs_weighted, int n_points, const orbfe_cov_keyframe* keyframes, int n_kf,
+                               const int32_t* local, int n_local_total, const orbfe_cov_problem* problems, int Q,
+                               orbfe_cov_verdict* verdicts);
+/* The same with DEVICE pointers and device addresses in the table, asynchronous on `stream`, Q problems in one launch.  Limits: as
+ * above except what lies behind a pointer, which the device checks; records not 4-byte (the keyframe table: 8-byte) aligned. */
+int orbfe_covis_cull_keyframes_batch_device(int Q, const orbfe_mp_obs* d_obs, int n_obs_total, const orbfe_mp_point* d_points,
+                                            const uint8_t* d_point_bad, const int32_t* d_n_obs_weighted, int n_points,
+                                            const orbfe_cov_keyframe* d_keyframes, int n_kf, const int32_t* d_local, int n_local_total,
+                                            const orbfe_cov_problem* d_problems, orbfe_cov_verdict* d_verdicts, void* stream);
 
 /* SearchForInitialization (L/src/ORBmatcher.cc:388-492), the monocular map-initialisation matcher: level-0
  * keypoints of F1 are searched in a window of `window_size` pixels around prev_matched_xy[2*i..2*i+1] in F2; a

@@ -156,6 +156,26 @@ MP_MAX_OBS, MP_MAX_POINTS, MP_MAX_TOTAL_OBS, MP_MAX_KEYFRAMES = 1024, 1048576, 1
 MP_DESCRIPTOR, MP_NORMAL_DEPTH = 1, 2
 MP_UPDATED, MP_UNCHANGED, MP_REFUSED = 0, 1, 2
 MP_SMALL_OBS = 64   # observations up to which a point is one wave's (csrc/mappoint_internal.h)
+# orbfe_cov_subject / orbfe_cov_header / orbfe_cov_entry / orbfe_cov_keyframe / orbfe_cov_problem / orbfe_cov_verdict and the ORBFE_COV_*
+# limits (KeyFrame::UpdateConnections, Tracking::UpdateLocalKeyFrames, LocalMapping::KeyFrameCulling, include/orbfe.h)
+COV_SUBJECT_DTYPE = np.dtype([("slot_offset", "<i4"), ("n_slots", "<i4"), ("self", "<i4"), ("mode", "<i4")])
+COV_HEADER_DTYPE = np.dtype([("n_counted", "<i4"), ("n_ordered", "<i4"), ("kf_max", "<i4"), ("w_max", "<i4"), ("status", "<i4"),
+                             ("n_written", "<i4"), ("single", "<i4"), ("reserved", "<i4")])
+COV_ENTRY_DTYPE = np.dtype([("kf", "<i4"), ("weight", "<i4")])
+COV_KEYFRAME_DTYPE = np.dtype([("keys_un", "<u8"), ("u_right", "<u8"), ("depth", "<u8"), ("slots", "<u8"), ("n_keys", "<i4"),
+                               ("th_depth", "<f4"), ("flags", "<i4"), ("reserved", "<i4")])
+COV_PROBLEM_DTYPE = np.dtype([("local_offset", "<i4"), ("n_local", "<i4"), ("monocular", "<i4"), ("reserved", "<i4")])
+COV_VERDICT_DTYPE = np.dtype([("n_mps", "<i4"), ("n_redundant", "<i4"), ("verdict", "<i4"), ("reserved", "<i4")])
+assert COV_SUBJECT_DTYPE.itemsize == 16 and COV_HEADER_DTYPE.itemsize == 32 and COV_ENTRY_DTYPE.itemsize == 8
+assert COV_KEYFRAME_DTYPE.itemsize == 48 and COV_PROBLEM_DTYPE.itemsize == 16 and COV_VERDICT_DTYPE.itemsize == 16
+(COV_MAX_KEYFRAMES, COV_MAX_CONN, COV_MAX_POINTS, COV_MAX_TOTAL_OBS, COV_MAX_TOTAL_SLOTS, COV_MAX_SUBJECTS, COV_MAX_PROBLEMS,
+ COV_MAX_TOTAL_LOCAL, COV_MAX_KEYS) = 32768, 2048, 1048576, 16777216, 16777216, 65535, 65535, 1048576, 65535
+COV_MAX_TOTAL_KEYS, COV_MAX_TOTAL_ENTRIES = 4194304, 4194304
+COV_TH = 15
+COV_CONNECTIONS, COV_VOTES = 0, 1
+COV_OK, COV_EMPTY, COV_OVERFLOW, COV_REFUSED = 0, 1, 2, 3
+COV_KEPT, COV_CULLED, COV_MARKED, COV_SKIPPED_ID0, COV_ROW_REFUSED = 0, 1, 2, 3, 4
+COV_IS_ID0, COV_NOT_ERASE = 1, 2
 
 
 class RectifyCamera(C.Structure):
@@ -206,6 +226,7 @@ EXPORTS = [
     "orbfe_kfdb_set_covisibles", "orbfe_kfdb_score", "orbfe_kfdb_detect_relocalization", "orbfe_kfdb_detect_loop",
     "orbfe_kfdb_detect_relocalization_device", "orbfe_kfdb_detect_loop_device", "orbfe_debug_kfdb_arrangement",
     "orbfe_refresh_map_points", "orbfe_refresh_map_points_batch_device",
+    "orbfe_covis_count", "orbfe_covis_count_batch_device", "orbfe_covis_cull_keyframes", "orbfe_covis_cull_keyframes_batch_device",
 ]
 
 
@@ -341,6 +362,10 @@ def lib():
     L.orbfe_kfdb_detect_loop_device.argtypes = [vp, ci, vp, vp, vp, vp, vp, vp, ci, vp, vp, vp, vp, vp, vp]
     L.orbfe_refresh_map_points.argtypes = [vp, ci, vp, ci, vp, vp, ci, vp, ci, ci, vp]
     L.orbfe_refresh_map_points_batch_device.argtypes = [ci, vp, ci, vp, ci, vp, vp, ci, vp, ci, ci, vp, vp]
+    L.orbfe_covis_count.argtypes = [vp, ci, vp, vp, ci, vp, vp, ci, vp, ci, vp, ci, ci, vp, vp]
+    L.orbfe_covis_count_batch_device.argtypes = [ci, vp, ci, vp, vp, ci, vp, vp, ci, vp, ci, vp, ci, vp, vp, vp]
+    L.orbfe_covis_cull_keyframes.argtypes = [vp, ci, vp, vp, vp, ci, vp, ci, vp, ci, vp, ci, vp]
+    L.orbfe_covis_cull_keyframes_batch_device.argtypes = [ci, vp, ci, vp, vp, vp, ci, vp, ci, vp, ci, vp, vp, vp]
     for name in EXPORTS:
         if name != "orbfe_last_error":
             getattr(L, name).restype = ci

@@ -1,6 +1,6 @@
 // host_internal.h -- what the host side of the device back ends shares: the error channel and the device check (every .cpp with a
 // C ABI), and HostCall, the staging of a one-problem host call on the calling thread's matcher handle (pose.cpp, mapping.cpp,
-// sim3.cpp, optsim3.cpp, lba.cpp, mappoint.cpp, matcher.cpp; its body is in matcher.cpp, where that handle lives).
+// sim3.cpp, optsim3.cpp, lba.cpp, mappoint.cpp, covis.cpp, matcher.cpp; its body is in matcher.cpp, where that handle lives).
 // With HOST_LAYOUT_ONLY defined only the region arithmetic is declared, which needs no HIP header or runtime.
 #pragma once
 #include <assert.h>
