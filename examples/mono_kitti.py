@@ -9,10 +9,14 @@ un-initialised monocular tracker:
        becomes the reference (vbPrevMatched = its keypoints); every later frame is matched against it with
        ORBmatcher(0.9, true).SearchForInitialization(ini, cur, vbPrevMatched, vnMatches12, 100); fewer than 101 keypoints or
        fewer than 100 matches drop the reference, exactly as the reference deletes its Initializer.
-Two-view geometry (Initializer::Initialize) is out of scope, so a reference frame is kept for as long as it keeps matching --
-what the reference does while Initialize() keeps returning false.  Prints the examples' timing report.
+Without --initialize a reference frame is kept for as long as it keeps matching -- what the reference does while Initialize()
+keeps returning false.  With it, every successful search is followed by the two-view geometry (Initializer::Initialize, :546-565:
+Initializer(frame, 1.0, 200), the sets of eight drawn from one generator seeded once); on success the model, R21, t21 and the
+triangulated count are recorded and the reference is dropped (CreateInitialMapMonocular and what follows are out of scope).
+Prints the examples' timing report.
 
 usage: mono_kitti.py <sequence_dir> [--features 2000] [--max-frames N] [--dump FILE.npz]
+                     [--initialize [--iterations 200] [--fx .. --fy .. --cx .. --cy ..]]   (camera defaults: KITTI 00-02)
 """
 from __future__ import annotations
 
@@ -35,6 +39,12 @@ def main():
     ap.add_argument("--features", type=int, default=2000)
     ap.add_argument("--max-frames", type=int, default=0)
     ap.add_argument("--dump", default="")
+    ap.add_argument("--initialize", action="store_true")
+    ap.add_argument("--fx", type=float, default=718.856)
+    ap.add_argument("--fy", type=float, default=718.856)
+    ap.add_argument("--cx", type=float, default=607.1928)
+    ap.add_argument("--cy", type=float, default=185.2157)
+    ap.add_argument("--iterations", type=int, default=200)
     args = ap.parse_args()
 
     from refactored_orb_slam2_amd import ORBextractor
@@ -49,7 +59,11 @@ def main():
     matcher = ORBmatcher(0.9, True)
     ini = None            # (FrameView of the reference frame, vbPrevMatched)
     track_times, dump = [], {}
-    n_ref, n_matched_frames, n_matches = 0, 0, 0
+    n_ref, n_matched_frames, n_matches, n_init = 0, 0, 0, 0
+    if args.initialize:
+        from refactored_orb_slam2_amd import initializer
+        init_par = initializer.init_params(args.fx, args.fy, args.cx, args.cy)   # sigma 1.0, parallax 1.0, 50 points
+        init_rng = np.random.default_rng(0)                                      # SeedRandOnce(0): one stream for the whole run
     img = None
     for i in range(n_all):
         img = read_gray(files[i], img)
@@ -71,6 +85,18 @@ def main():
             else:
                 ini = (ini[0], prev); state = "matched"
                 n_matched_frames += 1; n_matches += nm
+                if args.initialize:                               # :546-565
+                    ref_xy = np.stack([ini[0].keys["x"], ini[0].keys["y"]], 1).astype(np.float32)
+                    cur_xy = np.stack([keys["x"], keys["y"]], 1).astype(np.float32)
+                    sets = initializer.draw_sets(int((m12 >= 0).sum()), args.iterations, init_rng)
+                    got = initializer.initialize(init_par, ref_xy, cur_xy, m12, sets, want_candidates=False)
+                    res = got["result"]
+                    if args.dump:
+                        dump[f"sets_{i}"] = sets; dump[f"init_{i}"] = np.array(res)
+                    if res["success"]:
+                        n_init += 1
+                        print(f"frame {i}: initialised from {'H' if res['model'] == 1 else 'F'}, {int(res['n_triangulated'])} points")
+                        ini, state = None, "initialized"
         track_times.append(time.perf_counter() - t0)
         if args.dump:
             dump[f"kp_{i}"] = keys; dump[f"desc_{i}"] = desc; dump[f"nm_{i}"] = np.int32(nm); dump[f"m12_{i}"] = m12
@@ -83,6 +109,8 @@ def main():
     print(f"mean tracking time: {sum(track_times) / len(track_times)}")
     print(f"frames: {n_all}, reference frames: {n_ref}, frames matched against a reference: {n_matched_frames}, "
           f"matches/matched frame: {n_matches / max(n_matched_frames, 1):.1f}")
+    if args.initialize:
+        print(f"initialisations: {n_init}")
     ex.close()
 
 

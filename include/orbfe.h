@@ -1500,6 +1500,113 @@ int orbfe_pipeline_gather(orbfe_pipeline* p, int slot, orbfe_gather* g, int mode
                           uint8_t* d_desc_all);
 int orbfe_pipeline_gather_wait(orbfe_pipeline* p, int slot);
 
+/* ---- Initializer (L/src/Initializer.cc) ---------------------------------------------------------------------------------------------
+ * The two-view geometry between orbfe_search_for_initialization and a first monocular map (Tracking.cc:505-565): H hypotheses of
+ * a homography and of a fundamental matrix from eight matches each (ComputeH21 / ComputeF21, :218-292), scored over all matches
+ * (CheckHomography / CheckFundamental, :294-459); the first maximum per model, RH = SH / (SH + SF), H when RH > 0.40; then the
+ * eight Faugeras motions (ReconstructH, :562-721) or the four of DecomposeE (ReconstructF, :461-560), each triangulated over the
+ * model's inliers (CheckRT, :785-899), and the acceptance rules.  One call is five launches without a host round trip.
+ * The caller draws the sets of eight (:80-93; initializer.py: draw_sets); the library holds no random state.
+ * csrc/initializer_internal.h states the arithmetic once.  cv::SVDecomp, cv::Mat::inv and cv::determinant are not available where
+ * this library is built: the null vector of the 16x9 / 8x9 system and the 3x3 decompositions come from this
+ * project's own one-sided Jacobi in double on the float entries, rounded to float; inv and determinant of a 3x3 are the cofactor
+ * forms in double.  The sign of a null vector changes no decision (ratios in CheckHomography, squares in CheckFundamental, ratios
+ * of singular values, det U * det Vt and both signs of t behind them); it is fixed so that bytes are deterministic.  The ORDER of
+ * the motion candidates depends on such signs, their set does not.
+ * Normalize (:739-783) sums in float in index order over ALL keypoints of a frame; T1 / T2 are bit-equal to that reading.
+ * Where the reference is undefined this library is defined: SH = SF = 0 (the reference passes an empty cv::Mat on and throws) gives
+ * model 0; fewer than 8 matches (Tracking asks for 100) gives model 0 and launches nothing; a NaN cosine among the good points
+ * (std::sort's behaviour is undefined) sorts last.
+ * Deterministic: no float atomics, a problem's bytes do not depend on P or its place in the batch, hypothesis h's record and
+ * words do not depend on H.  No CPU fallback. */
+#define ORBFE_INIT_MAX_MATCHES 4096      /* keypoints of either frame, hence matches: mpIniORBextractor extracts 2 * nFeatures; 16 bytes
+                                            a match, 64 KiB = the LDS a workgroup stages them in */
+#define ORBFE_INIT_MAX_HYPOTHESES 1024   /* per model; the reference uses 200 */
+typedef struct orbfe_init_params {
+  float fx, fy, cx, cy;                  /* mK */
+  float sigma;                           /* mSigma (Tracking: 1.0) */
+  float min_parallax;                    /* degrees (Initialize: 1.0) */
+  int32_t min_triangulated;              /* (Initialize: 50) */
+  int32_t reserved;
+} orbfe_init_params;                     /* 32 bytes */
+typedef struct orbfe_init_hypothesis {
+  float M[9];                            /* H21i or F21i row-major, in pixel coordinates */
+  float score;                           /* currentScore */
+  int32_t n_inliers;                     /* set bits of its words */
+  int32_t status;                        /* 1 evaluated; 0: the set is no draw of :80-93 (an index outside [0, N) or a repeated one) and
+                                            the whole record and its words are zero */
+  int32_t reserved[4];
+} orbfe_init_hypothesis;                 /* 64 bytes */
+typedef struct orbfe_init_candidate {
+  float R[9], t[3];                      /* one motion of DecomposeE / Faugeras */
+  int32_t n_good;                        /* CheckRT's return value */
+  float parallax;                        /* degrees */
+  int32_t reserved[2];
+} orbfe_init_candidate;                  /* 64 bytes */
+/* orbfe_init_result.reason: one bit per condition that failed (0 on success) */
+#define ORBFE_INIT_FEW_MATCHES 1         /* fewer than 8 matches: no set of eight exists (not a reference exit, Tracking.cc:529 asks for 100) */
+#define ORBFE_INIT_NO_MODEL 2            /* SH == 0 and SF == 0, or no hypothesis at all: RH is 0 / 0 (:110) */
+#define ORBFE_INIT_H_DEGENERATE 4        /* :590  d1 / d2 < 1.00001 || d2 / d3 < 1.00001 */
+#define ORBFE_INIT_F_FEW_GOOD 8          /* :516  maxGood < nMinGood */
+#define ORBFE_INIT_F_SIMILAR 16          /* :516  nsimilar > 1 */
+#define ORBFE_INIT_F_PARALLAX 32         /* :522, :531, :540, :549  parallax of the first best candidate not > minParallax */
+#define ORBFE_INIT_H_SECOND 64           /* :710  not secondBestGood < 0.75 * bestGood */
+#define ORBFE_INIT_H_PARALLAX 128        /* :710  not bestParallax >= minParallax */
+#define ORBFE_INIT_H_MIN_TRIANGULATED 256 /* :711  not bestGood > minTriangulated */
+#define ORBFE_INIT_H_FEW_GOOD 512        /* :711  not bestGood > 0.9 * N */
+typedef struct orbfe_init_result {
+  int32_t model;                         /* 0 none, 1 homography, 2 fundamental */
+  int32_t success;                       /* Initialize's return value */
+  int32_t reason;                        /* ORBFE_INIT_* bits */
+  int32_t best_h, best_f;                /* first hypothesis with the maximal score > 0 per model, or -1 */
+  float score_h, score_f, rh;            /* SH, SF, RH (0 where undefined) */
+  int32_t n_matches;                     /* N = mvMatches12.size() */
+  int32_t n_inliers;                     /* of the chosen model: N of ReconstructF / ReconstructH */
+  int32_t n_candidates;                  /* 4 (F), 8 (H), 0 when none was built */
+  int32_t best_candidate;                /* F: the first with maxGood; H: bestSolutionIdx; -1 without one */
+  int32_t n_good;                        /* maxGood / bestGood */
+  int32_t second_good_or_n_similar;      /* H: secondBestGood; F: nsimilar */
+  float parallax;                        /* of best_candidate */
+  int32_t n_triangulated;                /* set bits of the triangulated words (0 without success) */
+  float H21[9], F21[9];                  /* the two winners (zero without one) */
+  float R21[9], t21[3];                  /* zero without success */
+  float norm1[4], norm2[4];              /* Normalize of the two frames: meanX, meanY, sX, sY (T = [sX 0 -meanX * sX; 0 sY -meanY * sY; 0 0 1]) */
+  int32_t reserved[2];
+} orbfe_init_result;                     /* 224 bytes */
+/* Initializer::Initialize on host arrays, synchronous: one packed upload, five launches, one packed download.
+ * keys1[n1] / keys2[n2]: (x, y) of mvKeysUn of the reference and the current frame; matches12[n1]: index into keys2 or < 0; sets[H][8]:
+ * indices into the match list (the pairs (i, matches12[i]) with matches12[i] >= 0, in order of i).
+ * Outputs: *result; P3D[n1][3] (zero rows where the reference leaves cv::Point3f's default; all zero without success);
+ * triangulated[ceil(n1 / 64)] (bit i = vbTriangulated[i]); inlier_words[ceil(N / 64)] sized for ceil(n1 / 64) (the chosen model's
+ * vbMatchesInliers over the match list; zero for model 0).  Optional (NULL to skip): hyps_h / hyps_f [H], words_h / words_f
+ * [H][ceil(n1 / 64)] (row stride ceil(n1 / 64) words, the first ceil(N / 64) used), candidates[8].
+ * Limits (ORBFE_ERR_INVALID): 0 <= n1, n2 <= ORBFE_INIT_MAX_MATCHES, 0 <= H <= ORBFE_INIT_MAX_HYPOTHESES, matches12[i] < n2, null
+ * pointers.  A set that is no draw yields a zero record (status 0) and reads nothing outside its problem. */
+int orbfe_initializer_initialize(const orbfe_init_params* params, const float* keys1, int n1, const float* keys2, int n2,
+                                 const int32_t* matches12, const int32_t* sets, int H, orbfe_init_result* result, float* P3D,
+                                 uint64_t* triangulated, uint64_t* inlier_words, orbfe_init_hypothesis* hyps_h,
+                                 orbfe_init_hypothesis* hyps_f, uint64_t* words_h, uint64_t* words_f, orbfe_init_candidate* candidates);
+/* Bytes of the workspace of orbfe_initializer_initialize_batch_device for P problems of at most `cap` keypoints a frame.
+ * Limits (ORBFE_ERR_INVALID): 0 <= P <= 65 535, 1 <= cap <= ORBFE_INIT_MAX_MATCHES, bytes != NULL. */
+int orbfe_initializer_workspace_bytes(int P, int cap, size_t* bytes);
+/* P ragged problems from device memory on `stream` (NULL: the NULL stream), asynchronous.  d_params [P]; d_keys1 / d_keys2
+ * [P][cap][2]; d_n1 / d_n2 [P] (clamped to [0, cap]); d_matches12 [P][cap] (an entry >= n2 counts as no match); d_sets
+ * [P][h_cap][8]; d_H [P] (clamped to [0, h_cap]).  Outputs, all required: d_result [P]; d_P3D [P][cap][3]; d_triangulated and
+ * d_inlier_words [P][W], W = ceil(cap / 64); d_hyps [P][2][h_cap] and d_words [P][2][h_cap][W] (model H first); d_candidates [P][8].
+ * A problem's bytes equal the host form's on the same problem (rows and words behind a problem's counts are not written, except
+ * P3D and the two word rows, which are written for all of n1).  One exception: for a problem with fewer than 8 matches no hypothesis
+ * is evaluated and its rows of d_hyps / d_words are left as they were, where the host form hands back zeros; its result record, P3D,
+ * word rows and candidates are the host form's.
+ * Limits (ORBFE_ERR_INVALID): 0 <= P <= 65 535 (0: nothing is launched), 1 <= cap <= ORBFE_INIT_MAX_MATCHES, 1 <= h_cap <=
+ * ORBFE_INIT_MAX_HYPOTHESES, workspace_bytes below orbfe_initializer_workspace_bytes(P, cap), null pointers, pointers not 4-byte
+ * (words, workspace: 8-byte) aligned. */
+int orbfe_initializer_initialize_batch_device(int P, const orbfe_init_params* d_params, const float* d_keys1, const int32_t* d_n1,
+                                              const float* d_keys2, const int32_t* d_n2, int cap, const int32_t* d_matches12,
+                                              const int32_t* d_sets, const int32_t* d_H, int h_cap, orbfe_init_result* d_result,
+                                              float* d_P3D, uint64_t* d_triangulated, uint64_t* d_inlier_words,
+                                              orbfe_init_hypothesis* d_hyps, uint64_t* d_words, orbfe_init_candidate* d_candidates,
+                                              void* d_workspace, size_t workspace_bytes, void* stream);
+
 /* --------------------------------------------------------------------------------------- sequence driver helpers */
 /* Dependency-free PNG input for the dataset drivers (the reference reads with cv::imread(..., IMREAD_UNCHANGED),
  * Source/Examples/Stereo/stereo_kitti.cc:88-89, Source/Examples/RGB-D/rgbd_tum.cc, and converts colour frames in

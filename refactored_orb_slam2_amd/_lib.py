@@ -118,6 +118,22 @@ assert SIM3_VIEW_DTYPE.itemsize == 64 and SIM3_PAIR_DTYPE.itemsize == 32 and SIM
 assert SIM3_RESULT_DTYPE.itemsize == 128
 SIM3_MAX_PAIRS, SIM3_MAX_HYPOTHESES, SIM3_MAX_PROBLEMS = 1024, 4096, 65535
 SIM3_WAVES = 4   # hypotheses per workgroup of sim3_hypotheses_kernel (csrc/sim3_internal.h)
+# orbfe_init_params / orbfe_init_hypothesis / orbfe_init_candidate / orbfe_init_result (Initializer, include/orbfe.h)
+INIT_PARAMS_DTYPE = np.dtype([("fx", "<f4"), ("fy", "<f4"), ("cx", "<f4"), ("cy", "<f4"), ("sigma", "<f4"), ("min_parallax", "<f4"),
+                              ("min_triangulated", "<i4"), ("reserved", "<i4")])
+INIT_HYPOTHESIS_DTYPE = np.dtype([("M", "<f4", (9,)), ("score", "<f4"), ("n_inliers", "<i4"), ("status", "<i4"), ("reserved", "<i4", (4,))])
+INIT_CANDIDATE_DTYPE = np.dtype([("R", "<f4", (9,)), ("t", "<f4", (3,)), ("n_good", "<i4"), ("parallax", "<f4"), ("reserved", "<i4", (2,))])
+INIT_RESULT_DTYPE = np.dtype([("model", "<i4"), ("success", "<i4"), ("reason", "<i4"), ("best_h", "<i4"), ("best_f", "<i4"), ("score_h", "<f4"),
+                              ("score_f", "<f4"), ("rh", "<f4"), ("n_matches", "<i4"), ("n_inliers", "<i4"), ("n_candidates", "<i4"),
+                              ("best_candidate", "<i4"), ("n_good", "<i4"), ("second_good_or_n_similar", "<i4"), ("parallax", "<f4"),
+                              ("n_triangulated", "<i4"), ("H21", "<f4", (9,)), ("F21", "<f4", (9,)), ("R21", "<f4", (9,)), ("t21", "<f4", (3,)),
+                              ("norm1", "<f4", (4,)), ("norm2", "<f4", (4,)), ("reserved", "<i4", (2,))])
+assert INIT_PARAMS_DTYPE.itemsize == 32 and INIT_HYPOTHESIS_DTYPE.itemsize == 64 and INIT_CANDIDATE_DTYPE.itemsize == 64
+assert INIT_RESULT_DTYPE.itemsize == 224
+INIT_MAX_MATCHES, INIT_MAX_HYPOTHESES, INIT_MAX_PROBLEMS = 4096, 1024, 65535
+INIT_WAVES = 4   # hypotheses per workgroup of initz_hypotheses_kernel (csrc/initializer_internal.h)
+(INIT_FEW_MATCHES, INIT_NO_MODEL, INIT_H_DEGENERATE, INIT_F_FEW_GOOD, INIT_F_SIMILAR, INIT_F_PARALLAX, INIT_H_SECOND, INIT_H_PARALLAX,
+ INIT_H_MIN_TRIANGULATED, INIT_H_FEW_GOOD) = (1 << k for k in range(10))
 # orbfe_optsim3_pair / orbfe_optsim3_result (Optimizer::OptimizeSim3, include/orbfe.h)
 OPTSIM3_PAIR_DTYPE = np.dtype([("Xw1", "<f4", (3,)), ("Xw2", "<f4", (3,)), ("obs1", "<f4", (2,)), ("obs2", "<f4", (2,)),
                                ("inv_sigma2_1", "<f4"), ("inv_sigma2_2", "<f4")])
@@ -227,6 +243,7 @@ EXPORTS = [
     "orbfe_kfdb_detect_relocalization_device", "orbfe_kfdb_detect_loop_device", "orbfe_debug_kfdb_arrangement",
     "orbfe_refresh_map_points", "orbfe_refresh_map_points_batch_device",
     "orbfe_covis_count", "orbfe_covis_count_batch_device", "orbfe_covis_cull_keyframes", "orbfe_covis_cull_keyframes_batch_device",
+    "orbfe_initializer_initialize", "orbfe_initializer_workspace_bytes", "orbfe_initializer_initialize_batch_device",
 ]
 
 
@@ -366,6 +383,9 @@ def lib():
     L.orbfe_covis_count_batch_device.argtypes = [ci, vp, ci, vp, vp, ci, vp, vp, ci, vp, ci, vp, ci, vp, vp, vp]
     L.orbfe_covis_cull_keyframes.argtypes = [vp, ci, vp, vp, vp, ci, vp, ci, vp, ci, vp, ci, vp]
     L.orbfe_covis_cull_keyframes_batch_device.argtypes = [ci, vp, ci, vp, vp, vp, ci, vp, ci, vp, ci, vp, vp, vp]
+    L.orbfe_initializer_initialize.argtypes = [vp, vp, ci, vp, ci, vp, vp, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.orbfe_initializer_workspace_bytes.argtypes = [ci, ci, C.POINTER(sz)]
+    L.orbfe_initializer_initialize_batch_device.argtypes = [ci, vp, vp, vp, vp, vp, ci, vp, vp, vp, ci, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]
     for name in EXPORTS:
         if name != "orbfe_last_error":
             getattr(L, name).restype = ci
