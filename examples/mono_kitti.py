@@ -12,11 +12,14 @@ un-initialised monocular tracker:
 Without --initialize a reference frame is kept for as long as it keeps matching -- what the reference does while Initialize()
 keeps returning false.  With it, every successful search is followed by the two-view geometry (Initializer::Initialize, :546-565:
 Initializer(frame, 1.0, 200), the sets of eight drawn from one generator seeded once); on success the model, R21, t21 and the
-triangulated count are recorded and the reference is dropped (CreateInitialMapMonocular and what follows are out of scope).
+triangulated count are recorded and the reference is dropped.  With --map on top, a successful initialisation is followed by
+Tracking::CreateInitialMapMonocular (:571-666) as far as the library takes it: the map points of the triangulated matches, the global
+bundle adjustment of 20 iterations, the median scene depth, the reset rule and the rescale (ComputeBoW and the map bookkeeping are
+out of scope); the points, the median depth, chi2 before and after and the decision are reported.
 Prints the examples' timing report.
 
 usage: mono_kitti.py <sequence_dir> [--features 2000] [--max-frames N] [--dump FILE.npz]
-                     [--initialize [--iterations 200] [--fx .. --fy .. --cx .. --cy ..]]   (camera defaults: KITTI 00-02)
+                     [--initialize [--map] [--iterations 200] [--fx .. --fy .. --cx .. --cy ..]]   (camera defaults: KITTI 00-02)
 """
 from __future__ import annotations
 
@@ -40,12 +43,15 @@ def main():
     ap.add_argument("--max-frames", type=int, default=0)
     ap.add_argument("--dump", default="")
     ap.add_argument("--initialize", action="store_true")
+    ap.add_argument("--map", action="store_true", help="with --initialize: create the initial map after a successful initialisation")
     ap.add_argument("--fx", type=float, default=718.856)
     ap.add_argument("--fy", type=float, default=718.856)
     ap.add_argument("--cx", type=float, default=607.1928)
     ap.add_argument("--cy", type=float, default=185.2157)
     ap.add_argument("--iterations", type=int, default=200)
     args = ap.parse_args()
+    if args.map and not args.initialize:
+        ap.error("--map needs --initialize")
 
     from refactored_orb_slam2_amd import ORBextractor
     from refactored_orb_slam2_amd.matcher import FrameView, ORBmatcher
@@ -59,11 +65,14 @@ def main():
     matcher = ORBmatcher(0.9, True)
     ini = None            # (FrameView of the reference frame, vbPrevMatched)
     track_times, dump = [], {}
-    n_ref, n_matched_frames, n_matches, n_init = 0, 0, 0, 0
+    n_ref, n_matched_frames, n_matches, n_init, n_maps = 0, 0, 0, 0, 0
     if args.initialize:
         from refactored_orb_slam2_amd import initializer
         init_par = initializer.init_params(args.fx, args.fy, args.cx, args.cy)   # sigma 1.0, parallax 1.0, 50 points
         init_rng = np.random.default_rng(0)                                      # SeedRandOnce(0): one stream for the whole run
+    if args.map:
+        from refactored_orb_slam2_amd import optimizer
+        map_cam = optimizer.pose_camera(args.fx, args.fy, args.cx, args.cy, 0.0, ex.GetInverseScaleSigmaSquares())
     img = None
     for i in range(n_all):
         img = read_gray(files[i], img)
@@ -96,6 +105,17 @@ def main():
                     if res["success"]:
                         n_init += 1
                         print(f"frame {i}: initialised from {'H' if res['model'] == 1 else 'F'}, {int(res['n_triangulated'])} points")
+                        if args.map:                              # :565 CreateInitialMapMonocular
+                            made = initializer.create_initial_map(map_cam, ref_xy, cur_xy, m12, got["P3D"], got["triangulated_words"], res,
+                                                                  ini[0].keys["octave"], keys["octave"])
+                            mr = made["result"]
+                            n_maps += int(mr["success"])
+                            print(f"frame {i}: initial map of {int(mr['n_points'])} points, median depth {float(mr['median_depth']):.4f}, chi2 "
+                                  f"{float(mr['ba']['chi2_first']):.1f} -> {float(mr['ba']['chi2_final']):.1f} in {int(mr['ba']['iterations'])} "
+                                  f"iterations: {'kept, scaled to median depth 1' if mr['success'] else 'reset (reason %d)' % int(mr['reason'])}")
+                            if args.dump:
+                                dump[f"map_{i}"] = np.array(mr); dump[f"map_poses_{i}"] = made["poses"]
+                                dump[f"map_points_{i}"] = made["points"]; dump[f"map_index_{i}"] = made["index"]
                         ini, state = None, "initialized"
         track_times.append(time.perf_counter() - t0)
         if args.dump:
@@ -110,7 +130,7 @@ def main():
     print(f"frames: {n_all}, reference frames: {n_ref}, frames matched against a reference: {n_matched_frames}, "
           f"matches/matched frame: {n_matches / max(n_matched_frames, 1):.1f}")
     if args.initialize:
-        print(f"initialisations: {n_init}")
+        print(f"initialisations: {n_init}" + (f", initial maps kept: {n_maps}" if args.map else ""))
     ex.close()
 
 

@@ -114,6 +114,12 @@ int orbfe_device_download(void* h_dst, const void* d_src, size_t bytes);
  *   local bundle adj.   at most 64 free and 256 keyframes in all, 65 535 points and 262 140 edges per problem, 65 535 problems per
  *                       launch (the ORBFE_LBA_MAX_* constants, each with its reason; pinned by tests/test_lba_cpu.py and
  *                       tests/test_lba_gpu.py)
+ *   bundle adjustment   the limits of the local bundle adjustment, and 1 .. 20 iterations (ORBFE_BA_MAX_ITERATIONS, with its reason;
+ *                       orbfe_bundle_adjustment, orbfe_bundle_adjustment_batch_device; pinned by tests/test_ba_cpu.py and
+ *                       tests/test_ba_gpu.py)
+ *   initial map         at most 4 096 keypoints a frame (ORBFE_INIT_MAX_MATCHES) and 65 535 problems per launch, 1 .. 20 iterations,
+ *                       q >= 1, min_points >= 0 (orbfe_create_initial_map, orbfe_create_initial_map_batch_device; pinned by
+ *                       tests/test_ba_cpu.py and tests/test_ba_gpu.py)
  *   keyframe database   at most 4 096 words per vector, 65 535 queries per call, 4 194 304 adds between two clears, Q x slots and
  *                       Q x cand_cap <= 67 108 864 (the ORBFE_KFDB_* constants, each with its reason; pinned by
  *                       tests/test_kfdb_cpu.py)
@@ -974,6 +980,56 @@ int orbfe_local_bundle_adjustment_batch_device(int P, const orbfe_pose_camera* d
                                                float* d_poses_out, float* d_points_out, uint8_t* d_erase, orbfe_lba_result* d_result,
                                                void* d_workspace, size_t workspace_bytes, void* stream);
 
+/* ---- Optimizer::BundleAdjustment (L/src/Optimizer.cc:43-231) -----------------------------------------------------------------------
+ * The full bundle adjustment behind GlobalBundleAdjustemnt: the call of Tracking::CreateInitialMapMonocular (20 iterations, robust)
+ * and of LoopClosing::RunGlobalBundleAdjustment (10 iterations, not robust).  The same graph as the local bundle adjustment above --
+ * its vertices, its two edge types, its records (orbfe_lba_edge, orbfe_lba_problem), its edge order, its workspace
+ * (orbfe_lba_workspace_bytes), its arithmetic (csrc/lba_internal.h) and its one workgroup per problem (csrc/lba_optimize.h) -- under
+ * another schedule: ONE optimize(n_iterations), the Huber kernel on every edge iff ORBFE_BA_ROBUST; no classification of the edges,
+ * no second round, no erase list.  The Huber delta of a monocular edge is (float)sqrt(5.99) here (:82), where the local bundle
+ * adjustment has (float)sqrt(5.991); the stereo delta is (float)sqrt(7.815) in both.  fixed[k] != 0 for the keyframe with mnId == 0.
+ * A point without an edge is left out of the graph and keeps its bytes.  EVERY keyframe comes back as
+ * Converter::toCvMat(SE3Quat) rounds its estimate (:189-203) -- a fixed one and a free one without an edge: the pose that went in,
+ * through the quaternion and back.
+ * Not taken over: the stop flag is not read while the launch runs.
+ * Deterministic: no atomics; a problem's bytes depend on its own rows only, not on P or on its place in the batch.  No CPU fallback.
+ * Limits, each refused with ORBFE_ERR_INVALID one step past it (pinned by tests/test_ba_cpu.py and tests/test_ba_gpu.py): the
+ * ORBFE_LBA_MAX_* of the kernel it shares, and
+ *   ORBFE_BA_MAX_ITERATIONS  20 iterations: the most a caller of the reference asks for (Tracking: 20, LoopClosing: 10, the default
+ *                            5).  A launch cannot be interrupted and an iteration runs up to ten trials, so the cap is what bounds
+ *                            a launch.  Measured: 9 ms per trial at 8 016 edges and 20 free keyframes, 4 ms per trial at the 7 194
+ *                            edges of a two-keyframe map at the initialiser's cap (profiles/local_bundle_adjustment.md,
+ *                            profiles/initial_map.md), i.e. 0.1 s and at worst 1 s for 20 iterations there.  NOT measured: a trial
+ *                            at the largest problem the limits admit (262 140 edges, 64 free keyframes); by operation count it is
+ *                            about a hundred times the first figure, so 20 iterations there are tens of seconds and at worst
+ *                            minutes.  A larger cap would admit nothing the reference asks for and multiply that */
+#define ORBFE_BA_MAX_ITERATIONS 20
+#define ORBFE_BA_ROBUST 1                 /* flags: the reference's bRobust -- a Huber kernel on every edge */
+typedef struct orbfe_ba_result {          /* 40 bytes, 8-byte aligned */
+  int32_t rounds;                         /* 1: optimize() ran; 0: no free keyframe or no edge; -1: refused on the device */
+  int32_t n_free, n_edges;
+  int32_t iterations, trials;             /* Levenberg iterations and trials (reported, not part of parity) */
+  int32_t reserved;
+  double chi2_first, chi2_final;          /* activeRobustChi2 at the start and at the end */
+} orbfe_ba_result;
+/* One problem.  HOST pointers, synchronous, on the calling thread's current device; arguments as orbfe_local_bundle_adjustment's
+ * (edges in any order, sorted here; the same pair twice is refused).  A problem without a free keyframe or without an edge returns
+ * its inputs, rounds = 0.  One upload, one launch, one download; the workspace is allocated for the call.
+ * Limits (ORBFE_ERR_INVALID): as orbfe_local_bundle_adjustment, 1 <= n_iterations <= ORBFE_BA_MAX_ITERATIONS, flags outside
+ * ORBFE_BA_ROBUST. */
+int orbfe_bundle_adjustment(const orbfe_pose_camera* camera, const float* poses, const uint8_t* fixed, int n_kf, const float* points,
+                            int n_points, const orbfe_lba_edge* edges, int n_edges, int n_iterations, int flags, float* poses_out,
+                            float* points_out, orbfe_ba_result* result);
+/* P problems in one launch, one workgroup each.  DEVICE pointers, asynchronous on `stream` (NULL: the NULL stream).  Layout, refusal
+ * of a problem by its workgroup (rounds = -1, poses and points copied through, no other problem touched) and workspace as
+ * orbfe_local_bundle_adjustment_batch_device; n_iterations and flags hold for every problem.
+ * Limits (ORBFE_ERR_INVALID): as that call, 1 <= n_iterations <= ORBFE_BA_MAX_ITERATIONS, flags outside ORBFE_BA_ROBUST. */
+int orbfe_bundle_adjustment_batch_device(int P, const orbfe_pose_camera* d_camera, const orbfe_lba_problem* d_problems,
+                                         const float* d_poses, const uint8_t* d_fixed, const uint8_t* d_points, int point_stride,
+                                         const orbfe_lba_edge* d_edges, int kf_cap, int point_cap, int edge_cap, int n_iterations,
+                                         int flags, float* d_poses_out, float* d_points_out, orbfe_ba_result* d_result,
+                                         void* d_workspace, size_t workspace_bytes, void* stream);
+
 /* ---- KeyFrameDatabase (L/src/KeyFrameDatabase.cc, D/src/ScoringObject.cpp: L1) -----------------------------------------------------
  * The first step of both place-recognition chains: DetectRelocalizationCandidates in front of orbfe_search_by_bow .. the pose
  * optimisation, DetectLoopCandidates in front of orbfe_search_by_bow_kf .. orbfe_optimize_sim3.  The handle keeps the BoW vectors
@@ -1606,6 +1662,69 @@ int orbfe_initializer_initialize_batch_device(int P, const orbfe_init_params* d_
                                               float* d_P3D, uint64_t* d_triangulated, uint64_t* d_inlier_words,
                                               orbfe_init_hypothesis* d_hyps, uint64_t* d_words, orbfe_init_candidate* d_candidates,
                                               void* d_workspace, size_t workspace_bytes, void* stream);
+
+/* ---- Tracking::CreateInitialMapMonocular (L/src/Tracking.cc:546-666) -----------------------------------------------------------------
+ * From the outputs of the initialiser above to a first map at the scale the rest of the system works in, in three launches without a
+ * host round trip:
+ *   build    Tracking.cc:551-556, :584-612: every match i with matches12[i] in [0, n2) and vbTriangulated[i] becomes a map point at
+ *            P3D[i], in order of i (its place is the popcount prefix over the words), with two monocular observations: keypoint i of
+ *            the initial keyframe (pose1, id 0, fixed) and keypoint matches12[i] of the current one (pose [R21 | t21], free)
+ *   adjust   GlobalBundleAdjustemnt(map, n_iterations): ba_kernel above, robust
+ *   finish   :620-642: z = Rcw2.dot(x) + zcw of every point in the initial keyframe as a float (cv::Mat::dot accumulates in double in
+ *            element order, the sum with zcw is a double, rounded once -- this project's restatement); the depths
+ *            sorted, the element at (n - 1) / q; a reset if that median is < 0 or fewer than min_points keypoints of the current
+ *            keyframe hold a point (TrackedMapPoints(1)); otherwise the current translation and every point times 1.0f / median
+ * Defined where the reference is not: without any point the reference indexes an empty vector -- here a reset with
+ * ORBFE_IMAP_NO_POINTS and median_depth 0; a NaN depth sorts last (std::sort is undefined on it), -0 before +0; a median of 0 is no
+ * reset and scales by 1.0f / 0 as the float arithmetic has it.  On a reset poses and points are the adjustment's, unscaled.
+ * Not taken over: ComputeBoW, the map bookkeeping of :573-612 and :644-665, UpdateNormalAndDepth inside the adjustment
+ * (orbfe_refresh_map_points), the stop flag.
+ * Deterministic: no atomics; a problem's bytes do not depend on P or on its place in the batch.  No CPU fallback.
+ * Limits: ORBFE_INIT_MAX_MATCHES keypoints a frame, ORBFE_LBA_MAX_PROBLEMS problems, 1 <= n_iterations <= ORBFE_BA_MAX_ITERATIONS. */
+#define ORBFE_IMAP_MEDIAN_NEGATIVE 1     /* reason bits: medianDepth < 0 */
+#define ORBFE_IMAP_FEW_POINTS 2          /* TrackedMapPoints(1) < min_points */
+#define ORBFE_IMAP_NO_POINTS 4           /* no match was triangulated */
+#define ORBFE_IMAP_REFUSED 8             /* an octave outside the camera's levels: the adjustment refused the problem (ba.rounds = -1) */
+typedef struct orbfe_initial_map_result { /* 72 bytes, 8-byte aligned */
+  int32_t n_points;                      /* map points = entries of the index list */
+  int32_t tracked;                       /* keypoints of the current keyframe that hold a point */
+  float median_depth;                    /* before the rescale; 0 without a point */
+  int32_t success;                       /* 1: the map stands and is scaled; 0: Tracking resets */
+  int32_t reason;                        /* ORBFE_IMAP_* bits, 0 on success */
+  int32_t reserved[3];
+  orbfe_ba_result ba;                    /* of the adjustment */
+} orbfe_initial_map_result;
+/* One problem on host arrays, synchronous: one packed upload, three launches, one packed download.  camera: fx fy cx cy, n_levels
+ * and inv_level_sigma2 are read; keys1[n1][2], keys2[n2][2], matches12[n1], P3D[n1][3], triangulated[ceil(n1 / 64)] and init (R21, t21
+ * are read) as orbfe_initializer_initialize takes and leaves them; octaves1[n1] / octaves2[n2]: the octave of every keypoint;
+ * pose1[12]: the initial keyframe's [R | t], NULL for Tracking's identity; q and min_points: Tracking's 2 and 100.
+ * Outputs: poses[2][12]; points[n1][3] in match-index order, zero rows where there is no point; index[n1]: the first n_points
+ * entries are the matches that became points, the rest -1; poses_ba / points_ba (NULL to skip): the same two arrays before the
+ * rescale; *result.
+ * Limits (ORBFE_ERR_INVALID): 0 <= n1, n2 <= ORBFE_INIT_MAX_MATCHES, 1 <= n_iterations <= ORBFE_BA_MAX_ITERATIONS, q >= 1, min_points
+ * >= 0, matches12[i] < n2, an octave of a keypoint that is used outside [0, n_levels), null pointers. */
+int orbfe_create_initial_map(const orbfe_pose_camera* camera, const float* keys1, int n1, const float* keys2, int n2,
+                             const int32_t* matches12, const float* P3D, const uint64_t* triangulated, const orbfe_init_result* init,
+                             const int32_t* octaves1, const int32_t* octaves2, const float* pose1, int n_iterations, int q,
+                             int min_points, float* poses, float* points, int32_t* index, float* poses_ba, float* points_ba,
+                             orbfe_initial_map_result* result);
+/* Bytes of the workspace of orbfe_create_initial_map_batch_device for P problems of at most `cap` keypoints a frame.
+ * Limits (ORBFE_ERR_INVALID): 0 <= P <= ORBFE_LBA_MAX_PROBLEMS, 1 <= cap <= ORBFE_INIT_MAX_MATCHES, bytes != NULL. */
+int orbfe_initial_map_workspace_bytes(int P, int cap, size_t* bytes);
+/* P problems from device memory on `stream` (NULL: the NULL stream), asynchronous.  d_keys1 .. d_init lie exactly as
+ * orbfe_initializer_initialize_batch_device reads and writes them ([P][cap][2], [P], [P][cap], [P][cap][3], [P][ceil(cap / 64)],
+ * [P]), so the two calls chain on one stream; d_octaves1 / d_octaves2 [P][cap]; d_pose1 [P][12] or NULL; one camera for all.
+ * Outputs: d_poses [P][2][12], d_points [P][cap][3] and d_index [P][cap] (rows below n1 are written), d_poses_ba / d_points_ba the
+ * same or NULL, d_result [P].  A problem with an octave outside the camera's levels is a reset with ORBFE_IMAP_REFUSED.
+ * Limits (ORBFE_ERR_INVALID): as above, workspace_bytes below orbfe_initial_map_workspace_bytes(P, cap), a workspace not 256-byte
+ * aligned, null pointers, pointers not 4-byte (words, d_result: 8-byte) aligned. */
+int orbfe_create_initial_map_batch_device(int P, const orbfe_pose_camera* d_camera, const float* d_keys1, const int32_t* d_n1,
+                                          const float* d_keys2, const int32_t* d_n2, int cap, const int32_t* d_matches12,
+                                          const float* d_P3D, const uint64_t* d_triangulated, const orbfe_init_result* d_init,
+                                          const int32_t* d_octaves1, const int32_t* d_octaves2, const float* d_pose1, int n_iterations,
+                                          int q, int min_points, float* d_poses, float* d_points, int32_t* d_index, float* d_poses_ba,
+                                          float* d_points_ba, orbfe_initial_map_result* d_result, void* d_workspace,
+                                          size_t workspace_bytes, void* stream);
 
 /* --------------------------------------------------------------------------------------- sequence driver helpers */
 /* Dependency-free PNG input for the dataset drivers (the reference reads with cv::imread(..., IMREAD_UNCHANGED),

@@ -152,6 +152,17 @@ assert LBA_EDGE_DTYPE.itemsize == 24 and LBA_PROBLEM_DTYPE.itemsize == 24 and LB
 LBA_MAX_FREE, LBA_MAX_KEYFRAMES, LBA_MAX_POINTS, LBA_MAX_EDGES, LBA_MAX_PROBLEMS = 64, 256, 65535, 262140, 65535
 LBA_FIRST_ROUND_ONLY = 1
 LBA_ERASE, LBA_DROPPED = 1, 2
+# orbfe_ba_result and the ORBFE_BA_* constants (Optimizer::BundleAdjustment, include/orbfe.h)
+BA_RESULT_DTYPE = np.dtype([("rounds", "<i4"), ("n_free", "<i4"), ("n_edges", "<i4"), ("iterations", "<i4"), ("trials", "<i4"),
+                            ("reserved", "<i4"), ("chi2_first", "<f8"), ("chi2_final", "<f8")])
+assert BA_RESULT_DTYPE.itemsize == 40
+BA_MAX_ITERATIONS = 20
+BA_ROBUST = 1
+# orbfe_initial_map_result and the ORBFE_IMAP_* reason bits (Tracking::CreateInitialMapMonocular, include/orbfe.h)
+INITIAL_MAP_RESULT_DTYPE = np.dtype([("n_points", "<i4"), ("tracked", "<i4"), ("median_depth", "<f4"), ("success", "<i4"), ("reason", "<i4"),
+                                     ("reserved", "<i4", (3,)), ("ba", BA_RESULT_DTYPE)])
+assert INITIAL_MAP_RESULT_DTYPE.itemsize == 72
+IMAP_MEDIAN_NEGATIVE, IMAP_FEW_POINTS, IMAP_NO_POINTS, IMAP_REFUSED = 1, 2, 4, 8
 # orbfe_kfdb_query_info and the ORBFE_KFDB_* limits (KeyFrameDatabase, include/orbfe.h)
 KFDB_INFO_DTYPE = np.dtype([("n_sharing", "<i4"), ("max_common_words", "<i4"), ("min_common_words", "<i4"), ("n_scored", "<i4"),
                             ("n_matches", "<i4"), ("best_acc_score", "<f4"), ("min_score_to_retain", "<f4"), ("n_candidates", "<i4")])
@@ -238,12 +249,14 @@ EXPORTS = [
     "orbfe_sim3_ransac_iterations", "orbfe_sim3_solve", "orbfe_sim3_solve_batch_device",
     "orbfe_optimize_sim3", "orbfe_optimize_sim3_batch_device",
     "orbfe_local_bundle_adjustment", "orbfe_lba_workspace_bytes", "orbfe_local_bundle_adjustment_batch_device",
+    "orbfe_bundle_adjustment", "orbfe_bundle_adjustment_batch_device",
     "orbfe_kfdb_create", "orbfe_kfdb_destroy", "orbfe_kfdb_clear", "orbfe_kfdb_size", "orbfe_kfdb_slots", "orbfe_kfdb_add", "orbfe_kfdb_erase",
     "orbfe_kfdb_set_covisibles", "orbfe_kfdb_score", "orbfe_kfdb_detect_relocalization", "orbfe_kfdb_detect_loop",
     "orbfe_kfdb_detect_relocalization_device", "orbfe_kfdb_detect_loop_device", "orbfe_debug_kfdb_arrangement",
     "orbfe_refresh_map_points", "orbfe_refresh_map_points_batch_device",
     "orbfe_covis_count", "orbfe_covis_count_batch_device", "orbfe_covis_cull_keyframes", "orbfe_covis_cull_keyframes_batch_device",
     "orbfe_initializer_initialize", "orbfe_initializer_workspace_bytes", "orbfe_initializer_initialize_batch_device",
+    "orbfe_create_initial_map", "orbfe_initial_map_workspace_bytes", "orbfe_create_initial_map_batch_device",
 ]
 
 
@@ -362,6 +375,8 @@ def lib():
     L.orbfe_local_bundle_adjustment.argtypes = [vp, vp, vp, ci, vp, ci, vp, ci, ci, vp, vp, vp, vp]
     L.orbfe_lba_workspace_bytes.argtypes = [ci, ci, ci, ci, C.POINTER(sz)]
     L.orbfe_local_bundle_adjustment_batch_device.argtypes = [ci, vp, vp, vp, vp, vp, ci, vp, ci, ci, ci, ci, vp, vp, vp, vp, vp, sz, vp]
+    L.orbfe_bundle_adjustment.argtypes = [vp, vp, vp, ci, vp, ci, vp, ci, ci, ci, vp, vp, vp]
+    L.orbfe_bundle_adjustment_batch_device.argtypes = [ci, vp, vp, vp, vp, vp, ci, vp, ci, ci, ci, ci, ci, vp, vp, vp, vp, sz, vp]
     i64 = C.c_int64
     L.orbfe_kfdb_create.argtypes = [ci, ci, ci, C.POINTER(vp)]
     L.orbfe_debug_kfdb_arrangement.argtypes = [ci]
@@ -386,6 +401,10 @@ def lib():
     L.orbfe_initializer_initialize.argtypes = [vp, vp, ci, vp, ci, vp, vp, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.orbfe_initializer_workspace_bytes.argtypes = [ci, ci, C.POINTER(sz)]
     L.orbfe_initializer_initialize_batch_device.argtypes = [ci, vp, vp, vp, vp, vp, ci, vp, vp, vp, ci, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]
+    L.orbfe_create_initial_map.argtypes = [vp, vp, ci, vp, ci, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, vp, vp, vp, vp, vp, vp]
+    L.orbfe_initial_map_workspace_bytes.argtypes = [ci, ci, C.POINTER(sz)]
+    L.orbfe_create_initial_map_batch_device.argtypes = [ci, vp, vp, vp, vp, vp, ci, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, vp, vp, vp, vp, vp,
+                                                        vp, vp, sz, vp]
     for name in EXPORTS:
         if name != "orbfe_last_error":
             getattr(L, name).restype = ci

@@ -1,5 +1,5 @@
-// Optimizer_hip.h -- host-side adapters that put ORB_SLAM2::Optimizer::PoseOptimization, Optimizer::OptimizeSim3 and
-// Optimizer::LocalBundleAdjustment on liborbfe.
+// Optimizer_hip.h -- host-side adapters that put ORB_SLAM2::Optimizer::PoseOptimization, Optimizer::OptimizeSim3,
+// Optimizer::LocalBundleAdjustment and Optimizer::BundleAdjustment / GlobalBundleAdjustemnt on liborbfe.
 //
 // The reference's function (Source/Libraries/ORB_SLAM2/src/Optimizer.cc:233-435) builds a g2o graph of one pose vertex and one
 // unary edge per keypoint with a map point, optimises it and writes the pose and the outlier flags back into the Frame.  This
@@ -24,6 +24,14 @@
 //   MapPoint: mnBALocalForKF, isBad(), GetObservations(), GetWorldPos(), SetWorldPos(cv::Mat), UpdateNormalAndDepth(),
 //             EraseObservation(KeyFrame*)
 //   Map:      mMutexMapUpdate
+//
+// BundleAdjustment and GlobalBundleAdjustemnt (Optimizer.cc:43-231) are the adapters for orbfe_bundle_adjustment, with the
+// reference's signatures, unit-tested by tests/cpp_ba.  Members used beyond the above:
+//   KeyFrame: mTcwGBA, mnBAGlobalForKF
+//   MapPoint: mPosGBA, mnBAGlobalForKF
+//   Map:      GetAllKeyFrames(), GetAllMapPoints()
+// AdjustAndScaleInitialMap is Tracking.cc:618-642 -- the adjustment of the two-keyframe map, the median depth, the reset rule and the
+// rescale -- on orbfe_create_initial_map.  Members used beyond the above: KeyFrame::N, MapPoint::GetIndexInKeyFrame(KeyFrame*).
 #pragma once
 #include <stdio.h>
 #include <string.h>
@@ -338,6 +346,230 @@ void LocalBundleAdjustment(KeyFrameT* pKF, bool* pbStopFlag, MapT* pMap) {
     return;
   }
   LocalBundleAdjustmentApply(B, poses_out.data(), points_out.data(), erase.data(), pMap);
+}
+
+// What Optimizer::BundleAdjustment collects before it optimises (Optimizer.cc:70-181), as the library's arguments.  Keyframe rows:
+// the keyframes of vpKFs that are not bad, in vector order; point rows: the map points of vpMP that are not bad, in vector order --
+// included[p] == 0 for one without an edge, which the reference removes from the graph again; edges point by point in the order of
+// the reference's addEdge calls, i.e. of the point's own std::map<KeyFrame*, size_t> (the library sorts them by keyframe row).
+template <class KeyFrameT, class MapPointT>
+struct GlobalBAProblem {
+  std::vector<KeyFrameT*> vpKF;
+  std::vector<MapPointT*> vpMP;
+  std::vector<uint8_t> included;
+  std::vector<float> poses, points;
+  std::vector<uint8_t> fixed;
+  std::vector<orbfe_lba_edge> edges;
+  long unsigned int maxKFid = 0;
+  orbfe_pose_camera cam;
+};
+
+template <class KeyFrameT, class MapPointT>
+void BundleAdjustmentMarshal(const std::vector<KeyFrameT*>& vpKFs, const std::vector<MapPointT*>& vpMP,
+                             GlobalBAProblem<KeyFrameT, MapPointT>& B) {
+  memset(&B.cam, 0, sizeof(B.cam));
+  std::map<KeyFrameT*, int32_t> row;
+  for (KeyFrameT* pKF : vpKFs) {   // :74-85
+    if (pKF->isBad()) continue;
+    if (B.vpKF.empty()) {
+      B.cam.fx = pKF->fx;
+      B.cam.fy = pKF->fy;
+      B.cam.cx = pKF->cx;
+      B.cam.cy = pKF->cy;
+      B.cam.mbf = pKF->mbf;
+    }
+    const cv::Mat T = pKF->GetPose();
+    for (int r = 0; r < 3; r++)
+      for (int c = 0; c < 4; c++) B.poses.push_back(T.template at<float>(r, c));
+    row[pKF] = (int32_t)B.vpKF.size();
+    B.vpKF.push_back(pKF);
+    B.fixed.push_back(pKF->mnId == 0 ? 1 : 0);
+    if (pKF->mnId > B.maxKFid) B.maxKFid = pKF->mnId;
+  }
+  for (MapPointT* pMP : vpMP) {   // :91-181
+    if (pMP->isBad()) continue;
+    const int32_t p = (int32_t)B.vpMP.size();
+    const cv::Mat Xw = pMP->GetWorldPos();
+    for (int r = 0; r < 3; r++) B.points.push_back(Xw.template at<float>(r));
+    B.vpMP.push_back(pMP);
+    const auto observations = pMP->GetObservations();
+    int nEdges = 0;
+    for (auto mit = observations.begin(), mend = observations.end(); mit != mend; mit++) {
+      KeyFrameT* pKF = mit->first;
+      if (pKF->isBad() || pKF->mnId > B.maxKFid) continue;
+      const auto it = row.find(pKF);
+      if (it == row.end()) continue;   // not among vpKFs: the reference has no vertex for it
+      nEdges++;
+      const auto& kpUn = pKF->mvKeysUn[mit->second];
+      orbfe_lba_edge e;
+      e.kf = it->second;
+      e.point = p;
+      e.u = kpUn.pt.x;
+      e.v = kpUn.pt.y;
+      const float kp_ur = pKF->mvuRight[mit->second];
+      e.u_right = kp_ur < 0 ? -1.0f : kp_ur;
+      e.inv_sigma2 = pKF->mvInvLevelSigma2[kpUn.octave];
+      B.edges.push_back(e);
+    }
+    B.included.push_back(nEdges > 0 ? 1 : 0);
+  }
+}
+
+// "Recover optimized data" (:184-230) for a problem B and the library's outputs for it: into the map when nLoopKF == 0, beside it
+// (mTcwGBA / mPosGBA / mnBAGlobalForKF) otherwise.  Every keyframe of the problem is written, the fixed one too, as the reference does
+template <class KeyFrameT, class MapPointT>
+void BundleAdjustmentApply(GlobalBAProblem<KeyFrameT, MapPointT>& B, const float* poses_out, const float* points_out,
+                           const unsigned long nLoopKF) {
+  for (size_t k = 0; k < B.vpKF.size(); k++) {
+    KeyFrameT* pKF = B.vpKF[k];
+    if (pKF->isBad()) continue;
+    cv::Mat pose = cv::Mat::eye(4, 4, CV_32F);
+    for (int r = 0; r < 3; r++)
+      for (int c = 0; c < 4; c++) pose.template at<float>(r, c) = poses_out[12 * k + 4 * r + c];
+    if (nLoopKF == 0) {
+      pKF->SetPose(pose);
+    } else {
+      pKF->mTcwGBA = pose;
+      pKF->mnBAGlobalForKF = nLoopKF;
+    }
+  }
+  for (size_t p = 0; p < B.vpMP.size(); p++) {
+    if (!B.included[p]) continue;
+    MapPointT* pMP = B.vpMP[p];
+    if (pMP->isBad()) continue;
+    cv::Mat X(3, 1, CV_32F);
+    for (int r = 0; r < 3; r++) X.template at<float>(r) = points_out[3 * p + r];
+    if (nLoopKF == 0) {
+      pMP->SetWorldPos(X);
+      pMP->UpdateNormalAndDepth();
+    } else {
+      pMP->mPosGBA = X;
+      pMP->mnBAGlobalForKF = nLoopKF;
+    }
+  }
+}
+
+// void Optimizer::BundleAdjustment(const vector<KeyFrame*>&, const vector<MapPoint*>&, int nIterations = 5, bool* pbStopFlag = NULL,
+// const unsigned long nLoopKF = 0, const bool bRobust = true).  The stop flag is read before the one library call, not while it runs
+// (INTEGRATION.md): found set on entry, nothing is done.  Errors (no device, a map beyond the library's limits) are logged and leave
+// the map untouched.  There is no CPU fallback.
+template <class KeyFrameT, class MapPointT>
+void BundleAdjustment(const std::vector<KeyFrameT*>& vpKFs, const std::vector<MapPointT*>& vpMP, int nIterations = 5,
+                      bool* pbStopFlag = NULL, const unsigned long nLoopKF = 0, const bool bRobust = true) {
+  if (pbStopFlag)
+    if (*pbStopFlag) return;
+  GlobalBAProblem<KeyFrameT, MapPointT> B;
+  BundleAdjustmentMarshal(vpKFs, vpMP, B);
+  const int n_kf = (int)B.vpKF.size(), n_points = (int)B.vpMP.size(), n_edges = (int)B.edges.size();
+  std::vector<float> poses_out(B.poses.size()), points_out(B.points.size());
+  orbfe_ba_result res;
+  const int rc = orbfe_bundle_adjustment(&B.cam, B.poses.data(), B.fixed.data(), n_kf, B.points.data(), n_points, B.edges.data(), n_edges,
+                                         nIterations, bRobust ? ORBFE_BA_ROBUST : 0, poses_out.data(), points_out.data(), &res);
+  if (rc != ORBFE_OK) {
+    fprintf(stderr, "orbfe BundleAdjustment: %s (code %d)\n", orbfe_last_error(), rc);
+    return;
+  }
+  BundleAdjustmentApply(B, poses_out.data(), points_out.data(), nLoopKF);
+}
+
+// void Optimizer::GlobalBundleAdjustemnt(Map* pMap, int nIterations = 5, bool* pbStopFlag = NULL, const unsigned long nLoopKF = 0,
+// const bool bRobust = true)
+template <class MapT>
+void GlobalBundleAdjustemnt(MapT* pMap, int nIterations = 5, bool* pbStopFlag = NULL, const unsigned long nLoopKF = 0,
+                            const bool bRobust = true) {
+  const auto vpKFs = pMap->GetAllKeyFrames();
+  const auto vpMP = pMap->GetAllMapPoints();
+  BundleAdjustment(vpKFs, vpMP, nIterations, pbStopFlag, nLoopKF, bRobust);
+}
+
+// Tracking.cc:618-642 for the two keyframes of CreateInitialMapMonocular, after the map points were created (:584-612): the global
+// bundle adjustment of nIterations, the median depth of the scene in pKFini, the reset rule and the rescale, in ONE library call
+// (orbfe_create_initial_map; nothing of it is computed here).  Returns false where Tracking resets ("Wrong initialization"); the
+// poses and points are then the adjustment's, as in the reference.  The adjustment's values are written with SetPose / SetWorldPos +
+// UpdateNormalAndDepth, the rescaled ones with SetPose / SetWorldPos alone, as :636-642 do.  Errors are logged, leave the map
+// untouched and return false.  *result (may be NULL) receives the library's record.
+template <class KeyFrameT>
+bool AdjustAndScaleInitialMap(KeyFrameT* pKFini, KeyFrameT* pKFcur, int nIterations = 20, orbfe_initial_map_result* result = NULL) {
+  using MapPointT = std::remove_pointer_t<typename decltype(pKFini->GetMapPointMatches())::value_type>;
+  const std::vector<MapPointT*> vpMP = pKFini->GetMapPointMatches();
+  const int n1 = pKFini->N, n2 = pKFcur->N, nw = (n1 + 63) / 64;
+  std::vector<float> keys1((size_t)2 * n1), keys2((size_t)2 * n2), P3D((size_t)3 * n1, 0.0f);
+  std::vector<int32_t> oct1(n1), oct2(n2), matches12(n1, -1);
+  std::vector<uint64_t> tri(nw > 0 ? nw : 1, 0);
+  for (int i = 0; i < n1; i++) {
+    keys1[2 * i] = pKFini->mvKeysUn[i].pt.x;
+    keys1[2 * i + 1] = pKFini->mvKeysUn[i].pt.y;
+    oct1[i] = pKFini->mvKeysUn[i].octave;
+  }
+  for (int j = 0; j < n2; j++) {
+    keys2[2 * j] = pKFcur->mvKeysUn[j].pt.x;
+    keys2[2 * j + 1] = pKFcur->mvKeysUn[j].pt.y;
+    oct2[j] = pKFcur->mvKeysUn[j].octave;
+  }
+  for (int i = 0; i < n1 && i < (int)vpMP.size(); i++) {
+    MapPointT* pMP = vpMP[i];
+    if (!pMP) continue;
+    const int j = pMP->GetIndexInKeyFrame(pKFcur);
+    if (j < 0) continue;
+    matches12[i] = j;
+    tri[i >> 6] |= 1ull << (i & 63);
+    const cv::Mat Xw = pMP->GetWorldPos();
+    for (int r = 0; r < 3; r++) P3D[3 * i + r] = Xw.template at<float>(r);
+  }
+  orbfe_pose_camera cam;
+  memset(&cam, 0, sizeof(cam));
+  cam.fx = pKFini->fx;
+  cam.fy = pKFini->fy;
+  cam.cx = pKFini->cx;
+  cam.cy = pKFini->cy;
+  cam.mbf = pKFini->mbf;
+  cam.n_levels = (int32_t)pKFini->mvInvLevelSigma2.size();
+  for (int l = 0; l < cam.n_levels && l < ORBFE_MAX_LEVELS; l++) cam.inv_level_sigma2[l] = pKFini->mvInvLevelSigma2[l];
+  orbfe_init_result init;
+  memset(&init, 0, sizeof(init));
+  float pose1[12];
+  const cv::Mat T1 = pKFini->GetPose(), T2 = pKFcur->GetPose();
+  for (int r = 0; r < 3; r++) {
+    for (int c = 0; c < 4; c++) pose1[4 * r + c] = T1.template at<float>(r, c);
+    for (int c = 0; c < 3; c++) init.R21[3 * r + c] = T2.template at<float>(r, c);
+    init.t21[r] = T2.template at<float>(r, 3);
+  }
+  std::vector<float> points((size_t)3 * n1), points_ba((size_t)3 * n1);
+  std::vector<int32_t> index(n1 > 0 ? n1 : 1);
+  float poses[24], poses_ba[24];
+  orbfe_initial_map_result res;
+  const int rc = orbfe_create_initial_map(&cam, keys1.data(), n1, keys2.data(), n2, matches12.data(), P3D.data(), tri.data(), &init, oct1.data(),
+                                          oct2.data(), pose1, nIterations, 2, 100, poses, points.data(), index.data(), poses_ba,
+                                          points_ba.data(), &res);
+  if (rc != ORBFE_OK) {
+    fprintf(stderr, "orbfe AdjustAndScaleInitialMap: %s (code %d)\n", orbfe_last_error(), rc);
+    return false;
+  }
+  if (result) *result = res;
+  auto pose_of = [](const float* T) {
+    cv::Mat pose = cv::Mat::eye(4, 4, CV_32F);
+    for (int r = 0; r < 3; r++)
+      for (int c = 0; c < 4; c++) pose.template at<float>(r, c) = T[4 * r + c];
+    return pose;
+  };
+  auto point_of = [](const float* X) {
+    cv::Mat x(3, 1, CV_32F);
+    for (int r = 0; r < 3; r++) x.template at<float>(r) = X[r];
+    return x;
+  };
+  if (res.ba.rounds > 0) {   // GlobalBundleAdjustemnt(mpMap, 20)
+    pKFini->SetPose(pose_of(poses_ba));
+    pKFcur->SetPose(pose_of(poses_ba + 12));
+    for (int k = 0; k < res.n_points; k++) {
+      MapPointT* pMP = vpMP[index[k]];
+      pMP->SetWorldPos(point_of(points_ba.data() + 3 * index[k]));
+      pMP->UpdateNormalAndDepth();
+    }
+  }
+  if (!res.success) return false;   // :623
+  pKFcur->SetPose(pose_of(poses + 12));   // :630-633
+  for (int k = 0; k < res.n_points; k++) vpMP[index[k]]->SetWorldPos(point_of(points.data() + 3 * index[k]));   // :636-642
+  return true;
 }
 
 }  // namespace orbfe_host

@@ -26,6 +26,9 @@
 constexpr int LBA_EKF = 27;   // per edge: the 21 upper entries and the 6 of b that it adds to its keyframe's block (lm_accumulate<6>)
 
 __host__ __device__ inline double lba_bound(bool stereo) { return stereo ? 7.815 : 5.991; }   // Optimizer.cc:669, :683 (doubles)
+// The Huber delta of a monocular edge in Optimizer::BundleAdjustment: (float)sqrt(5.99) (Optimizer.cc:82), where LocalBundleAdjustment
+// and PoseOptimization have (float)sqrt(5.991) = pose_delta(false).  The stereo delta is pose_delta(true) in all three
+__host__ __device__ inline double ba_delta_mono() { return (double)2.44744754f; }
 
 // One problem: its inputs and its workspace
 struct LbaWs {
@@ -177,8 +180,9 @@ __host__ __device__ inline void lba_inverse3(const double* M, double* R) {
 // ---- building the system: one point ------------------------------------------------------------------------------------------------
 // computeActiveErrors, linearizeOplus and constructQuadraticForm of the level-0 edges of point p: Hll and bl of the point, and per edge
 // its chi2, its Hpl block and what it adds to its keyframe's block.  Adds the robustified chi2 to *chi and raises *maxdiag to the
-// point's largest |Hll_jj|.  A point without a level-0 edge is not active.
-__host__ __device__ inline void lba_point_build(const LbaWs& W, int p, bool robust, double* chi, double* maxdiag) {
+// point's largest |Hll_jj|.  A point without a level-0 edge is not active.  delta_mono: the Huber delta of a monocular edge.
+__host__ __device__ inline void lba_point_build(const LbaWs& W, int p, bool robust, double* chi, double* maxdiag,
+                                                double delta_mono = pose_delta(false)) {
   const double X = W.pt[3 * p], Y = W.pt[3 * p + 1], Z = W.pt[3 * p + 2];
   double Hll[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, bl[3] = {0, 0, 0};
   bool any = false;
@@ -193,7 +197,7 @@ __host__ __device__ inline void lba_point_build(const LbaWs& W, int p, bool robu
     const double chi2 = lba_edge_error(E, W.K, P, X, Y, Z, e, &x, &y, &z);
     W.chi2[i] = chi2;
     double rho0 = chi2, rho1 = 1.0;
-    if (robust) lm_huber(chi2, pose_delta(stereo), &rho0, &rho1);
+    if (robust) lm_huber(chi2, stereo ? pose_delta(true) : delta_mono, &rho0, &rho1);
     *chi += rho0;
     lba_edge_jacobians(W.K, P, stereo, x, y, z, A, B);
     const double ow = rho1 * w;
@@ -422,7 +426,7 @@ __host__ __device__ inline void lba_pose_update(const LbaWs& W, int slot, double
 }
 
 // computeActiveErrors + activeRobustChi2 of the level-0 edges of point p at the estimates
-__host__ __device__ inline void lba_point_chi(const LbaWs& W, int p, bool robust, double* chi) {
+__host__ __device__ inline void lba_point_chi(const LbaWs& W, int p, bool robust, double* chi, double delta_mono = pose_delta(false)) {
   if (!W.pt_active[p]) return;
   const double X = W.pt[3 * p], Y = W.pt[3 * p + 1], Z = W.pt[3 * p + 2];
   for (int i = W.pt_start[p]; i < W.pt_end[p]; i++) {
@@ -432,7 +436,7 @@ __host__ __device__ inline void lba_point_chi(const LbaWs& W, int p, bool robust
     const double chi2 = lba_edge_error(E, W.K, W.pose[E.kf], X, Y, Z, e, &x, &y, &z);
     W.chi2[i] = chi2;
     double rho0 = chi2, rho1;
-    if (robust) lm_huber(chi2, pose_delta(!(E.u_right < 0)), &rho0, &rho1);
+    if (robust) lm_huber(chi2, !(E.u_right < 0) ? pose_delta(true) : delta_mono, &rho0, &rho1);
     *chi += rho0;
   }
 }
@@ -481,3 +485,21 @@ struct LbaLaunch {   // the arguments of orbfe_local_bundle_adjustment_batch_dev
   uint8_t* workspace;
 };
 void orbfe_launch_lba(const LbaLaunch& L, int P, hipStream_t s);
+
+// lba.cpp: the two entry points for either schedule of the graph.  ba: Optimizer::BundleAdjustment -- ONE optimize(n_iterations),
+// d_result / result is an orbfe_ba_result and no erase list exists (erase may be null); otherwise LocalBundleAdjustment's two rounds
+struct LbaSchedule {
+  const char* who;   // the name error messages carry
+  int n_iterations;  // read iff ba
+  int known_flags;
+  bool ba = false;
+};
+int lba_batch_entry(const LbaSchedule& S, int P, const orbfe_pose_camera* d_camera, const orbfe_lba_problem* d_problems,
+                    const float* d_poses, const uint8_t* d_fixed, const uint8_t* d_points, int point_stride, const orbfe_lba_edge* d_edges,
+                    int kf_cap, int point_cap, int edge_cap, int flags, float* d_poses_out, float* d_points_out, uint8_t* d_erase,
+                    void* d_result, void* d_workspace, size_t workspace_bytes, void* stream);
+int lba_host_entry(const LbaSchedule& S, const orbfe_pose_camera* camera, const float* poses, const uint8_t* fixed, int n_kf,
+                   const float* points, int n_points, const orbfe_lba_edge* edges, int n_edges, int flags, float* poses_out,
+                   float* points_out, uint8_t* erase, void* result);
+// ba_kernels.hip: the same arguments under Optimizer::BundleAdjustment's schedule; L.flags holds ORBFE_BA_*, L.erase and L.result are not read
+void orbfe_launch_ba(const LbaLaunch& L, int n_iterations, orbfe_ba_result* result, int P, hipStream_t s);

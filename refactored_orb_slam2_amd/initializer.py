@@ -13,9 +13,11 @@ import numpy as np
 
 from . import _lib
 from ._lib import INIT_CANDIDATE_DTYPE, INIT_HYPOTHESIS_DTYPE, INIT_PARAMS_DTYPE, INIT_RESULT_DTYPE
+from ._lib import INITIAL_MAP_RESULT_DTYPE, POSE_CAMERA_DTYPE
 
 __all__ = ["INIT_PARAMS_DTYPE", "INIT_HYPOTHESIS_DTYPE", "INIT_CANDIDATE_DTYPE", "INIT_RESULT_DTYPE", "init_params", "draw_sets",
-           "initialize", "initialize_batch", "workspace_bytes", "bits"]
+           "initialize", "initialize_batch", "workspace_bytes", "bits",
+           "INITIAL_MAP_RESULT_DTYPE", "create_initial_map", "create_initial_map_batch", "initial_map_workspace_bytes"]
 
 
 def init_params(fx, fy, cx, cy, sigma=1.0, min_parallax=1.0, min_triangulated=50) -> np.ndarray:
@@ -101,3 +103,66 @@ def initialize_batch(params, keys1, n1, keys2, n2, matches12, sets, H, result, P
         _lib.ptr(H), h_cap, _lib.ptr(result), _lib.ptr(P3D), _lib.ptr(triangulated), _lib.ptr(inlier_words), _lib.ptr(hyps), _lib.ptr(words),
         _lib.ptr(candidates), _lib.ptr(workspace), int(workspace.numel() * workspace.element_size()), _lib.stream_handle(stream)),
         "orbfe_initializer_initialize_batch_device")
+
+
+def create_initial_map(camera, keys1, keys2, matches12, P3D, triangulated, init_result, octaves1, octaves2, pose1=None, n_iterations=20,
+                       q=2, min_points=100, want_unscaled=False) -> dict:
+    """orbfe_create_initial_map: Tracking::CreateInitialMapMonocular from what initialize() returned.  camera: optimizer.pose_camera(...)
+    with the pyramid's inv_level_sigma2; keys1 / keys2 / matches12 as given to initialize(); P3D (n1, 3), triangulated (n1) bool or the
+    uint64 words, init_result: initialize()'s result record; octaves1 (n1) / octaves2 (n2): the octave of every keypoint; pose1: the
+    initial keyframe's (12) [R | t], None for the identity.  Returns a dict: result (one INITIAL_MAP_RESULT_DTYPE record), poses (2, 12),
+    points (n1, 3) in match-index order with zero rows where there is no point, index (n_points) the matches that became points, and --
+    when want_unscaled -- poses_ba / points_ba, the same before the rescale."""
+    cam = np.ascontiguousarray(camera, POSE_CAMERA_DTYPE).reshape(1)
+    k1 = np.ascontiguousarray(keys1, np.float32).reshape(-1, 2)
+    k2 = np.ascontiguousarray(keys2, np.float32).reshape(-1, 2)
+    n1, n2 = len(k1), len(k2)
+    m12 = np.ascontiguousarray(matches12, np.int32).reshape(-1)
+    p3d = np.ascontiguousarray(np.asarray(P3D, np.float32).reshape(-1, 3))
+    o1, o2 = np.ascontiguousarray(octaves1, np.int32).reshape(-1), np.ascontiguousarray(octaves2, np.int32).reshape(-1)
+    if len(m12) != n1 or len(p3d) != n1 or len(o1) != n1 or len(o2) != n2:
+        raise ValueError("matches12, P3D and octaves1 have one entry per keypoint of the initial frame, octaves2 one per keypoint of the current")
+    tri = np.asarray(triangulated)
+    if tri.dtype != np.uint64:
+        b = np.zeros(((n1 + 63) // 64) * 64, np.uint8)
+        b[:n1] = tri.astype(bool).reshape(-1)
+        tri = np.packbits(b.reshape(-1, 8), axis=1, bitorder="little").reshape(-1).view(np.uint64) if n1 else np.zeros(0, np.uint64)
+    words = np.zeros(max((n1 + 63) // 64, 1), np.uint64)
+    words[:(n1 + 63) // 64] = tri[:(n1 + 63) // 64]
+    init = np.ascontiguousarray(init_result, _lib.INIT_RESULT_DTYPE).reshape(1)
+    p1 = None if pose1 is None else np.ascontiguousarray(np.asarray(pose1, np.float32).reshape(12))
+    result = np.zeros(1, INITIAL_MAP_RESULT_DTYPE)
+    poses, points, index = np.zeros((2, 12), np.float32), np.zeros((n1, 3), np.float32), np.full(n1, -1, np.int32)
+    poses_ba = np.zeros((2, 12), np.float32) if want_unscaled else None
+    points_ba = np.zeros((n1, 3), np.float32) if want_unscaled else None
+    opt = lambda a: _lib.ptr(a) if a is not None and len(a) else None
+    _lib.check(_lib.lib().orbfe_create_initial_map(_lib.ptr(cam), opt(k1), n1, opt(k2), n2, opt(m12), opt(p3d), _lib.ptr(words), _lib.ptr(init),
+                                                   opt(o1), opt(o2), _lib.ptr(p1), int(n_iterations), int(q), int(min_points),
+                                                   _lib.ptr(poses), opt(points), opt(index), _lib.ptr(poses_ba), opt(points_ba),
+                                                   _lib.ptr(result)), "orbfe_create_initial_map")
+    return {"result": result[0], "poses": poses, "points": points, "index": index[:int(result["n_points"][0])], "poses_ba": poses_ba,
+            "points_ba": points_ba}
+
+
+def initial_map_workspace_bytes(P, cap) -> int:
+    """orbfe_initial_map_workspace_bytes"""
+    n = C.c_size_t(0)
+    _lib.check(_lib.lib().orbfe_initial_map_workspace_bytes(int(P), int(cap), C.byref(n)), "orbfe_initial_map_workspace_bytes")
+    return int(n.value)
+
+
+def create_initial_map_batch(camera, keys1, n1, keys2, n2, matches12, P3D, triangulated, init_result, octaves1, octaves2, poses, points,
+                             index, result, workspace, pose1=None, poses_ba=None, points_ba=None, n_iterations=20, q=2, min_points=100,
+                             stream=None):
+    """orbfe_create_initial_map_batch_device on torch CUDA tensors: camera (88) u8 = one POSE_CAMERA_DTYPE record; keys1 / keys2
+    (P,cap,2) f32, n1 / n2 (P) i32, matches12 (P,cap) i32, P3D (P,cap,3) f32, triangulated (P,ceil(cap/64)) i64 words and init_result
+    (P,224) u8 exactly as initialize_batch reads and writes them; octaves1 / octaves2 (P,cap) i32; pose1 (P,12) f32 or None.  Outputs:
+    poses (P,2,12) f32, points (P,cap,3) f32, index (P,cap) i32, poses_ba / points_ba the same or None, result (P,72) u8 =
+    INITIAL_MAP_RESULT_DTYPE; workspace: u8 of at least initial_map_workspace_bytes(P, cap) bytes."""
+    P, cap = int(keys1.shape[0]), int(keys1.shape[1])
+    _lib.check(_lib.lib().orbfe_create_initial_map_batch_device(
+        P, _lib.ptr(camera), _lib.ptr(keys1), _lib.ptr(n1), _lib.ptr(keys2), _lib.ptr(n2), cap, _lib.ptr(matches12), _lib.ptr(P3D),
+        _lib.ptr(triangulated), _lib.ptr(init_result), _lib.ptr(octaves1), _lib.ptr(octaves2), _lib.ptr(pose1), int(n_iterations), int(q),
+        int(min_points), _lib.ptr(poses), _lib.ptr(points), _lib.ptr(index), _lib.ptr(poses_ba), _lib.ptr(points_ba), _lib.ptr(result),
+        _lib.ptr(workspace), int(workspace.numel()) * int(workspace.element_size()), _lib.stream_handle(stream)),
+        "orbfe_create_initial_map_batch_device")

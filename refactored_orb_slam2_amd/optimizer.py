@@ -1,7 +1,8 @@
-"""Optimizer::PoseOptimization, Optimizer::OptimizeSim3 and Optimizer::LocalBundleAdjustment over the C ABI of liborbfe.so
-(L/src/Optimizer.cc:233-435, :1381-1573, :437-760, L/ = Source/Libraries/ORB_SLAM2/): the pose of a frame from its keypoint <->
-map-point pairs, and which pairs were wrong; the similarity between two keyframes of a loop candidate from their matched map points,
-and which matches were wrong; the poses of the local keyframes and the points they see, and which observations to erase.
+"""Optimizer::PoseOptimization, Optimizer::OptimizeSim3, Optimizer::LocalBundleAdjustment and Optimizer::BundleAdjustment over the C
+ABI of liborbfe.so (L/src/Optimizer.cc:233-435, :1381-1573, :437-760, :43-231, L/ = Source/Libraries/ORB_SLAM2/): the pose of a frame
+from its keypoint <-> map-point pairs, and which pairs were wrong; the similarity between two keyframes of a loop candidate from their
+matched map points, and which matches were wrong; the poses of the local keyframes and the points they see, and which observations to
+erase; the poses of all keyframes of a map and all its points.
 
 pose_optimization is the per-frame call of Tracking on host arrays; pose_optimization_batch optimises every frame of a batch in one
 launch on device tensors (pose_kernels.hip, one workgroup per frame) and reads the `assigned` array of the batched projection
@@ -12,6 +13,10 @@ a batch in one launch on device tensors (optsim3_kernels.hip, one workgroup per 
 
 local_bundle_adjustment is the call of LocalMapping::Run on host arrays; local_bundle_adjustment_batch optimises ragged problems that
 lie in device tensors in one launch (lba_kernels.hip, one workgroup per problem) with a workspace of lba_workspace_bytes(...) bytes.
+
+bundle_adjustment is the call of Tracking::CreateInitialMapMonocular (20 iterations, robust) and of
+LoopClosing::RunGlobalBundleAdjustment (10, not robust) on host arrays; bundle_adjustment_batch takes the same ragged device tensors
+and the same workspace as local_bundle_adjustment_batch (ba_kernels.hip: one optimize() call, no classification, no erase list).
 """
 from __future__ import annotations
 
@@ -20,13 +25,15 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
+from ._lib import BA_MAX_ITERATIONS, BA_RESULT_DTYPE, BA_ROBUST
 from ._lib import (LBA_DROPPED, LBA_EDGE_DTYPE, LBA_ERASE, LBA_FIRST_ROUND_ONLY, LBA_PROBLEM_DTYPE, LBA_RESULT_DTYPE)
 from ._lib import OPTSIM3_PAIR_DTYPE, OPTSIM3_RESULT_DTYPE, POSE_CAMERA_DTYPE, POSE_DISCARD, POSE_RESULT_DTYPE, SIM3_VIEW_DTYPE
 
 __all__ = ["POSE_CAMERA_DTYPE", "POSE_RESULT_DTYPE", "POSE_DISCARD", "pose_camera", "pose_optimization", "pose_optimization_batch",
            "OPTSIM3_PAIR_DTYPE", "OPTSIM3_RESULT_DTYPE", "sim3_view", "optimize_sim3", "optimize_sim3_batch",
            "LBA_EDGE_DTYPE", "LBA_PROBLEM_DTYPE", "LBA_RESULT_DTYPE", "LBA_FIRST_ROUND_ONLY", "LBA_ERASE", "LBA_DROPPED",
-           "local_bundle_adjustment", "local_bundle_adjustment_batch", "lba_workspace_bytes"]
+           "local_bundle_adjustment", "local_bundle_adjustment_batch", "lba_workspace_bytes",
+           "BA_RESULT_DTYPE", "BA_ROBUST", "BA_MAX_ITERATIONS", "bundle_adjustment", "bundle_adjustment_batch"]
 
 
 def pose_camera(fx, fy, cx, cy, mbf, inv_level_sigma2) -> np.ndarray:
@@ -164,3 +171,37 @@ def local_bundle_adjustment_batch(camera, problems, poses, fixed, points, edges,
         int(point_cap), int(edge_cap), int(flags), _lib.ptr(poses_out), _lib.ptr(points_out), _lib.ptr(erase), _lib.ptr(result),
         _lib.ptr(workspace), int(workspace.numel()) * int(workspace.element_size()), _lib.stream_handle(stream)),
         "orbfe_local_bundle_adjustment_batch_device")
+
+
+def bundle_adjustment(camera, poses, fixed, points, edges, n_iterations: int = 5, robust: bool = True):
+    """Optimizer::BundleAdjustment of one map from its edge list on: ONE optimize(n_iterations), a Huber kernel on every edge iff
+    `robust`.  Arguments as local_bundle_adjustment's; fixed: != 0 for the keyframe with mnId == 0.  Returns (poses_out, points_out,
+    result): result is one BA_RESULT_DTYPE record.  A point without an edge keeps its bytes."""
+    cam = np.ascontiguousarray(camera, POSE_CAMERA_DTYPE).reshape(1)
+    poses = np.ascontiguousarray(np.asarray(poses, np.float32).reshape(-1, 12))
+    fixed = np.ascontiguousarray(fixed, np.uint8).reshape(-1)
+    points = np.ascontiguousarray(np.asarray(points, np.float32).reshape(-1, 3))
+    edges = np.ascontiguousarray(edges, LBA_EDGE_DTYPE).reshape(-1)
+    if len(fixed) != len(poses):
+        raise ValueError("poses and fixed must have one entry per keyframe")
+    poses_out, points_out = np.zeros_like(poses), np.zeros_like(points)
+    res = np.zeros(1, BA_RESULT_DTYPE)
+    opt = lambda a: _lib.ptr(a) if len(a) else None
+    _lib.check(_lib.lib().orbfe_bundle_adjustment(_lib.ptr(cam), opt(poses), opt(fixed), len(poses), opt(points), len(points), opt(edges),
+                                                  len(edges), int(n_iterations), BA_ROBUST if robust else 0, opt(poses_out),
+                                                  opt(points_out), _lib.ptr(res)), "orbfe_bundle_adjustment")
+    return poses_out, points_out, res[0]
+
+
+def bundle_adjustment_batch(camera, problems, poses, fixed, points, edges, kf_cap, point_cap, edge_cap, poses_out, points_out, result,
+                            workspace, n_iterations: int = 5, robust: bool = True, stream=None):
+    """orbfe_bundle_adjustment_batch_device on torch CUDA tensors, laid out as local_bundle_adjustment_batch's; result (P,40) u8 =
+    BA_RESULT_DTYPE, workspace: u8 of at least lba_workspace_bytes(P, kf_cap, point_cap, edge_cap) bytes.  n_iterations and robust
+    hold for every problem.  Rows no problem names are not written."""
+    P = int(problems.shape[0])
+    stride = int(points.shape[1]) * int(points.element_size()) if points.dim() == 2 else 12
+    _lib.check(_lib.lib().orbfe_bundle_adjustment_batch_device(
+        P, _lib.ptr(camera), _lib.ptr(problems), _lib.ptr(poses), _lib.ptr(fixed), _lib.ptr(points), stride, _lib.ptr(edges), int(kf_cap),
+        int(point_cap), int(edge_cap), int(n_iterations), BA_ROBUST if robust else 0, _lib.ptr(poses_out), _lib.ptr(points_out),
+        _lib.ptr(result), _lib.ptr(workspace), int(workspace.numel()) * int(workspace.element_size()), _lib.stream_handle(stream)),
+        "orbfe_bundle_adjustment_batch_device")
