@@ -382,6 +382,7 @@ def ref_extract(img, nfeatures, scale_factor, nlevels, ini_th, min_th, pattern):
 # no query records inside the loops).  tests/test_oracle_cpu.py asserts that the C oracle agrees with it on real-image pairs and
 # on a ties-heavy synthetic case; a misread quirk would have to be made twice, in two languages, to go unnoticed.
 import math
+import operator
 
 FRAME_GRID_ROWS, FRAME_GRID_COLS = 48, 64      # L/include/Frame.h:36-37
 TH_HIGH, TH_LOW, HISTO_LENGTH = 100, 50, 30    # L/src/ORBmatcher.cc:36-38
@@ -421,9 +422,14 @@ class RefFrame:
                 continue
             self.mGrid[posX][posY].append(i)
 
-    def GetFeaturesInArea(self, x, y, r, minLevel=-1, maxLevel=-1):
+    def GetFeaturesInArea(self, x, y, r, minLevel=-1, maxLevel=-1, in_box=None, info=None):
+        """`in_box(|d|, r)` stands in for the box comparison `|d| < r` (proj_walk's rules).  `info`, a dict, receives what proj_walk
+        records on the way: outside (one of the four early returns was taken), ncol (grid columns of the window), raw_pos (per
+        returned index its place among ALL entries of the window's cells, the order a wave consumes them in)."""
         x, y, r = _f32(x), _f32(y), _f32(r)
         vIndices = []
+        if info is not None:
+            info.update(outside=True, ncol=0, raw_pos=[])
         nMinCellX = max(0, int(math.floor((x - self.mnMinX - r) * self.mfGridElementWidthInv)))
         if nMinCellX >= FRAME_GRID_COLS:
             return vIndices
@@ -436,10 +442,14 @@ class RefFrame:
         nMaxCellY = min(FRAME_GRID_ROWS - 1, int(math.ceil((y - self.mnMinY + r) * self.mfGridElementHeightInv)))
         if nMaxCellY < 0:
             return vIndices
+        if info is not None:
+            info.update(outside=False, ncol=nMaxCellX - nMinCellX + 1)
         bCheckLevels = (minLevel > 0) or (maxLevel >= 0)
+        raw = 0
         for ix in range(nMinCellX, nMaxCellX + 1):
             for iy in range(nMinCellY, nMaxCellY + 1):
                 for j in self.mGrid[ix][iy]:
+                    raw += 1
                     if bCheckLevels:
                         if self.octave[j] < minLevel:
                             continue
@@ -447,13 +457,15 @@ class RefFrame:
                             continue
                     distx = self.x[j] - x
                     disty = self.y[j] - y
-                    if abs(distx) < r and abs(disty) < r:
+                    if (abs(distx) < r and abs(disty) < r) if in_box is None else (in_box(abs(distx), r) and in_box(abs(disty), r)):
                         vIndices.append(j)
+                        if info is not None:
+                            info["raw_pos"].append(raw - 1)
         return vIndices
 
 
-def compute_three_maxima(sizes):
-    """ORBmatcher::ComputeThreeMaxima (:1506-1538) on the bin sizes."""
+def compute_three_maxima(sizes, lt=operator.lt):
+    """ORBmatcher::ComputeThreeMaxima (:1506-1538) on the bin sizes.  `lt` stands in for the `<` of the 0.1 rule (proj_walk's rules)."""
     max1 = max2 = max3 = 0
     ind1 = ind2 = ind3 = -1
     for i, s in enumerate(sizes):
@@ -466,19 +478,172 @@ def compute_three_maxima(sizes):
         elif s > max3:
             max3 = s
             ind3 = i
-    if _f32(max2) < _f32(0.1) * _f32(max1):
+    if lt(_f32(max2), _f32(0.1) * _f32(max1)):
         ind2 = ind3 = -1
-    elif _f32(max3) < _f32(0.1) * _f32(max1):
+    elif lt(_f32(max3), _f32(0.1) * _f32(max1)):
         ind3 = -1
     return ind1, ind2, ind3
 
 
-def _rot_bin(angle_a, angle_b):
+def _rot_bin(angle_a, angle_b, rnd=c_round):
     rot = _f32(angle_a) - _f32(angle_b)
     if rot < 0.0:
         rot = rot + _f32(360.0)
-    b = c_round(rot * (_f32(1.0) / _f32(HISTO_LENGTH)))
+    b = rnd(rot * (_f32(1.0) / _f32(HISTO_LENGTH)))
     return 0 if b == HISTO_LENGTH else b
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# The ordered projection searches, one body: SearchByProjection(Frame&, vector<MapPoint*>&, th) (:45-128, mode 0),
+# SearchByProjection(Frame& cur, const Frame& last, th, bMono) from the window search on (:1289-1383, mode 1) and
+# SearchByProjection(Frame&, KeyFrame*, sAlreadyFound, th, ORBdist) from the window search on (:1439-1501: mode 1 without the stereo
+# gate, with ORBdist for TH_HIGH and every match blocking).
+(PX_SKIPPED, PX_OUTSIDE_GRID, PX_EMPTY_WINDOW, PX_ALL_GONE, PX_TOO_FAR, PX_RATIO, PX_MATCHED, PX_OVERWRITTEN, PX_ROTATION) = range(9)
+
+# The reference's comparisons.  A test swaps exactly one of them to show that the directed scenes tell the two readings apart.
+PROJ_RULES = dict(
+    best_lt=operator.lt,          # dist < bestDist: the first minimum in enumeration order wins
+    second_lt=operator.lt,        # dist < bestDist2: the first of tied second-best candidates gives bestLevel2
+    accept=operator.le,           # bestDist <= TH_HIGH
+    ratio_reject=operator.gt,     # bestDist > mfNNratio * bestDist2
+    same_level=operator.eq,       # bestLevel == bestLevel2
+    last_taker_wins=True,         # F.mvpMapPoints[bestIdx] = pMP overwrites
+    blocks=bool,                  # only a point with Observations() > 0 keeps later queries off its keypoint
+    rot_unblocks=True,            # the rotation check leaves NULL: the slot is free again
+    rot_clears_all=True,          # ... through every entry of a removed bin, whoever took the keypoint last
+    in_box=operator.lt,           # fabs(distx) < r && fabs(disty) < r
+    gate_fail=operator.gt,        # er > radius
+    has_right=lambda ur: ur > 0,  # mvuRight[idx] > 0
+    maxima_lt=operator.lt,        # max2 < 0.1f * max1
+    round=c_round,                # round(): halves away from zero
+)
+
+
+def proj_walk(F, queries, mode, nnratio, check_orientation, has_observed_point, th_high=TH_HIGH, stereo_gate=True, rules=None):
+    """The reference read literally, one query after the other.  queries[i] is indexable by the fields of the library's query record
+    (u, v, u_r, radius, min_level, max_level, valid, blocks, angle, desc); min_level / max_level go to GetFeaturesInArea as they are.
+    Returns (nmatches, assigned, blocked, exits, facts): assigned[idx] the query F.mvpMapPoints[idx] was written by (-1: none, or NULL
+    again), blocked[idx] whether the slot holds a point with Observations() > 0 after the call, exits one PX_* code per query, facts
+    what the walk saw.  Facts are counted on the indices that pass level, box AND stereo gate -- the list proj_candidates_kernel
+    writes -- so a keypoint that is blocked and fails the gate counts as gated.
+    per query: n_window, n_blocked_before, n_blocked_by_call, depth (0 without a by-call skip, else 1 + the largest depth among the
+    queries whose matches were skipped), dep_min (the earliest of those queries, -1), best_idx, best_dist, second_dist (256: none),
+    best_ties, best_tie_out_of_index_order, second_level_tied, matters_kept (not blocked before the call and d <= th_high, or in
+    mode 0 nnratio * d < th_high), ncol, best_pos / second_pos (place of the two among all entries of the window's cells),
+    first_choice / first_accept (what the query would do if no match of this call blocked anything), rot_bin (-1: none).
+    per call: hist, maxima, cleared_but_won_by_kept_bin."""
+    R = PROJ_RULES if rules is None else rules
+    nq, N = len(queries), F.N
+    blocked = [bool(b) for b in has_observed_point]
+    by_call = [-1] * N                      # the query of this call whose match blocks the slot
+    assigned = [-1] * N
+    takers = [[] for _ in range(N)]
+    exits = np.full(nq, PX_SKIPPED, np.int32)
+    zi = lambda v=0: np.full(nq, v, np.int32)
+    facts = dict(n_window=zi(), n_blocked_before=zi(), n_blocked_by_call=zi(), depth=zi(), dep_min=zi(-1), best_idx=zi(-1),
+                 best_dist=zi(256), second_dist=zi(256), best_ties=zi(), best_tie_out_of_index_order=np.zeros(nq, bool),
+                 second_level_tied=np.zeros(nq, bool), matters_kept=zi(), ncol=zi(), best_pos=zi(-1), second_pos=zi(-1),
+                 first_choice=zi(-1), first_accept=np.zeros(nq, bool), rot_bin=zi(-1))
+    rotHist = [[] for _ in range(HISTO_LENGTH)]
+    use_gate = stereo_gate and F.u_right is not None
+    use_hist = mode == 1 and check_orientation
+    nn, thf = _f32(nnratio), _f32(th_high)
+    nmatches = 0
+
+    def step(s, dist, idx, pos):
+        if R["best_lt"](dist, s[0]):
+            s[2], s[3], s[6] = s[0], s[1], s[5]
+            s[0], s[1], s[4], s[5] = dist, F.octave[idx], idx, pos
+        elif R["second_lt"](dist, s[2]):
+            s[2], s[3], s[6] = dist, F.octave[idx], pos
+
+    def decide(s):
+        if s[4] < 0:
+            return PX_ALL_GONE
+        if not R["accept"](s[0], th_high):
+            return PX_TOO_FAR
+        if mode == 0 and R["same_level"](s[1], s[3]) and R["ratio_reject"](_f32(s[0]), nn * _f32(s[2])):
+            return PX_RATIO
+        return PX_MATCHED
+
+    for i in range(nq):
+        q = queries[i]
+        if not q["valid"]:
+            continue
+        info = {}
+        r = _f32(q["radius"])
+        vIndices = F.GetFeaturesInArea(q["u"], q["v"], r, int(q["min_level"]), int(q["max_level"]), R["in_box"], info)
+        facts["ncol"][i] = info["ncol"]
+        if not vIndices:
+            exits[i] = PX_OUTSIDE_GRID if info["outside"] else PX_EMPTY_WINDOW
+            continue
+        s = [256, -1, 256, -1, -1, -1, -1]      # bestDist, bestLevel, bestDist2, bestLevel2, bestIdx and the places of the two
+        s0 = list(s)                            # the same without the blocks this call has made
+        open_ = []
+        for idx, pos in zip(vIndices, info["raw_pos"]):
+            gated = use_gate and R["has_right"](F.u_right[idx]) and R["gate_fail"](abs(_f32(q["u_r"]) - F.u_right[idx]), r)
+            if gated:
+                continue
+            facts["n_window"][i] += 1
+            dist = descriptor_distance(q["desc"], F.desc[idx])
+            if blocked[idx] and by_call[idx] < 0:
+                facts["n_blocked_before"][i] += 1
+                continue
+            if dist <= th_high or (mode == 0 and nn * _f32(dist) < thf):
+                facts["matters_kept"][i] += 1
+            step(s0, dist, idx, pos)
+            if blocked[idx]:
+                j = by_call[idx]
+                facts["n_blocked_by_call"][i] += 1
+                facts["depth"][i] = max(facts["depth"][i], 1 + facts["depth"][j])
+                facts["dep_min"][i] = j if facts["dep_min"][i] < 0 else min(facts["dep_min"][i], j)
+                continue
+            step(s, dist, idx, pos)
+            open_.append((idx, dist))
+        facts["first_choice"][i] = s0[4]
+        facts["first_accept"][i] = decide(s0) == PX_MATCHED
+        exits[i] = decide(s)
+        if s[4] >= 0:
+            bestIdx = s[4]
+            facts["best_idx"][i], facts["best_dist"][i], facts["second_dist"][i] = bestIdx, s[0], s[2]
+            facts["best_pos"][i], facts["second_pos"][i] = s[5], s[6]
+            tied = [idx for idx, d in open_ if d == s[0] and idx != bestIdx]
+            facts["best_ties"][i] = len(tied)
+            facts["best_tie_out_of_index_order"][i] = any(idx < bestIdx for idx in tied)
+            facts["second_level_tied"][i] = len({F.octave[idx] for idx, d in open_ if d == s[2] and idx != bestIdx}) > 1
+        if exits[i] != PX_MATCHED:
+            continue
+        if R["last_taker_wins"] or not takers[bestIdx]:
+            assigned[bestIdx] = i
+        takers[bestIdx].append(i)
+        blocked[bestIdx] = R["blocks"](q["blocks"])
+        by_call[bestIdx] = i if blocked[bestIdx] else -1
+        nmatches += 1
+        if use_hist:
+            facts["rot_bin"][i] = _rot_bin(q["angle"], F.angle[bestIdx], R["round"])
+            rotHist[facts["rot_bin"][i]].append((bestIdx, i))
+    for t in takers:
+        for i in t[:-1]:
+            exits[i] = PX_OVERWRITTEN
+    facts["hist"] = [len(h) for h in rotHist]
+    facts["maxima"] = (-1, -1, -1)
+    won = set()
+    if use_hist:
+        ind = facts["maxima"] = compute_three_maxima(facts["hist"], R["maxima_lt"])
+        for b in range(HISTO_LENGTH):
+            if b in ind:
+                continue
+            for idx, i in rotHist[b]:
+                if R["rot_clears_all"] or assigned[idx] == i:
+                    assigned[idx] = -1              # static_cast<MapPoint*>(NULL)
+                    if R["rot_unblocks"]:
+                        blocked[idx] = False
+                    if takers[idx][-1] != i and facts["rot_bin"][takers[idx][-1]] in ind:
+                        won.add(idx)
+                nmatches -= 1
+                exits[i] = PX_ROTATION
+    facts["cleared_but_won_by_kept_bin"] = len(won)
+    return nmatches, assigned, blocked, exits, facts
 
 
 def ref_search_by_projection_points(F, points, nnratio, has_observed_point):
@@ -487,41 +652,17 @@ def ref_search_by_projection_points(F, points, nnratio, has_observed_point):
     (= r * mvScaleFactors[level]), observed (Observations() > 0), desc.  has_observed_point[idx]: F.mvpMapPoints[idx] exists
     with Observations() > 0 before the call.  Returns (nmatches, point index per keypoint or -1, and per keypoint whether
     F.mvpMapPoints[idx] holds a point with Observations() > 0 after the call)."""
-    mvpMapPoints = [None] * F.N                      # index of the point written by this call
-    pre = list(has_observed_point)
-    nmatches = 0
-    for iMP, p in enumerate(points):
-        if p["skip"]:
-            continue
-        lvl = p["level"]
-        vIndices = F.GetFeaturesInArea(p["proj_x"], p["proj_y"], p["radius"], lvl - 1, lvl)
-        if not vIndices:
-            continue
-        bestDist, bestLevel, bestDist2, bestLevel2, bestIdx = 256, -1, 256, -1, -1
-        for idx in vIndices:
-            cur = mvpMapPoints[idx]
-            if (cur is not None and points[cur]["observed"]) or (cur is None and pre[idx]):
-                continue
-            if F.u_right is not None and F.u_right[idx] > 0:
-                er = abs(_f32(p["proj_xr"]) - F.u_right[idx])
-                if er > _f32(p["radius"]):
-                    continue
-            dist = descriptor_distance(p["desc"], F.desc[idx])
-            if dist < bestDist:
-                bestDist2, bestDist = bestDist, dist
-                bestLevel2, bestLevel = bestLevel, F.octave[idx]
-                bestIdx = idx
-            elif dist < bestDist2:
-                bestLevel2 = F.octave[idx]
-                bestDist2 = dist
-        if bestDist <= TH_HIGH:
-            if bestLevel == bestLevel2 and _f32(bestDist) > _f32(nnratio) * _f32(bestDist2):
-                continue
-            mvpMapPoints[bestIdx] = iMP
-            pre[bestIdx] = False
-            nmatches += 1
-    after = [bool(points[c]["observed"]) if c is not None else bool(pre[i]) for i, c in enumerate(mvpMapPoints)]
-    return nmatches, [(-1 if v is None else v) for v in mvpMapPoints], after
+    q = [dict(valid=False) if p["skip"] else
+         dict(valid=True, u=p["proj_x"], v=p["proj_y"], u_r=p["proj_xr"], radius=p["radius"], min_level=p["level"] - 1,
+              max_level=p["level"], blocks=p["observed"], angle=0.0, desc=p["desc"]) for p in points]
+    return proj_walk(F, q, 0, nnratio, False, has_observed_point)[:3]
+
+
+def _last_as_queries(last, blocks=None):
+    return [dict(valid=False) if p["skip"] else
+            dict(valid=True, u=p["u"], v=p["v"], u_r=p.get("ur", 0.0), radius=p["radius"], min_level=p["min_level"],
+                 max_level=p["max_level"], blocks=p["observed"] if blocks is None else blocks, angle=p["angle"], desc=p["desc"])
+            for p in last]
 
 
 def ref_search_by_projection_frame(F, last, check_orientation, has_observed_point):
@@ -531,44 +672,15 @@ def ref_search_by_projection_frame(F, last, check_orientation, has_observed_poin
     observed, angle (LastFrame.mvKeysUn[i].angle), desc.  Returns (nmatches, last-frame index per keypoint or -1, and per
     keypoint whether CurrentFrame.mvpMapPoints[idx] holds a point with Observations() > 0 after the call -- a slot the rotation
     check cleared is NULL again)."""
-    mvpMapPoints = [None] * F.N
-    pre = list(has_observed_point)
-    rotHist = [[] for _ in range(HISTO_LENGTH)]
-    nmatches = 0
-    for i, p in enumerate(last):
-        if p["skip"]:
-            continue
-        vIndices2 = F.GetFeaturesInArea(p["u"], p["v"], p["radius"], p["min_level"], p["max_level"])
-        if not vIndices2:
-            continue
-        bestDist, bestIdx2 = 256, -1
-        for i2 in vIndices2:
-            cur = mvpMapPoints[i2]
-            if (cur is not None and cur >= 0 and last[cur]["observed"]) or (cur is None and pre[i2]):
-                continue
-            if F.u_right is not None and F.u_right[i2] > 0:
-                er = abs(_f32(p["ur"]) - F.u_right[i2])
-                if er > _f32(p["radius"]):
-                    continue
-            dist = descriptor_distance(p["desc"], F.desc[i2])
-            if dist < bestDist:
-                bestDist, bestIdx2 = dist, i2
-        if bestDist <= TH_HIGH:
-            mvpMapPoints[bestIdx2] = i
-            pre[bestIdx2] = False
-            nmatches += 1
-            if check_orientation:
-                rotHist[_rot_bin(p["angle"], F.angle[bestIdx2])].append(bestIdx2)
-    if check_orientation:
-        ind = compute_three_maxima([len(h) for h in rotHist])
-        for b in range(HISTO_LENGTH):
-            if b in ind:
-                continue
-            for idx in rotHist[b]:
-                mvpMapPoints[idx] = -1          # static_cast<MapPoint*>(NULL)
-                nmatches -= 1
-    after = [(c >= 0 and bool(last[c]["observed"])) if c is not None else bool(pre[i]) for i, c in enumerate(mvpMapPoints)]
-    return nmatches, [(-1 if v is None else v) for v in mvpMapPoints], after
+    return proj_walk(F, _last_as_queries(last), 1, 0.0, check_orientation, has_observed_point)[:3]
+
+
+def ref_search_by_projection_keyframe(F, points, orb_dist, check_orientation, has_point):
+    """SearchByProjection(Frame& CurrentFrame, KeyFrame*, sAlreadyFound, th, ORBdist) from the window search on (:1439-1501).
+    points: as `last` above without ur and observed (there is no stereo gate, :1453 tests the slot for NULL and :1468 fills it:
+    every match blocks).  has_point[i2]: CurrentFrame.mvpMapPoints[i2] != NULL on entry.  Returns (nmatches, point index per
+    keypoint or -1, has_point after the call)."""
+    return proj_walk(F, _last_as_queries(points, True), 1, 0.0, check_orientation, has_point, th_high=orb_dist, stereo_gate=False)[:3]
 
 
 def ref_search_by_bow(descKF, angleKF, validKF, featvecKF, descF, angleF, featvecF, nnratio, check_orientation):
