@@ -129,7 +129,10 @@ int orbfe_device_download(void* h_dst, const void* d_src, size_t bytes);
  *   covisibility graph  at most 32 768 keyframe rows, 2 048 entries per subject (conn_cap), 65 535 subjects or problems per launch,
  *                       16 777 216 slots and 1 048 576 local keyframes per call, the point and observation limits of the map-point
  *                       refresh (the ORBFE_COV_MAX_* constants, each with its reason; pinned by tests/test_covis_cpu.py)
- * Each limit is pinned at its largest accepted and its first refused value by tests/test_limits_gpu.py (levels: also
+ *   essential graph     at most 32 768 vertices, 262 144 edges and 131 072 envelope blocks per problem, 65 535 problems per launch,
+ *                       16 777 216 points per map correction (the ORBFE_EG_MAX_* constants, each with its reason; pinned by
+ *                       tests/test_egraph_cpu.py and tests/test_egraph_gpu.py)
+ * Each limit up to the covisibility graph's is pinned at its largest accepted and its first refused value by tests/test_limits_gpu.py (levels: also
  * tests/test_cabi_cpu.py; depth maps: tests/test_frames_cpu.py and tests/test_frames_gpu.py; rectification:
  * tests/test_rectify_cpu.py and tests/test_rectify_gpu.py; pose optimisation: tests/test_pose_cpu.py).
  * Threads: a handle serialises its own calls (internal mutex); different handles may be used from different threads at the same
@@ -1725,6 +1728,113 @@ int orbfe_create_initial_map_batch_device(int P, const orbfe_pose_camera* d_came
                                           int q, int min_points, float* d_poses, float* d_points, int32_t* d_index, float* d_poses_ba,
                                           float* d_points_ba, orbfe_initial_map_result* d_result, void* d_workspace,
                                           size_t workspace_bytes, void* stream);
+
+/* ---- Optimizer::OptimizeEssentialGraph (L/src/Optimizer.cc:1366, :760-1043, :1052-1362) and the map correction behind it --------------
+ * The pose graph of LoopClosing::CorrectLoop: one vertex per keyframe, one edge per spanning-tree, loop and strong covisibility link
+ * and per loop connection, information the identity, no robust kernel, ONE optimize(20) of g2o's Levenberg with
+ * setUserLambdaInit(1e-16) and at most 10 trials per iteration; fixed vertices and vertices without an edge are left out of the
+ * system and keep their record byte for byte.  Without ORBFE_EG_FIX_SCALE it is the 7-DoF form: VertexSim3Expmap, EdgeSim3, error
+ * (C * Si * Sj^-1).log(), the NUMERIC Jacobian of G/core/base_fixed_sized_edge.hpp (central differences, step 1e-9: G2O_SIM3_JACOBIAN is
+ * defined nowhere in the reference).  With it, the 6-DoF form the reference adds for stereo and RGB-D: VertexSE3Expmap, EdgeSE3Expmap,
+ * error (Tj^-1 * C * Ti).log(), the analytic Jacobian of G/types/sba/edge_se3_expmap.cpp.  csrc/egraph_internal.h states the
+ * arithmetic once, all in double; the Levenberg rules are csrc/lm_internal.h's.
+ * The measurement of an edge is computed once per edge by the kernel: Scw[j] * Scw[i]^-1 for a loop connection, Snc[j] * Snc[i]^-1 for
+ * every other edge.
+ * The solve: SimplicialLLT with its AMD ordering becomes an unpivoted block L L^T on the ROW ENVELOPE of the free vertices IN THE
+ * CALLER'S VERTEX ORDER: the vertex order is the elimination order.  Row r of the factor is stored from the first free vertex it
+ * shares an edge with up to its diagonal, and a Cholesky factor never fills outside that envelope.  Keyframes ascending by mnId is
+ * what keeps it small: a spanning tree and covisibility links join keyframes of nearby ids, so the envelope is a band plus the few
+ * rows that carry a loop edge.  No fill-reducing reordering is applied.  A pivot that is not > 0 fails the trial (g2o's ok2 = false):
+ * the estimates are left alone, lambda grows, and ORBFE_EG_FACTOR_FAILED is reported in the result's status.
+ * One workgroup per problem; a multi-workgroup form of one problem does not exist.  Deterministic: no floating-point atomics, every
+ * sum has one owner that walks a sorted list; a problem's bytes depend on its own rows only.  No CPU fallback.
+ * Limits, each refused with ORBFE_ERR_INVALID one step past it (a per-problem ORBFE_EG_REFUSED on the batch form; pinned by
+ * tests/test_egraph_cpu.py and tests/test_egraph_gpu.py):
+ *   ORBFE_EG_MAX_KEYFRAMES        32 768 vertices: the keyframe-row limit of the covisibility graph whose links the edges are
+ *   ORBFE_EG_MAX_EDGES            262 144 edges: 113 doubles of workspace an edge (measurement, error, both Jacobians) -- 237 MB
+ *   ORBFE_EG_MAX_ENVELOPE_BLOCKS  131 072 blocks of 7 x 7 doubles: 51 MB of workspace, its elements indexed in 32 bits, and the ONE
+ *                                 workgroup walks the blocks of a row one after the other -- about half a second per trial for
+ *                                 the 77 000 blocks of 2 000 keyframes in a band of 20 with 30 loop rows
+ *                                 (profiles/essential_graph.md)
+ *   ORBFE_EG_MAX_PROBLEMS         65 535 problems per launch
+ *   records                       finite, s > 0, a quaternion of non-zero norm; with ORBFE_EG_FIX_SCALE |s - 1| <= 1e-3 for every
+ *                                 record and every derived measurement (the reference throws there, Optimizer.cc:1057-1067) */
+#define ORBFE_EG_MAX_KEYFRAMES 32768
+#define ORBFE_EG_MAX_EDGES 262144
+#define ORBFE_EG_MAX_ENVELOPE_BLOCKS 131072
+#define ORBFE_EG_MAX_PROBLEMS 65535
+#define ORBFE_EG_FIX_SCALE 1              /* flags: bFixScale -- the SE3 form */
+#define ORBFE_EG_NORMAL 0                 /* edge kinds: spanning tree, old loop edge, covisibility (Optimizer.cc:1191-1286) */
+#define ORBFE_EG_LOOP_CONNECTION 1        /* an entry of LoopConnections (:1146-1183) */
+#define ORBFE_EG_DONE 0                   /* status of a result */
+#define ORBFE_EG_FACTOR_FAILED 1          /* at least one trial met a pivot that was not > 0 */
+#define ORBFE_EG_REFUSED (-1)             /* batch form: the problem breaks a limit; nothing of it was optimised */
+typedef struct orbfe_eg_sim3 {            /* g2o::Sim3's own fields; 64 bytes */
+  double q[4];                            /* x y z w */
+  double t[3];
+  double s;
+} orbfe_eg_sim3;
+typedef struct orbfe_eg_vertex {          /* 136 bytes */
+  orbfe_eg_sim3 Scw;                      /* the start estimate and vScw: the CorrectedSim3 entry, else Sim3(Rcw, tcw, 1) */
+  orbfe_eg_sim3 Snc;                      /* the NonCorrectedSim3 entry, else equal to Scw */
+  uint32_t fixed;                         /* != 0: pLoopKF */
+  uint32_t reserved;
+} orbfe_eg_vertex;
+typedef struct orbfe_eg_edge {            /* 12 bytes */
+  int32_t i, j;                           /* vertex 0 and vertex 1 of the g2o edge; i != j */
+  uint32_t kind;                          /* ORBFE_EG_NORMAL or ORBFE_EG_LOOP_CONNECTION */
+} orbfe_eg_edge;
+typedef struct orbfe_eg_problem {         /* where one problem of a batch lies in the batch's arrays; 16 bytes */
+  int32_t kf_offset, n_kf;                /* rows of d_vertices / d_sim3_out / d_poses_out */
+  int32_t edge_offset, n_edges;           /* rows of d_edges */
+} orbfe_eg_problem;
+typedef struct orbfe_eg_result {          /* 48 bytes, 8-byte aligned */
+  int32_t status;                         /* ORBFE_EG_DONE, ORBFE_EG_FACTOR_FAILED, ORBFE_EG_REFUSED */
+  int32_t iterations, trials;             /* Levenberg iterations and trials run (0 without a free vertex with an edge) */
+  int32_t n_free;                         /* vertices in the system: not fixed, with an edge */
+  int32_t n_edges;
+  int32_t envelope_blocks;                /* blocks of the row envelope of this problem */
+  double chi2_first, chi2_last;           /* activeChi2 before the first iteration and at the final estimates */
+  double lambda;                          /* the final damping */
+} orbfe_eg_result;
+/* The blocks of the row envelope of a graph: for every vertex that is not fixed and has an edge, one diagonal block and one per free
+ * vertex from the earliest it shares an edge with up to itself.  HOST pointers.  fixed[n_kf]: != 0 for a fixed vertex (NULL: none).
+ * Limits (ORBFE_ERR_INVALID): the counts within 0 .. ORBFE_EG_MAX_KEYFRAMES / ORBFE_EG_MAX_EDGES, edge indices in range, i != j,
+ * null blocks.  The count itself is not limited here. */
+int orbfe_essential_graph_envelope_blocks(int n_kf, const uint8_t* fixed, const orbfe_eg_edge* edges, int n_edges, int64_t* blocks);
+/* One graph.  HOST pointers, synchronous.  sim3_out[n_kf]: the corrected Siw of every vertex (with ORBFE_EG_FIX_SCALE: the SE3Quat's
+ * rotation and translation, s = 1); a vertex that is fixed or has no edge: its Scw as given.  poses_out: n_kf x 12 floats, rows of
+ * [R | t / s] as SetPose receives them (:1003-1011; with ORBFE_EG_FIX_SCALE [R | t], :1324-1329).  A problem without a free vertex or
+ * without an edge returns its inputs, iterations = 0.  One upload, one launch, one download; the workspace is allocated for the call.
+ * Limits (ORBFE_ERR_INVALID): those above, null arrays with a count > 0, null result, flags outside ORBFE_EG_FIX_SCALE. */
+int orbfe_essential_graph(const orbfe_eg_vertex* vertices, int n_kf, const orbfe_eg_edge* edges, int n_edges, int flags,
+                          orbfe_eg_sim3* sim3_out, float* poses_out, orbfe_eg_result* result);
+/* The bytes of workspace a batch of P problems needs whose counts stay within kf_cap vertices, edge_cap edges and env_cap envelope
+ * blocks each.  Limits (ORBFE_ERR_INVALID): 0 <= P <= ORBFE_EG_MAX_PROBLEMS, the caps >= 0 and within the ORBFE_EG_MAX_*, null bytes. */
+int orbfe_essential_graph_workspace_bytes(int P, int kf_cap, int edge_cap, int env_cap, size_t* bytes);
+/* P graphs in one launch, one workgroup each.  DEVICE pointers, asynchronous on `stream` (NULL: the NULL stream).  Problem p lies
+ * where d_problems[p] says.  A problem that breaks a limit above, or whose envelope exceeds env_cap, is refused by its workgroup:
+ * status ORBFE_EG_REFUSED, its Scw and their poses written through when its rows can be addressed; no other problem is touched.
+ * d_workspace: 256-byte aligned, at least what orbfe_essential_graph_workspace_bytes states; its contents mean nothing before or
+ * after.  A problem's bytes do not depend on P, on its position or on the run: they are those of the host form. */
+int orbfe_essential_graph_batch_device(int P, const orbfe_eg_problem* d_problems, const orbfe_eg_vertex* d_vertices,
+                                       const orbfe_eg_edge* d_edges, int kf_cap, int edge_cap, int env_cap, int flags,
+                                       orbfe_eg_sim3* d_sim3_out, float* d_poses_out, orbfe_eg_result* d_result, void* d_workspace,
+                                       size_t workspace_bytes, void* stream);
+/* The map correction of OptimizeEssentialGraph (:1014-1042, :1332-1361) and the neighbour propagation of CorrectLoop
+ * (L/src/LoopClosing.cc:445-475): points_out[p] = to[ref[p]]^-1 .map( from[ref[p]].map(points[p]) ), with Eigen's quaternion-vector
+ * product, the float position widened to double and rounded once to float at the end (Converter::toCvMat).  ref[p] < 0: the point
+ * goes through as it is (a bad point, or one CorrectLoop has moved already).  from = vScw (the Scw of the vertices), to = sim3_out of
+ * orbfe_essential_graph; n_tables rows each.  One thread per point.  HOST pointers, synchronous.
+ * Limits (ORBFE_ERR_INVALID): 0 <= n_points <= 16 777 216, 0 <= n_tables <= ORBFE_EG_MAX_KEYFRAMES, ref[p] < n_tables, null arrays with
+ * a count > 0. */
+int orbfe_sim3_correct_points(const float* points, int n_points, const int32_t* ref, const orbfe_eg_sim3* from, const orbfe_eg_sim3* to,
+                              int n_tables, float* points_out);
+/* The same on DEVICE pointers, asynchronous on `stream`: d_to may be the d_sim3_out of orbfe_essential_graph_batch_device, so the chain
+ * needs no host round trip.  d_from: `from_stride` bytes apart (sizeof(orbfe_eg_vertex) reads the Scw of a vertex array in place,
+ * sizeof(orbfe_eg_sim3) a plain table).  A ref[p] >= n_tables goes through like a negative one (it cannot be checked on the host). */
+int orbfe_sim3_correct_points_device(const float* d_points, int n_points, const int32_t* d_ref, const void* d_from, int from_stride,
+                                     const orbfe_eg_sim3* d_to, int n_tables, float* d_points_out, void* stream);
 
 /* --------------------------------------------------------------------------------------- sequence driver helpers */
 /* Dependency-free PNG input for the dataset drivers (the reference reads with cv::imread(..., IMREAD_UNCHANGED),

@@ -203,6 +203,20 @@ COV_CONNECTIONS, COV_VOTES = 0, 1
 COV_OK, COV_EMPTY, COV_OVERFLOW, COV_REFUSED = 0, 1, 2, 3
 COV_KEPT, COV_CULLED, COV_MARKED, COV_SKIPPED_ID0, COV_ROW_REFUSED = 0, 1, 2, 3, 4
 COV_IS_ID0, COV_NOT_ERASE = 1, 2
+# orbfe_eg_sim3 / orbfe_eg_vertex / orbfe_eg_edge / orbfe_eg_problem / orbfe_eg_result and the ORBFE_EG_* limits
+# (Optimizer::OptimizeEssentialGraph and the map correction behind it, include/orbfe.h)
+EG_SIM3_DTYPE = np.dtype([("q", "<f8", (4,)), ("t", "<f8", (3,)), ("s", "<f8")])
+EG_VERTEX_DTYPE = np.dtype([("Scw", EG_SIM3_DTYPE), ("Snc", EG_SIM3_DTYPE), ("fixed", "<u4"), ("reserved", "<u4")])
+EG_EDGE_DTYPE = np.dtype([("i", "<i4"), ("j", "<i4"), ("kind", "<u4")])
+EG_PROBLEM_DTYPE = np.dtype([("kf_offset", "<i4"), ("n_kf", "<i4"), ("edge_offset", "<i4"), ("n_edges", "<i4")])
+EG_RESULT_DTYPE = np.dtype([("status", "<i4"), ("iterations", "<i4"), ("trials", "<i4"), ("n_free", "<i4"), ("n_edges", "<i4"),
+                            ("envelope_blocks", "<i4"), ("chi2_first", "<f8"), ("chi2_last", "<f8"), ("lambda", "<f8")])
+assert EG_SIM3_DTYPE.itemsize == 64 and EG_VERTEX_DTYPE.itemsize == 136 and EG_EDGE_DTYPE.itemsize == 12
+assert EG_PROBLEM_DTYPE.itemsize == 16 and EG_RESULT_DTYPE.itemsize == 48
+EG_MAX_KEYFRAMES, EG_MAX_EDGES, EG_MAX_ENVELOPE_BLOCKS, EG_MAX_PROBLEMS, EG_MAX_POINTS = 32768, 262144, 131072, 65535, 16777216
+EG_FIX_SCALE = 1
+EG_NORMAL, EG_LOOP_CONNECTION = 0, 1
+EG_DONE, EG_FACTOR_FAILED, EG_REFUSED = 0, 1, -1
 
 
 class RectifyCamera(C.Structure):
@@ -257,6 +271,8 @@ EXPORTS = [
     "orbfe_covis_count", "orbfe_covis_count_batch_device", "orbfe_covis_cull_keyframes", "orbfe_covis_cull_keyframes_batch_device",
     "orbfe_initializer_initialize", "orbfe_initializer_workspace_bytes", "orbfe_initializer_initialize_batch_device",
     "orbfe_create_initial_map", "orbfe_initial_map_workspace_bytes", "orbfe_create_initial_map_batch_device",
+    "orbfe_essential_graph_envelope_blocks", "orbfe_essential_graph", "orbfe_essential_graph_workspace_bytes",
+    "orbfe_essential_graph_batch_device", "orbfe_sim3_correct_points", "orbfe_sim3_correct_points_device",
 ]
 
 
@@ -405,6 +421,12 @@ def lib():
     L.orbfe_initial_map_workspace_bytes.argtypes = [ci, ci, C.POINTER(sz)]
     L.orbfe_create_initial_map_batch_device.argtypes = [ci, vp, vp, vp, vp, vp, ci, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, vp, vp, vp, vp, vp,
                                                         vp, vp, sz, vp]
+    L.orbfe_essential_graph_envelope_blocks.argtypes = [ci, vp, vp, ci, C.POINTER(i64)]
+    L.orbfe_essential_graph.argtypes = [vp, ci, vp, ci, ci, vp, vp, vp]
+    L.orbfe_essential_graph_workspace_bytes.argtypes = [ci, ci, ci, ci, C.POINTER(sz)]
+    L.orbfe_essential_graph_batch_device.argtypes = [ci, vp, vp, vp, ci, ci, ci, ci, vp, vp, vp, vp, sz, vp]
+    L.orbfe_sim3_correct_points.argtypes = [vp, ci, vp, vp, vp, ci, vp]
+    L.orbfe_sim3_correct_points_device.argtypes = [vp, ci, vp, vp, ci, vp, ci, vp, vp]
     for name in EXPORTS:
         if name != "orbfe_last_error":
             getattr(L, name).restype = ci

@@ -32,6 +32,15 @@
 //   Map:      GetAllKeyFrames(), GetAllMapPoints()
 // AdjustAndScaleInitialMap is Tracking.cc:618-642 -- the adjustment of the two-keyframe map, the median depth, the reset rule and the
 // rescale -- on orbfe_create_initial_map.  Members used beyond the above: KeyFrame::N, MapPoint::GetIndexInKeyFrame(KeyFrame*).
+//
+// OptimizeEssentialGraph (Optimizer.cc:1366, both forms) is the adapter for orbfe_essential_graph and orbfe_sim3_correct_points, with
+// the reference's signature, split into a marshal and an apply half and unit-tested by tests/cpp/test_egraph_dropin.cpp.  Members used
+// beyond the above:
+//   KeyFrame: GetRotation(), GetTranslation(), GetParent(), hasChild(KeyFrame*), GetLoopEdges(), GetCovisiblesByWeight(int),
+//             GetWeight(KeyFrame*)
+//   MapPoint: mnCorrectedByKF, mnCorrectedReference, GetReferenceKeyFrame(), and what MapPoint_hip.h names
+//   Map:      GetAllKeyFrames(), GetAllMapPoints()
+//   Sim3:     rotation() with x() y() z() w(), translation(), scale(), the constructor (Matrix3, Vector3, double)
 #pragma once
 #include <stdio.h>
 #include <string.h>
@@ -42,7 +51,12 @@
 #include <type_traits>
 #include <vector>
 
+#include <algorithm>
+#include <set>
+#include <utility>
+
 #include "../../../include/orbfe.h"
+#include "MapPoint_hip.h"
 
 namespace ORB_SLAM2 {
 namespace orbfe_host {
@@ -570,6 +584,172 @@ bool AdjustAndScaleInitialMap(KeyFrameT* pKFini, KeyFrameT* pKFcur, int nIterati
   pKFcur->SetPose(pose_of(poses + 12));   // :630-633
   for (int k = 0; k < res.n_points; k++) vpMP[index[k]]->SetWorldPos(point_of(points.data() + 3 * index[k]));   // :636-642
   return true;
+}
+
+// g2o::Sim3's own fields into the library's record: a copy, never a conversion
+template <class Sim3T>
+orbfe_eg_sim3 EssentialGraphRecord(const Sim3T& S) {
+  orbfe_eg_sim3 r;
+  r.q[0] = S.rotation().x();
+  r.q[1] = S.rotation().y();
+  r.q[2] = S.rotation().z();
+  r.q[3] = S.rotation().w();
+  for (int k = 0; k < 3; k++) r.t[k] = S.translation()[k];
+  r.s = S.scale();
+  return r;
+}
+
+// Sim3(Rcw, tcw, 1.0) of a float pose by the caller's own Sim3 type (Optimizer.cc:813-818, LoopClosing.cc:435-438)
+template <class Sim3T>
+Sim3T EssentialGraphSim3(const cv::Mat& R, const cv::Mat& t) {
+  std::decay_t<decltype(std::declval<Sim3T>().rotation().toRotationMatrix())> Rd;
+  std::decay_t<decltype(std::declval<Sim3T>().translation())> td;
+  for (int r = 0; r < 3; r++) {
+    for (int c = 0; c < 3; c++) Rd(r, c) = (double)R.template at<float>(r, c);
+    td[r] = (double)t.template at<float>(r);
+  }
+  return Sim3T(Rd, td, 1.0);
+}
+
+// What Optimizer::OptimizeEssentialGraph builds before it optimises (Optimizer.cc:787-985, :1083-1301), as the library's arguments.
+// Vertex rows: the keyframes that are not bad, ascending by mnId -- the elimination order of the library's solve; edges in the order of
+// the reference's addEdge calls over that keyframe order; point rows: GetAllMapPoints() in its order, ref = the vertex row of the
+// keyframe the point is corrected through (:1022-1028), -1 for a bad point.
+template <class KeyFrameT, class MapPointT>
+struct EssentialGraphProblem {
+  std::vector<KeyFrameT*> vpKFs;
+  std::vector<orbfe_eg_vertex> vertices;
+  std::vector<orbfe_eg_edge> edges;
+  std::vector<MapPointT*> vpMPs;
+  std::vector<float> points;
+  std::vector<int32_t> ref;
+};
+
+template <class MapT, class KeyFrameT, class MapPointT, class PoseMapT, class ConnectionsT>
+void OptimizeEssentialGraphMarshal(MapT* pMap, KeyFrameT* pLoopKF, KeyFrameT* pCurKF, const PoseMapT& NonCorrectedSim3,
+                                   const PoseMapT& CorrectedSim3, const ConnectionsT& LoopConnections,
+                                   EssentialGraphProblem<KeyFrameT, MapPointT>& B) {
+  typedef typename PoseMapT::mapped_type Sim3T;
+  const int minFeat = 100;
+  for (KeyFrameT* pKF : pMap->GetAllKeyFrames())
+    if (!pKF->isBad()) B.vpKFs.push_back(pKF);
+  std::sort(B.vpKFs.begin(), B.vpKFs.end(), [](KeyFrameT* a, KeyFrameT* b) { return a->mnId < b->mnId; });
+  std::map<KeyFrameT*, int32_t> row;
+  std::map<long unsigned int, int32_t> row_of_id;
+  // Set KeyFrame vertices (:799-831)
+  for (KeyFrameT* pKF : B.vpKFs) {
+    orbfe_eg_vertex v;
+    memset(&v, 0, sizeof(v));
+    const auto it = CorrectedSim3.find(pKF);
+    v.Scw = it != CorrectedSim3.end() ? EssentialGraphRecord(it->second)
+                                      : EssentialGraphRecord(EssentialGraphSim3<Sim3T>(pKF->GetRotation(), pKF->GetTranslation()));
+    const auto itn = NonCorrectedSim3.find(pKF);
+    v.Snc = itn != NonCorrectedSim3.end() ? EssentialGraphRecord(itn->second) : v.Scw;
+    v.fixed = pKF == pLoopKF ? 1 : 0;
+    row[pKF] = row_of_id[pKF->mnId] = (int32_t)B.vertices.size();
+    B.vertices.push_back(v);
+  }
+  // an edge one of whose keyframes has no vertex is not added by g2o either
+  auto add = [&B, &row](KeyFrameT* a, KeyFrameT* b, uint32_t kind) {
+    const auto ia = row.find(a), ib = row.find(b);
+    if (ia == row.end() || ib == row.end() || ia->second == ib->second) return;
+    orbfe_eg_edge e;
+    e.i = ia->second;
+    e.j = ib->second;
+    e.kind = kind;
+    B.edges.push_back(e);
+  };
+  std::set<std::pair<long unsigned int, long unsigned int>> sInsertedEdges;
+  // Set Loop edges (:839-873)
+  for (auto mit = LoopConnections.begin(), mend = LoopConnections.end(); mit != mend; mit++) {
+    KeyFrameT* pKF = mit->first;
+    const long unsigned int nIDi = pKF->mnId;
+    for (KeyFrameT* pKFj : mit->second) {
+      const long unsigned int nIDj = pKFj->mnId;
+      if ((nIDi != pCurKF->mnId || nIDj != pLoopKF->mnId) && pKF->GetWeight(pKFj) < minFeat) continue;
+      add(pKF, pKFj, ORBFE_EG_LOOP_CONNECTION);
+      sInsertedEdges.insert(std::make_pair(std::min(nIDi, nIDj), std::max(nIDi, nIDj)));
+    }
+  }
+  // Set normal edges (:876-985)
+  for (KeyFrameT* pKF : B.vpKFs) {
+    KeyFrameT* pParentKF = pKF->GetParent();
+    if (pParentKF) add(pKF, pParentKF, ORBFE_EG_NORMAL);   // Spanning tree edge
+    const auto sLoopEdges = pKF->GetLoopEdges();
+    for (KeyFrameT* pLKF : sLoopEdges)
+      if (pLKF->mnId < pKF->mnId) add(pKF, pLKF, ORBFE_EG_NORMAL);
+    const std::vector<KeyFrameT*> vpConnectedKFs = pKF->GetCovisiblesByWeight(minFeat);
+    for (KeyFrameT* pKFn : vpConnectedKFs)
+      if (pKFn && pKFn != pParentKF && !pKF->hasChild(pKFn) && !sLoopEdges.count(pKFn))
+        if (!pKFn->isBad() && pKFn->mnId < pKF->mnId) {
+          if (sInsertedEdges.count(std::make_pair(std::min(pKF->mnId, pKFn->mnId), std::max(pKF->mnId, pKFn->mnId)))) continue;
+          add(pKF, pKFn, ORBFE_EG_NORMAL);
+        }
+  }
+  // the point table (:1016-1034)
+  B.vpMPs = pMap->GetAllMapPoints();
+  B.points.assign(3 * B.vpMPs.size(), 0.0f);
+  B.ref.assign(B.vpMPs.size(), -1);
+  for (size_t i = 0; i < B.vpMPs.size(); i++) {
+    MapPointT* pMP = B.vpMPs[i];
+    if (!pMP || pMP->isBad()) continue;
+    const long unsigned int nIDr = pMP->mnCorrectedByKF == pCurKF->mnId ? pMP->mnCorrectedReference : pMP->GetReferenceKeyFrame()->mnId;
+    const auto it = row_of_id.find(nIDr);
+    if (it == row_of_id.end()) continue;   // the reference keyframe has no vertex: the point is left alone
+    B.ref[i] = it->second;
+    const cv::Mat P3Dw = pMP->GetWorldPos();
+    for (int r = 0; r < 3; r++) B.points[3 * i + r] = P3Dw.template at<float>(r);
+  }
+}
+
+// The second half of OptimizeEssentialGraph (:991-1042, :1307-1361) for a problem B and the library's outputs for it: under the map's
+// mutex SetPose of every keyframe with a vertex, SetWorldPos of every point with a row, and their UpdateNormalAndDepth in ONE batch
+// (MapPoint_hip.h) instead of per point.
+template <class KeyFrameT, class MapPointT, class MapT>
+void OptimizeEssentialGraphApply(EssentialGraphProblem<KeyFrameT, MapPointT>& B, const float* poses_out, const float* points_out, MapT* pMap) {
+  std::unique_lock<std::mutex> lock(pMap->mMutexMapUpdate);
+  for (size_t k = 0; k < B.vpKFs.size(); k++) {
+    cv::Mat Tiw = cv::Mat::eye(4, 4, CV_32F);
+    for (int r = 0; r < 3; r++)
+      for (int c = 0; c < 4; c++) Tiw.template at<float>(r, c) = poses_out[12 * k + 4 * r + c];
+    B.vpKFs[k]->SetPose(Tiw);
+  }
+  std::vector<MapPointT*> moved;
+  for (size_t i = 0; i < B.vpMPs.size(); i++) {
+    if (B.ref[i] < 0) continue;
+    cv::Mat X(3, 1, CV_32F);
+    for (int r = 0; r < 3; r++) X.template at<float>(r) = points_out[3 * i + r];
+    B.vpMPs[i]->SetWorldPos(X);
+    moved.push_back(B.vpMPs[i]);
+  }
+  UpdateNormalAndDepth(moved);
+}
+
+// void Optimizer::OptimizeEssentialGraph(Map* pMap, KeyFrame* pLoopKF, KeyFrame* pCurKF, const LoopClosing::KeyFrameAndPose&
+// NonCorrectedSim3, const LoopClosing::KeyFrameAndPose& CorrectedSim3, const map<KeyFrame*, set<KeyFrame*>>& LoopConnections, const
+// bool& bFixScale).  Two library calls: the graph, then the map correction.  Errors (no device, a graph beyond the library's limits,
+// a scale beyond 1e-3 of 1 with bFixScale -- where the reference throws) are logged and leave the map untouched.
+template <class MapT, class KeyFrameT, class PoseMapT, class ConnectionsT>
+void OptimizeEssentialGraph(MapT* pMap, KeyFrameT* pLoopKF, KeyFrameT* pCurKF, const PoseMapT& NonCorrectedSim3,
+                            const PoseMapT& CorrectedSim3, const ConnectionsT& LoopConnections, const bool& bFixScale) {
+  using MapPointT = std::remove_pointer_t<typename decltype(pMap->GetAllMapPoints())::value_type>;
+  EssentialGraphProblem<KeyFrameT, MapPointT> B;
+  OptimizeEssentialGraphMarshal(pMap, pLoopKF, pCurKF, NonCorrectedSim3, CorrectedSim3, LoopConnections, B);
+  const int n_kf = (int)B.vertices.size(), n_pt = (int)B.vpMPs.size();
+  std::vector<orbfe_eg_sim3> sim3_out((size_t)n_kf), vScw((size_t)n_kf);
+  std::vector<float> poses_out((size_t)12 * n_kf), points_out((size_t)3 * n_pt);
+  orbfe_eg_result res;
+  int rc = orbfe_essential_graph(B.vertices.data(), n_kf, B.edges.data(), (int)B.edges.size(), bFixScale ? ORBFE_EG_FIX_SCALE : 0,
+                                 sim3_out.data(), poses_out.data(), &res);
+  if (rc == ORBFE_OK) {
+    for (int k = 0; k < n_kf; k++) vScw[k] = B.vertices[k].Scw;
+    rc = orbfe_sim3_correct_points(B.points.data(), n_pt, B.ref.data(), vScw.data(), sim3_out.data(), n_kf, points_out.data());
+  }
+  if (rc != ORBFE_OK) {
+    fprintf(stderr, "orbfe OptimizeEssentialGraph: %s (code %d)\n", orbfe_last_error(), rc);
+    return;
+  }
+  OptimizeEssentialGraphApply(B, poses_out.data(), points_out.data(), pMap);
 }
 
 }  // namespace orbfe_host

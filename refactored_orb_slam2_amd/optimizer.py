@@ -17,6 +17,12 @@ lie in device tensors in one launch (lba_kernels.hip, one workgroup per problem)
 bundle_adjustment is the call of Tracking::CreateInitialMapMonocular (20 iterations, robust) and of
 LoopClosing::RunGlobalBundleAdjustment (10, not robust) on host arrays; bundle_adjustment_batch takes the same ragged device tensors
 and the same workspace as local_bundle_adjustment_batch (ba_kernels.hip: one optimize() call, no classification, no erase list).
+
+essential_graph is the call of LoopClosing::CorrectLoop on host arrays (Optimizer::OptimizeEssentialGraph, :1366: the Sim3 form, or
+the SE3 form with fix_scale); essential_graph_batch optimises ragged graphs that lie in device tensors in one launch
+(egraph_kernels.hip, one workgroup per graph) with a workspace of essential_graph_workspace_bytes(...) bytes, whose env_cap
+essential_graph_envelope_blocks(...) states per graph.  The vertex order is the elimination order: list keyframes by ascending mnId.
+The map correction behind it is sim3.correct_points.
 """
 from __future__ import annotations
 
@@ -27,13 +33,18 @@ import numpy as np
 from . import _lib
 from ._lib import BA_MAX_ITERATIONS, BA_RESULT_DTYPE, BA_ROBUST
 from ._lib import (LBA_DROPPED, LBA_EDGE_DTYPE, LBA_ERASE, LBA_FIRST_ROUND_ONLY, LBA_PROBLEM_DTYPE, LBA_RESULT_DTYPE)
+from ._lib import (EG_DONE, EG_EDGE_DTYPE, EG_FACTOR_FAILED, EG_FIX_SCALE, EG_LOOP_CONNECTION, EG_NORMAL, EG_PROBLEM_DTYPE, EG_REFUSED,
+                   EG_RESULT_DTYPE, EG_SIM3_DTYPE, EG_VERTEX_DTYPE)
 from ._lib import OPTSIM3_PAIR_DTYPE, OPTSIM3_RESULT_DTYPE, POSE_CAMERA_DTYPE, POSE_DISCARD, POSE_RESULT_DTYPE, SIM3_VIEW_DTYPE
 
 __all__ = ["POSE_CAMERA_DTYPE", "POSE_RESULT_DTYPE", "POSE_DISCARD", "pose_camera", "pose_optimization", "pose_optimization_batch",
            "OPTSIM3_PAIR_DTYPE", "OPTSIM3_RESULT_DTYPE", "sim3_view", "optimize_sim3", "optimize_sim3_batch",
            "LBA_EDGE_DTYPE", "LBA_PROBLEM_DTYPE", "LBA_RESULT_DTYPE", "LBA_FIRST_ROUND_ONLY", "LBA_ERASE", "LBA_DROPPED",
            "local_bundle_adjustment", "local_bundle_adjustment_batch", "lba_workspace_bytes",
-           "BA_RESULT_DTYPE", "BA_ROBUST", "BA_MAX_ITERATIONS", "bundle_adjustment", "bundle_adjustment_batch"]
+           "BA_RESULT_DTYPE", "BA_ROBUST", "BA_MAX_ITERATIONS", "bundle_adjustment", "bundle_adjustment_batch",
+           "EG_SIM3_DTYPE", "EG_VERTEX_DTYPE", "EG_EDGE_DTYPE", "EG_PROBLEM_DTYPE", "EG_RESULT_DTYPE", "EG_FIX_SCALE", "EG_NORMAL",
+           "EG_LOOP_CONNECTION", "EG_DONE", "EG_FACTOR_FAILED", "EG_REFUSED", "essential_graph", "essential_graph_batch",
+           "essential_graph_envelope_blocks", "essential_graph_workspace_bytes"]
 
 
 def pose_camera(fx, fy, cx, cy, mbf, inv_level_sigma2) -> np.ndarray:
@@ -205,3 +216,54 @@ def bundle_adjustment_batch(camera, problems, poses, fixed, points, edges, kf_ca
         int(point_cap), int(edge_cap), int(n_iterations), BA_ROBUST if robust else 0, _lib.ptr(poses_out), _lib.ptr(points_out),
         _lib.ptr(result), _lib.ptr(workspace), int(workspace.numel()) * int(workspace.element_size()), _lib.stream_handle(stream)),
         "orbfe_bundle_adjustment_batch_device")
+
+
+def essential_graph_envelope_blocks(n_kf: int, fixed, edges) -> int:
+    """orbfe_essential_graph_envelope_blocks: the blocks of the row envelope of a graph of n_kf vertices in their order; fixed:
+    (n_kf) uint8 or None, edges: EG_EDGE_DTYPE."""
+    edges = np.ascontiguousarray(edges, EG_EDGE_DTYPE).reshape(-1)
+    fixed = None if fixed is None else np.ascontiguousarray(fixed, np.uint8).reshape(-1)
+    if fixed is not None and len(fixed) != int(n_kf):
+        raise ValueError("fixed must have one entry per vertex")
+    n = C.c_int64(0)
+    _lib.check(_lib.lib().orbfe_essential_graph_envelope_blocks(int(n_kf), _lib.ptr(fixed) if fixed is not None and len(fixed) else None,
+                                                                _lib.ptr(edges) if len(edges) else None, len(edges), C.byref(n)),
+               "orbfe_essential_graph_envelope_blocks")
+    return int(n.value)
+
+
+def essential_graph_workspace_bytes(P: int, kf_cap: int, edge_cap: int, env_cap: int) -> int:
+    """orbfe_essential_graph_workspace_bytes: the workspace of a batch of P graphs of at most kf_cap vertices, edge_cap edges and
+    env_cap envelope blocks each."""
+    n = C.c_size_t(0)
+    _lib.check(_lib.lib().orbfe_essential_graph_workspace_bytes(int(P), int(kf_cap), int(edge_cap), int(env_cap), C.byref(n)),
+               "orbfe_essential_graph_workspace_bytes")
+    return int(n.value)
+
+
+def essential_graph(vertices, edges, fix_scale: bool = False):
+    """Optimizer::OptimizeEssentialGraph of one graph from its vertex and edge lists on.  vertices: EG_VERTEX_DTYPE (n_kf), ascending
+    by mnId; edges: EG_EDGE_DTYPE (n_edges); fix_scale: the SE3 form.  Returns (sim3_out, poses_out, result): EG_SIM3_DTYPE (n_kf), the
+    corrected Siw; (n_kf, 12) float32, rows of [R | t / s]; one EG_RESULT_DTYPE record."""
+    vertices = np.ascontiguousarray(vertices, EG_VERTEX_DTYPE).reshape(-1)
+    edges = np.ascontiguousarray(edges, EG_EDGE_DTYPE).reshape(-1)
+    sim3_out = np.zeros(len(vertices), EG_SIM3_DTYPE)
+    poses_out = np.zeros((len(vertices), 12), np.float32)
+    res = np.zeros(1, EG_RESULT_DTYPE)
+    opt = lambda a: _lib.ptr(a) if len(a) else None
+    _lib.check(_lib.lib().orbfe_essential_graph(opt(vertices), len(vertices), opt(edges), len(edges), EG_FIX_SCALE if fix_scale else 0,
+                                                opt(sim3_out), opt(poses_out), _lib.ptr(res)), "orbfe_essential_graph")
+    return sim3_out, poses_out, res[0]
+
+
+def essential_graph_batch(problems, vertices, edges, kf_cap, edge_cap, env_cap, sim3_out, poses_out, result, workspace,
+                          fix_scale: bool = False, stream=None):
+    """orbfe_essential_graph_batch_device on torch CUDA tensors: problems (P,16) u8 = EG_PROBLEM_DTYPE, vertices (K,136) u8 =
+    EG_VERTEX_DTYPE, edges (E,12) u8 = EG_EDGE_DTYPE; sim3_out (K,8) f64 = EG_SIM3_DTYPE, poses_out (K,12) f32, result (P,48) u8 =
+    EG_RESULT_DTYPE, workspace: u8 of at least essential_graph_workspace_bytes(P, kf_cap, edge_cap, env_cap) bytes.  fix_scale holds for
+    every problem.  Rows no problem names are not written.  stream: a torch.cuda.Stream, or None for the NULL stream."""
+    P = int(problems.shape[0])
+    _lib.check(_lib.lib().orbfe_essential_graph_batch_device(
+        P, _lib.ptr(problems), _lib.ptr(vertices), _lib.ptr(edges), int(kf_cap), int(edge_cap), int(env_cap),
+        EG_FIX_SCALE if fix_scale else 0, _lib.ptr(sim3_out), _lib.ptr(poses_out), _lib.ptr(result), _lib.ptr(workspace),
+        int(workspace.numel()) * int(workspace.element_size()), _lib.stream_handle(stream)), "orbfe_essential_graph_batch_device")

@@ -4,6 +4,10 @@ LoopClosing::ComputeSim3 between search_by_bow and the Sim3 search.
 sim3_solve evaluates H hypotheses of one problem on host arrays, sim3_solve_batch P problems in one launch pair on device tensors;
 both run sim3_kernels.hip, there is no CPU path.  The caller draws the triples (draw_triples) and owns the random state.  The
 solver's sequential surface -- iterate(n) in chunks, find -- is a cursor over the per-hypothesis counts: iterate_replay.
+
+correct_points is the map correction of LoopClosing::CorrectLoop and of Optimizer::OptimizeEssentialGraph: every point through
+to[ref]^-1 . from[ref] (egraph_kernels.hip, one thread per point); correct_points_device the same on device tensors, reading the
+sim3_out of optimizer.essential_graph_batch where it lies.
 """
 from __future__ import annotations
 
@@ -12,10 +16,12 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
+from ._lib import EG_SIM3_DTYPE
 from ._lib import SIM3_HYPOTHESIS_DTYPE, SIM3_PAIR_DTYPE, SIM3_RESULT_DTYPE, SIM3_VIEW_DTYPE
 
 __all__ = ["SIM3_VIEW_DTYPE", "SIM3_PAIR_DTYPE", "SIM3_HYPOTHESIS_DTYPE", "SIM3_RESULT_DTYPE", "sim3_view", "sim3_pairs", "max_error",
-           "ransac_iterations", "draw_triples", "iterate_replay", "sim3_solve", "sim3_solve_batch"]
+           "ransac_iterations", "draw_triples", "iterate_replay", "sim3_solve", "sim3_solve_batch", "EG_SIM3_DTYPE", "correct_points",
+           "correct_points_device"]
 
 
 def sim3_view(Rcw, tcw, fx, fy, cx, cy) -> np.ndarray:
@@ -126,3 +132,30 @@ def inlier_bits(words, n) -> np.ndarray:
     w = np.ascontiguousarray(words, np.uint64)
     bits = np.unpackbits(w.view(np.uint8).reshape(w.shape[:-1] + (-1,)), axis=-1, bitorder="little")
     return bits[..., :n].astype(bool)
+
+
+def correct_points(points, ref, sim3_from, sim3_to) -> np.ndarray:
+    """orbfe_sim3_correct_points: points (n, 3) float32; ref (n) int32, a row of the two tables or < 0 for a point that goes through;
+    sim3_from / sim3_to: EG_SIM3_DTYPE (n_tables), vScw and the corrected Siw.  Returns (n, 3) float32:
+    sim3_to[ref]^-1 .map( sim3_from[ref].map(P) ), rounded to float once."""
+    points = np.ascontiguousarray(np.asarray(points, np.float32).reshape(-1, 3))
+    ref = np.ascontiguousarray(ref, np.int32).reshape(-1)
+    a = np.ascontiguousarray(sim3_from, EG_SIM3_DTYPE).reshape(-1)
+    b = np.ascontiguousarray(sim3_to, EG_SIM3_DTYPE).reshape(-1)
+    if len(ref) != len(points) or len(a) != len(b):
+        raise ValueError("one ref per point and two tables of the same length")
+    out = np.zeros_like(points)
+    opt = lambda x: _lib.ptr(x) if len(x) else None
+    _lib.check(_lib.lib().orbfe_sim3_correct_points(opt(points), len(points), opt(ref), opt(a), opt(b), len(a), opt(out)),
+               "orbfe_sim3_correct_points")
+    return out
+
+
+def correct_points_device(points, ref, sim3_from, sim3_to, points_out, n_tables=None, stream=None):
+    """orbfe_sim3_correct_points_device on torch CUDA tensors: points (n,3) f32, ref (n) i32, sim3_from (K,8) f64 = EG_SIM3_DTYPE or
+    (K,136) u8 = EG_VERTEX_DTYPE (its Scw is read in place), sim3_to (K,8) f64, points_out (n,3) f32."""
+    stride = int(sim3_from.shape[1]) * int(sim3_from.element_size())
+    K = int(sim3_to.shape[0]) if n_tables is None else int(n_tables)
+    _lib.check(_lib.lib().orbfe_sim3_correct_points_device(_lib.ptr(points), int(points.shape[0]), _lib.ptr(ref), _lib.ptr(sim3_from), stride,
+                                                           _lib.ptr(sim3_to), K, _lib.ptr(points_out), _lib.stream_handle(stream)),
+               "orbfe_sim3_correct_points_device")
