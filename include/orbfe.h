@@ -111,6 +111,9 @@ int orbfe_device_download(void* h_dst, const void* d_src, size_t bytes);
  *   Sim3 optimisation   at most 9 500 correspondences per problem (orbfe_optimize_sim3, orbfe_optimize_sim3_batch_device: the frame
  *                       limit of the Sim3 search whose matches it reads), at most 65 535 problems per batch launch, th2 > 0
  *                       (pinned by tests/test_optsim3_cpu.py)
+ *   PnP solver          at most 1 024 correspondences and 4 096 hypotheses per problem (ORBFE_PNP_MAX_POINTS / _HYPOTHESES, each with
+ *                       its reason), minimal sets of four, min_inliers >= 4, at most 65 535 problems per batch launch (orbfe_pnp_solve,
+ *                       orbfe_pnp_solve_batch_device; pinned by tests/test_pnp_cpu.py)
  *   local bundle adj.   at most 64 free and 256 keyframes in all, 65 535 points and 262 140 edges per problem, 65 535 problems per
  *                       launch (the ORBFE_LBA_MAX_* constants, each with its reason; pinned by tests/test_lba_cpu.py and
  *                       tests/test_lba_gpu.py)
@@ -845,6 +848,107 @@ int orbfe_sim3_solve_batch_device(int P, const orbfe_sim3_view* d_view1, const o
                                   const int32_t* d_n, int cap, const int32_t* d_triples, const int32_t* d_H, int h_cap,
                                   const int32_t* d_fix_scale, const int32_t* d_min_inliers, orbfe_sim3_hypothesis* d_hyps,
                                   uint64_t* d_words, orbfe_sim3_result* d_result, uint64_t* d_result_mask, void* stream);
+
+/* ---- PnPsolver (L/src/PnPsolver.cc) -----------------------------------------------------------------------------------------------
+ * The RANSAC of Tracking::Relocalization (L/src/Tracking.cc:1258-1283) between orbfe_search_by_bow and orbfe_pose_optimization: a
+ * hypothesis is EPnP (compute_pose, :451-500) on four correspondences, its score the reprojection test of CheckInliers (:291-320);
+ * a hypothesis that becomes the best so far is refined by EPnP on all its inliers (Refine, :248-289).  All H hypotheses of a problem
+ * are independent, so one launch evaluates them all (one wave per hypothesis).  A failed refine is deterministic, so the refines
+ * that matter are those of the STRICT PREFIX MAXIMA of the count sequence with count >= min_inliers; a second launch evaluates
+ * them side by side, and a third applies the sequential rule of iterate (:205-243) to the counts and refine verdicts: find()
+ * returns the refined pose of the first prefix maximum whose refine has count > min_inliers, and without one the best hypothesis
+ * (the first with the maximal count) if that count is >= min_inliers.  iterate(n) in chunks is a cursor over the same records
+ * (refactored_orb_slam2_amd/pnp.py: iterate_replay).  The caller draws the minimal sets (:184-197; pnp.py: draw_minimal_sets) and
+ * sets the parameters (orbfe_pnp_ransac_parameters); the library holds no random state.
+ * csrc/pnp_internal.h states the arithmetic once: double where the reference is double (all of compute_pose), and the float
+ * roundings of CheckInliers where it rounds.  The legacy CvMat routines are not available where this library is built: symmetric
+ * eigenproblems (3x3 PCA, 12x12 MtM) go through this project's cyclic two-sided Jacobi in double, the 3x3 inverse, the 3x3 SVD of
+ * Horn's step and the three small least-squares solves through a one-sided Jacobi SVD without any threshold.
+ *   - With four points MtM has a four-dimensional null space and the four vectors an SVD returns for it are an arbitrary basis,
+ *     which the rest of EPnP depends on.  The basis this library chose is part of the interface: orbfe_pnp_diag exports it, with
+ *     the control points (whose PCA axes have a free sign each), so that a reading of the reference can continue from it.
+ *   - A coplanar or repeated set makes the third PCA eigenvalue 0 and the inverse 0 / 0: everything behind it is NaN, every
+ *     comparison of CheckInliers is false, n_inliers == 0 and the word row is all zero; the rest of the record is unspecified (it
+ *     may hold NaN).  Every iteration has a cap, nothing traps and no other record is touched.
+ * Deterministic: no atomics, a hypothesis' record depends on its problem and its minimal set only.  No CPU fallback. */
+#define ORBFE_PNP_MAX_POINTS 1024        /* correspondences of a problem: 24 bytes each, 24 KiB of the LDS a workgroup stages them
+                                            in beside its waves' workspaces; a relocalisation candidate has tens to hundreds */
+#define ORBFE_PNP_MAX_HYPOTHESES 4096    /* the reference never exceeds its maxIterations (300) */
+typedef struct orbfe_pnp_point {         /* one kept match (PnPsolver.cc:81-100) */
+  float Xw[3];                           /* pMP->GetWorldPos() */
+  float u, v;                            /* mvKeysUn[i].pt */
+  float max_err;                         /* mvLevelSigma2[octave] * th2 in float (:155) */
+} orbfe_pnp_point;                       /* 24 bytes */
+typedef struct orbfe_pnp_camera {
+  float fx, fy, cx, cy;                  /* the frame's floats; the solver widens them to double (:104-107) */
+} orbfe_pnp_camera;                      /* 16 bytes */
+typedef struct orbfe_pnp_hypothesis {
+  double R[9], t[3];                     /* mRi row-major, mti */
+  int32_t n_inliers;                     /* mnInliersi */
+  int32_t winner;                        /* 0, 1, 2: which of find_betas_approx_1 / _2 / _3 had the smallest reprojection error */
+  int32_t refine;                        /* row of its refine record (== its own index) when it is a strict prefix maximum with
+                                            count >= min_inliers, else -1 */
+  int32_t reserved;
+} orbfe_pnp_hypothesis;                  /* 112 bytes; all 0 (refine -1) for a set the device form rejects */
+typedef struct orbfe_pnp_refine {
+  double R[9], t[3];                     /* the pose of Refine() on the hypothesis' inliers */
+  int32_t n_inliers;                     /* mnRefinedInliers */
+  int32_t success;                       /* n_inliers > min_inliers (:277) */
+  int32_t winner;
+  int32_t n_used;                        /* correspondences the refine solved on (the hypothesis' count) */
+} orbfe_pnp_refine;                      /* 112 bytes; rows of hypotheses without a refine are not written */
+typedef struct orbfe_pnp_result {        /* what find() returns */
+  int32_t returned;                      /* the hypothesis at which find() returns: the first whose refine succeeds; at exhaustion the
+                                            best one if its count is >= min_inliers; else -1 */
+  int32_t refined;                       /* 1: Tcw / n_inliers are the refine record's of `returned`, 0: the hypothesis' own */
+  int32_t n_inliers;                     /* nInliers, 0 without a pose */
+  int32_t best;                          /* the first hypothesis with the maximal count >= min_inliers when find() ended, or -1 */
+  int32_t best_inliers;                  /* mnBestInliers */
+  int32_t reserved[3];
+  float Tcw[12];                         /* rows 0-2 of the returned matrix: the doubles rounded to float as convertTo does */
+} orbfe_pnp_result;                      /* 80 bytes */
+typedef struct orbfe_pnp_diag {          /* one compute_pose: the conventions it chose and what it derived from them */
+  double cws[12];                        /* the control points: centroid, then centroid + sqrt(d_k / n) * axis_k */
+  double V[48];                          /* v[0..3] (:727-730): unit vectors of the four smallest eigenvalues of MtM, smallest first */
+  double eig[5];                         /* their eigenvalues, and the fifth smallest */
+  double betas[12];                      /* Betas[1..3] after gauss_newton */
+  double rep_errors[3];                  /* rep_errors[1..3] */
+} orbfe_pnp_diag;                        /* 640 bytes */
+/* SetRansacParameters (:119-156) for N correspondences, except the error bounds.  *min_inliers_out = max((int)(N * epsilon),
+ * min_inliers, min_set) with the float product truncated, *epsilon_out = max(epsilon, (float)that / N), *iterations_out = 1 when
+ * that == N, else ceil(log(1 - probability) / log(1 - pow(epsilon, 3))) in double, then max(1, min(it, max_iterations)).  Pure host.
+ * ORBFE_ERR_INVALID: N < 1, min_inliers < 0, max_iterations < 0, min_set != 4, probability outside (0, 1), epsilon outside [0, 1],
+ * a null output. */
+int orbfe_pnp_ransac_parameters(int N, double probability, int min_inliers, int max_iterations, int min_set, float epsilon,
+                                int32_t* min_inliers_out, int32_t* iterations_out, float* epsilon_out);
+/* One problem.  HOST pointers, synchronous, on the calling thread's current device.  sets[4*h .. 4*h+3] index the points; min_set
+ * must be 4.  min_inliers is the adjusted value (orbfe_pnp_ransac_parameters).  Optional outputs (NULL skips them): hyps[H],
+ * words[H][ceil(n/64)], refines[H], refine_words[H][ceil(n/64)], diag[H], refine_diag[H]; rows of refines / refine_words /
+ * refine_diag are meaningful where hyps[h].refine == h and zero elsewhere.  Bit (i & 63) of word i / 64 is the verdict of point i,
+ * the tail bits of the last word are 0 and n_inliers is the popcount of the row.  result_mask[ceil(n/64)] is the word row that goes
+ * with result->Tcw (zeros without a pose).  n < min_inliers (:171-174): returned = best = -1, nothing is evaluated or launched, the
+ * optional outputs come back zero.  One packed upload, one packed download, one synchronisation.
+ * Limits (ORBFE_ERR_INVALID): 0 <= n <= ORBFE_PNP_MAX_POINTS, 0 <= H <= ORBFE_PNP_MAX_HYPOTHESES, min_inliers >= 4, min_set == 4, an
+ * index outside [0, n) or repeated within its set, null camera / result / result_mask, null points with n > 0 or sets with H > 0. */
+int orbfe_pnp_solve(const orbfe_pnp_camera* camera, const orbfe_pnp_point* points, int n, const int32_t* sets, int min_set, int H,
+                    int min_inliers, orbfe_pnp_hypothesis* hyps, uint64_t* words, orbfe_pnp_refine* refines, uint64_t* refine_words,
+                    orbfe_pnp_diag* diag, orbfe_pnp_diag* refine_diag, orbfe_pnp_result* result, uint64_t* result_mask);
+/* P problems in three launches.  DEVICE pointers, asynchronous on `stream` (NULL: the NULL stream).  Problem p: d_camera[p],
+ * d_min_inliers[p], point rows [p*cap, p*cap + d_n[p]), set rows [p*h_cap, p*h_cap + d_H[p]); it writes the same rows of d_hyps (and
+ * of d_refines / d_diag / d_refine_diag where a refine ran; d_diag and d_refine_diag may be NULL), the first ceil(d_n[p]/64) words of
+ * those rows of d_words / d_refine_words (row stride W = ceil(cap/64)), d_result[p] and the first ceil(d_n[p]/64) words of
+ * d_result_mask[p*W ..].  Counts are clamped to [0, cap] / [0, h_cap]; rows and words behind them are neither read nor written.  A
+ * set with an index outside [0, d_n[p]) or a repeated one yields an all-zero record (refine -1) and word row and reads nothing
+ * outside the problem.  A problem with fewer than 4 or than min_inliers points gets returned = best = -1 and nothing else.  A
+ * problem's bytes do not depend on P, on its position in the batch or on the run.
+ * Limits (ORBFE_ERR_INVALID): 0 <= P <= 65 535 (0: nothing is launched), 1 <= cap <= ORBFE_PNP_MAX_POINTS, 1 <= h_cap <=
+ * ORBFE_PNP_MAX_HYPOTHESES, null pointers, records not 8-byte aligned (d_camera / d_points / d_n / d_sets / d_H / d_min_inliers /
+ * d_result: 4-byte). */
+int orbfe_pnp_solve_batch_device(int P, const orbfe_pnp_camera* d_camera, const orbfe_pnp_point* d_points, const int32_t* d_n, int cap,
+                                 const int32_t* d_sets, const int32_t* d_H, int h_cap, const int32_t* d_min_inliers,
+                                 orbfe_pnp_hypothesis* d_hyps, uint64_t* d_words, orbfe_pnp_refine* d_refines, uint64_t* d_refine_words,
+                                 orbfe_pnp_diag* d_diag, orbfe_pnp_diag* d_refine_diag, orbfe_pnp_result* d_result,
+                                 uint64_t* d_result_mask, void* stream);
 
 /* ---- Optimizer::OptimizeSim3 (L/src/Optimizer.cc:1381-1573) ----------------------------------------------------------------------
  * The last step of LoopClosing::ComputeSim3 (L/src/LoopClosing.cc:224-322): the similarity S12 of orbfe_sim3_result and the matches

@@ -118,6 +118,21 @@ assert SIM3_VIEW_DTYPE.itemsize == 64 and SIM3_PAIR_DTYPE.itemsize == 32 and SIM
 assert SIM3_RESULT_DTYPE.itemsize == 128
 SIM3_MAX_PAIRS, SIM3_MAX_HYPOTHESES, SIM3_MAX_PROBLEMS = 1024, 4096, 65535
 SIM3_WAVES = 4   # hypotheses per workgroup of sim3_hypotheses_kernel (csrc/sim3_internal.h)
+# orbfe_pnp_point / orbfe_pnp_camera / orbfe_pnp_hypothesis / orbfe_pnp_refine / orbfe_pnp_result / orbfe_pnp_diag (PnPsolver, include/orbfe.h)
+PNP_POINT_DTYPE = np.dtype([("Xw", "<f4", (3,)), ("u", "<f4"), ("v", "<f4"), ("max_err", "<f4")])
+PNP_CAMERA_DTYPE = np.dtype([("fx", "<f4"), ("fy", "<f4"), ("cx", "<f4"), ("cy", "<f4")])
+PNP_HYPOTHESIS_DTYPE = np.dtype([("R", "<f8", (9,)), ("t", "<f8", (3,)), ("n_inliers", "<i4"), ("winner", "<i4"), ("refine", "<i4"),
+                                 ("reserved", "<i4")])
+PNP_REFINE_DTYPE = np.dtype([("R", "<f8", (9,)), ("t", "<f8", (3,)), ("n_inliers", "<i4"), ("success", "<i4"), ("winner", "<i4"),
+                             ("n_used", "<i4")])
+PNP_RESULT_DTYPE = np.dtype([("returned", "<i4"), ("refined", "<i4"), ("n_inliers", "<i4"), ("best", "<i4"), ("best_inliers", "<i4"),
+                             ("reserved", "<i4", (3,)), ("Tcw", "<f4", (12,))])
+PNP_DIAG_DTYPE = np.dtype([("cws", "<f8", (12,)), ("V", "<f8", (48,)), ("eig", "<f8", (5,)), ("betas", "<f8", (12,)),
+                           ("rep_errors", "<f8", (3,))])
+assert PNP_POINT_DTYPE.itemsize == 24 and PNP_CAMERA_DTYPE.itemsize == 16 and PNP_HYPOTHESIS_DTYPE.itemsize == 112
+assert PNP_REFINE_DTYPE.itemsize == 112 and PNP_RESULT_DTYPE.itemsize == 80 and PNP_DIAG_DTYPE.itemsize == 640
+PNP_MAX_POINTS, PNP_MAX_HYPOTHESES, PNP_MAX_PROBLEMS = 1024, 4096, 65535
+PNP_WAVES = 4   # hypotheses per workgroup of pnp_hypotheses_kernel (csrc/pnp_internal.h)
 # orbfe_init_params / orbfe_init_hypothesis / orbfe_init_candidate / orbfe_init_result (Initializer, include/orbfe.h)
 INIT_PARAMS_DTYPE = np.dtype([("fx", "<f4"), ("fy", "<f4"), ("cx", "<f4"), ("cy", "<f4"), ("sigma", "<f4"), ("min_parallax", "<f4"),
                               ("min_triangulated", "<i4"), ("reserved", "<i4")])
@@ -273,6 +288,7 @@ EXPORTS = [
     "orbfe_create_initial_map", "orbfe_initial_map_workspace_bytes", "orbfe_create_initial_map_batch_device",
     "orbfe_essential_graph_envelope_blocks", "orbfe_essential_graph", "orbfe_essential_graph_workspace_bytes",
     "orbfe_essential_graph_batch_device", "orbfe_sim3_correct_points", "orbfe_sim3_correct_points_device",
+    "orbfe_pnp_ransac_parameters", "orbfe_pnp_solve", "orbfe_pnp_solve_batch_device",
 ]
 
 
@@ -427,6 +443,9 @@ def lib():
     L.orbfe_essential_graph_batch_device.argtypes = [ci, vp, vp, vp, ci, ci, ci, ci, vp, vp, vp, vp, sz, vp]
     L.orbfe_sim3_correct_points.argtypes = [vp, ci, vp, vp, vp, ci, vp]
     L.orbfe_sim3_correct_points_device.argtypes = [vp, ci, vp, vp, ci, vp, ci, vp, vp]
+    L.orbfe_pnp_ransac_parameters.argtypes = [ci, C.c_double, ci, ci, ci, cf, vp, vp, vp]
+    L.orbfe_pnp_solve.argtypes = [vp, vp, ci, vp, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.orbfe_pnp_solve_batch_device.argtypes = [ci, vp, vp, vp, ci, vp, vp, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     for name in EXPORTS:
         if name != "orbfe_last_error":
             getattr(L, name).restype = ci
