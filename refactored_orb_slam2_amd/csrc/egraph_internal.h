@@ -62,17 +62,6 @@ __host__ __device__ inline OsSim3 eg_to_se3(const OsSim3& S) {
   return T;
 }
 
-// Eigen toRotationMatrix, row-major
-__host__ __device__ inline void eg_rotation(const PoseSE3& p, double* R) {
-  const double tx = 2.0 * p.qx, ty = 2.0 * p.qy, tz = 2.0 * p.qz;
-  const double twx = tx * p.qw, twy = ty * p.qw, twz = tz * p.qw;
-  const double txx = tx * p.qx, txy = ty * p.qx, txz = tz * p.qx;
-  const double tyy = ty * p.qy, tyz = tz * p.qy, tzz = tz * p.qz;
-  R[0] = 1.0 - (tyy + tzz); R[1] = txy - twz;         R[2] = txz + twy;
-  R[3] = txy + twz;         R[4] = 1.0 - (txx + tzz); R[5] = tyz - twx;
-  R[6] = txz - twy;         R[7] = tyz + twx;         R[8] = 1.0 - (txx + tyy);
-}
-
 // W.lu().solve(t): PartialPivLU of a 3 x 3 (the first largest |entry| of the column is the pivot), the unit lower solve, the upper
 // solve.  Rows are exchanged by comparisons, never through an index.
 __host__ __device__ inline void eg_lu_solve3(const double* W, const double* t, double* x) {
@@ -120,7 +109,7 @@ __host__ __device__ inline void eg_lu_solve3(const double* W, const double* t, d
 __host__ __device__ inline void eg_sim3_log(const OsSim3& S, double* res) {
   const double sigma = log(S.s);
   double R[9];
-  eg_rotation(S.q, R);
+  pose_rotation(S.q, R);
   const double d = 0.5 * (R[0] + R[4] + R[8] - 1);
   const double dR[3] = {R[7] - R[5], R[2] - R[6], R[3] - R[1]};   // deltaR
   const double eps = 0.00001;
@@ -177,7 +166,7 @@ __host__ __device__ inline void eg_sim3_log(const OsSim3& S, double* res) {
 // SE3Quat::log: omega, upsilon
 __host__ __device__ inline void eg_se3_log(const PoseSE3& p, double* res) {
   double R[9];
-  eg_rotation(p, R);
+  pose_rotation(p, R);
   const double d = 0.5 * (R[0] + R[4] + R[8] - 1);
   const double dR[3] = {R[7] - R[5], R[2] - R[6], R[3] - R[1]};
   double k, c2;
@@ -231,7 +220,7 @@ __host__ __device__ inline void eg_error_se3(const PoseSE3& C, const PoseSE3& Ti
 // sign * T.adj() into J, column-major 6 x 6: [R 0; skew(t) R  R]
 __host__ __device__ inline void eg_adj(const PoseSE3& T, bool negate, double* J) {
   double R[9];
-  eg_rotation(T, R);
+  pose_rotation(T, R);
   const double tR[9] = {-T.tz * R[3] + T.ty * R[6], -T.tz * R[4] + T.ty * R[7], -T.tz * R[5] + T.ty * R[8],
                         T.tz * R[0] - T.tx * R[6],  T.tz * R[1] - T.tx * R[7],  T.tz * R[2] - T.tx * R[8],
                         -T.ty * R[0] + T.tx * R[3], -T.ty * R[1] + T.tx * R[4], -T.ty * R[2] + T.tx * R[5]};
@@ -264,7 +253,7 @@ __host__ __device__ inline OsSim3 eg_oplus_se3(const OsSim3& T, const double* u)
 // One row of poses_out: [R | t / s] of the Sim3 path (`eigt *= (1. / s)`, Optimizer.cc:1003-1011), [R | t] of the SE3 path
 __host__ __device__ inline void eg_pose_row(const OsSim3& S, bool se3, float* T) {
   double R[9];
-  eg_rotation(S.q, R);
+  pose_rotation(S.q, R);
   const double k = 1. / S.s;
   T[0] = (float)R[0]; T[1] = (float)R[1]; T[2] = (float)R[2];
   T[4] = (float)R[3]; T[5] = (float)R[4]; T[6] = (float)R[5];

@@ -4,8 +4,11 @@
 // With HOST_LAYOUT_ONLY defined only the region arithmetic is declared, which needs no HIP header or runtime.
 #pragma once
 #include <assert.h>
+#include <math.h>
 #include <stddef.h>
 #include <stdint.h>
+
+#include <algorithm>
 
 // offsets at 256-byte boundaries of one block
 struct Layout {
@@ -36,6 +39,20 @@ struct HostLayout {
   size_t end[2] = {0, 0};   // of the input group, of the scratch group
   int group = 0;
 };
+
+// The iteration count of SetRansacParameters (Sim3Solver.cc:112-136, PnPsolver.cc:119-151), for minimal sets of three or four alike
+// (both files raise epsilon to the third power): 1 when every correspondence must be an inlier, else
+// ceil(log(1 - probability) / log(1 - epsilon^3)), clamped to 1 .. max_iterations.  pow(float, int) is double.  epsilon == 0 gives
+// log(1) == 0 and a quotient of -inf, epsilon >= 1 gives log(<= 0): the int conversion of the reference without its overflow -- below 1
+// (or NaN) the max() underneath decides, above max_iterations the min().
+inline int ransac_iterations(bool all_inliers, double probability, float epsilon, int max_iterations) {
+  int n_iterations = 1;
+  if (!all_inliers) {
+    const double v = ceil(log(1 - probability) / log(1 - pow(epsilon, 3)));
+    n_iterations = !(v >= 1.0) ? 1 : (v >= (double)max_iterations ? max_iterations : (int)v);
+  }
+  return std::max(1, std::min(n_iterations, max_iterations));
+}
 
 #ifndef HOST_LAYOUT_ONLY
 #include <hip/hip_runtime.h>

@@ -14,7 +14,8 @@
 // element in index order (zeros of a sparse factor included: x * 0 + y is y for finite x), a gemm with a scalar folded in multiplies
 // the float dot by the scalar in double, a gemm with an addend adds it in double, Mat::dot and cv::norm accumulate in double in
 // element order, `Mat / scalar` multiplies by (float)(1.0 / scalar).  `1.0 / x` assigned to a float divides in double.
-// What is not available where this library is built is stated here:
+// What is not available where this library is built is stated here; the rotation rule, its convergence test, the
+// sweep cap and the column pick of both decompositions are jacobi_internal.h's:
 //   cv::SVDecomp of the 16x9 / 8x9   ini_null9_*: one-sided (Hestenes) Jacobi in double on the float entries; a lane -- or, on the
 //                                    host, an array element -- holds one ROW of [A; V] as nine named doubles, the 36 column pairs of
 //                                    a sweep are written out, the three dot products of a pair are sums over the 16 rows of A in the
@@ -39,7 +40,7 @@
 #include "mapping_internal.h"   // tri_null_vector: the 4x4 of Triangulate
 
 #define INI_HD __host__ __device__ __forceinline__
-#define INI_JACOBI_SWEEPS 30   // cap; the 9 columns converge in 6-9 sweeps, a 3x3 in 3-5
+#define INI_JACOBI_EPS 0x1p-50  // "orthogonal to working precision" of float entries; the 9 columns converge in 6-9 sweeps, a 3x3 in 3-5
 #define INI_WAVES 4            // hypotheses (waves) per workgroup of initz_hypotheses_kernel
 #define INI_RT_THREADS 256     // of a CheckRT workgroup
 
@@ -135,16 +136,6 @@ INI_HD IniRow ini_row_v(int k) {
   r.c0 = k == 0; r.c1 = k == 1; r.c2 = k == 2; r.c3 = k == 3; r.c4 = k == 4; r.c5 = k == 5; r.c6 = k == 6; r.c7 = k == 7; r.c8 = k == 8;
   return r;
 }
-// The rotation that makes two columns with squared norms alpha, beta and dot product gamma orthogonal; false: they already are,
-// to working precision (also gamma == 0, nan)
-INI_HD bool ini_givens(double alpha, double beta, double gamma, double& c, double& s) {
-  if (!(fabs(gamma) > 0x1p-50 * sqrt(alpha * beta))) return false;
-  const double zeta = (beta - alpha) / (2.0 * gamma);
-  const double t = (zeta < 0.0 ? -1.0 : 1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
-  c = 1.0 / sqrt(1.0 + t * t);
-  s = c * t;
-  return true;
-}
 // the 36 pairs of a cyclic sweep, every index a literal
 #define INI_SWEEP(P)                                                                                                          \
   P(0, 1) P(0, 2) P(0, 3) P(0, 4) P(0, 5) P(0, 6) P(0, 7) P(0, 8) P(1, 2) P(1, 3) P(1, 4) P(1, 5) P(1, 6) P(1, 7) P(1, 8) P(2, 3) \
@@ -159,16 +150,6 @@ INI_HD void ini_null9_finish(const double* w, float* v) {
     if (fabs(w[k]) > m) { m = fabs(w[k]); sg = w[k] < 0.0 ? -1.0 : 1.0; }
 #pragma unroll
   for (int k = 0; k < 9; k++) v[k] = (float)(w[k] * sg);
-}
-// the first smallest of nine column norms as 0 / 1 weights (mapping_internal.h: tri_null_vector)
-INI_HD void ini_smallest9(const double* n, double* s) {
-  int j = 0;
-  double m = n[0];
-#pragma unroll
-  for (int k = 1; k < 9; k++)
-    if (n[k] < m) { m = n[k]; j = k; }
-#pragma unroll
-  for (int k = 0; k < 9; k++) s[k] = j == k ? 1.0 : 0.0;
 }
 
 #if defined(__HIP__)   // the translation unit is HIP: a kernel file
@@ -186,13 +167,13 @@ __device__ __forceinline__ double ini_sum16(double x) {
 // The wave form: lane l < 16 holds row l of A (zero rows behind the model's own), lane 16 + k row k of V = I, every other lane a
 // zero row.  All 64 lanes call it; v[9] is wave-uniform.
 __device__ __forceinline__ void ini_null9_wave(IniRow r, int lane, float* v) {
-  for (int sweep = 0; sweep < INI_JACOBI_SWEEPS; sweep++) {
+  for (int sweep = 0; sweep < JACOBI_SWEEPS; sweep++) {
     bool rotated = false;
 #define INI_PAIR(p, q)                                                                                                       \
   {                                                                                                                          \
     const double alpha = ini_sum16(r.c##p * r.c##p), beta = ini_sum16(r.c##q * r.c##q), gamma = ini_sum16(r.c##p * r.c##q); \
     double c, s;                                                                                                             \
-    if (ini_givens(alpha, beta, gamma, c, s)) {                                                                              \
+    if (jacobi_onesided_rotation(alpha, beta, gamma, INI_JACOBI_EPS, c, s)) {                                                \
       rotated = true;                                                                                                        \
       const double x = r.c##p;                                                                                               \
       r.c##p = c * x - s * r.c##q;                                                                                           \
@@ -207,7 +188,7 @@ __device__ __forceinline__ void ini_null9_wave(IniRow r, int lane, float* v) {
 #define INI_NORM(k) n[k] = ini_sum16(r.c##k * r.c##k);
   INI_COLUMNS(INI_NORM)
 #undef INI_NORM
-  ini_smallest9(n, s);
+  jacobi_first_min(n, s);
   double mine = 0.0;
 #define INI_TAKE(k) mine += r.c##k * s[k];
   INI_COLUMNS(INI_TAKE)
@@ -230,7 +211,7 @@ inline double ini_tree16(const double* x) {
 }
 inline void ini_null9_host(IniRow* rows, float* v) {
   double xa[16], xb[16], xg[16];
-  for (int sweep = 0; sweep < INI_JACOBI_SWEEPS; sweep++) {
+  for (int sweep = 0; sweep < JACOBI_SWEEPS; sweep++) {
     bool rotated = false;
 #define INI_PAIR(p, q)                                                                   \
   {                                                                                      \
@@ -239,8 +220,9 @@ inline void ini_null9_host(IniRow* rows, float* v) {
       xb[l] = rows[l].c##q * rows[l].c##q;                                               \
       xg[l] = rows[l].c##p * rows[l].c##q;                                               \
     }                                                                                    \
+    const double alpha = ini_tree16(xa), beta = ini_tree16(xb), gamma = ini_tree16(xg);  \
     double c, s;                                                                         \
-    if (ini_givens(ini_tree16(xa), ini_tree16(xb), ini_tree16(xg), c, s)) {              \
+    if (jacobi_onesided_rotation(alpha, beta, gamma, INI_JACOBI_EPS, c, s)) {            \
       rotated = true;                                                                    \
       for (int l = 0; l < 25; l++) {                                                     \
         const double x = rows[l].c##p;                                                   \
@@ -259,7 +241,7 @@ inline void ini_null9_host(IniRow* rows, float* v) {
   n[k] = ini_tree16(xa);
   INI_COLUMNS(INI_NORM)
 #undef INI_NORM
-  ini_smallest9(n, s);
+  jacobi_first_min(n, s);
   for (int k = 0; k < 9; k++) {
     double mine = 0.0;
 #define INI_TAKE(j) mine += rows[16 + k].c##j * s[j];
@@ -273,8 +255,9 @@ inline void ini_null9_host(IniRow* rows, float* v) {
 // ---- the 3x3 decomposition
 INI_HD bool ini_rot3(double& a0p, double& a1p, double& a2p, double& a0q, double& a1q, double& a2q, double& v0p, double& v1p, double& v2p,
                      double& v0q, double& v1q, double& v2q) {
+  const double alpha = a0p * a0p + a1p * a1p + a2p * a2p, beta = a0q * a0q + a1q * a1q + a2q * a2q, gamma = a0p * a0q + a1p * a1q + a2p * a2q;
   double c, s;
-  if (!ini_givens(a0p * a0p + a1p * a1p + a2p * a2p, a0q * a0q + a1q * a1q + a2q * a2q, a0p * a0q + a1p * a1q + a2p * a2q, c, s)) return false;
+  if (!jacobi_onesided_rotation(alpha, beta, gamma, INI_JACOBI_EPS, c, s)) return false;
   double x;
   x = a0p; a0p = c * x - s * a0q; a0q = s * x + c * a0q;
   x = a1p; a1p = c * x - s * a1q; a1q = s * x + c * a1q;
@@ -299,7 +282,7 @@ INI_HD void ini_swap_columns(bool swap, double& n0, double& b0, double& b1, doub
 INI_HD void ini_svd3(const float* A, float* U, float* w, float* Vt) {
   double a00 = A[0], a01 = A[1], a02 = A[2], a10 = A[3], a11 = A[4], a12 = A[5], a20 = A[6], a21 = A[7], a22 = A[8];
   double v00 = 1, v01 = 0, v02 = 0, v10 = 0, v11 = 1, v12 = 0, v20 = 0, v21 = 0, v22 = 1;
-  for (int sweep = 0; sweep < INI_JACOBI_SWEEPS; sweep++) {
+  for (int sweep = 0; sweep < JACOBI_SWEEPS; sweep++) {
     bool rotated = false;
     rotated |= ini_rot3(a00, a10, a20, a01, a11, a21, v00, v10, v20, v01, v11, v21);   // (0, 1)
     rotated |= ini_rot3(a00, a10, a20, a02, a12, a22, v00, v10, v20, v02, v12, v22);   // (0, 2)

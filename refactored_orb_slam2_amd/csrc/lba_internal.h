@@ -83,17 +83,6 @@ __host__ __device__ inline void lba_ws_carve(uint8_t* base, int F, int NP, int N
   W.pt_active = b;
 }
 
-// Eigen toRotationMatrix of the pose's quaternion
-__host__ __device__ inline void lba_rotation(const PoseSE3& p, double R[3][3]) {
-  const double tx = 2.0 * p.qx, ty = 2.0 * p.qy, tz = 2.0 * p.qz;
-  const double twx = tx * p.qw, twy = ty * p.qw, twz = tz * p.qw;
-  const double txx = tx * p.qx, txy = ty * p.qx, txz = tz * p.qx;
-  const double tyy = ty * p.qy, tyz = tz * p.qy, tzz = tz * p.qz;
-  R[0][0] = 1.0 - (tyy + tzz); R[0][1] = txy - twz; R[0][2] = txz + twy;
-  R[1][0] = txy + twz; R[1][1] = 1.0 - (txx + tzz); R[1][2] = tyz - twx;
-  R[2][0] = txz - twy; R[2][1] = tyz + twx; R[2][2] = 1.0 - (txx + tyy);
-}
-
 // computeError + chi2() of one edge: e[3] (e[2] = 0 for a monocular edge), the camera-frame point, returns chi2.  The stereo edge's
 // invz is `const double invz = 1.0f / z` here -- a double, unlike the pose-only edge's float
 __host__ __device__ inline double lba_edge_error(const orbfe_lba_edge& E, const PoseIntr& K, const PoseSE3& p, double X, double Y, double Z,
@@ -119,23 +108,23 @@ __host__ __device__ inline double lba_edge_error(const orbfe_lba_edge& E, const 
 // linearizeOplus of one edge at the camera-frame point (x, y, z): A (the point's rows) and B (the pose's); row 2 is the stereo edge's
 __host__ __device__ inline void lba_edge_jacobians(const PoseIntr& K, const PoseSE3& p, bool stereo, double x, double y, double z,
                                                    double A[3][3], double B[3][6]) {
-  double R[3][3];
-  lba_rotation(p, R);
+  double R[9];
+  pose_rotation(p, R);
   const double z_2 = z * z;
   if (stereo) {
 #pragma unroll
     for (int c = 0; c < 3; c++) {
-      A[0][c] = -K.fx * R[0][c] / z + K.fx * x * R[2][c] / z_2;
-      A[1][c] = -K.fy * R[1][c] / z + K.fy * y * R[2][c] / z_2;
-      A[2][c] = A[0][c] - K.bf * R[2][c] / z_2;
+      A[0][c] = -K.fx * R[c] / z + K.fx * x * R[6 + c] / z_2;
+      A[1][c] = -K.fy * R[3 + c] / z + K.fy * y * R[6 + c] / z_2;
+      A[2][c] = A[0][c] - K.bf * R[6 + c] / z_2;
     }
   } else {   // -1. / z * tmp * R, tmp = [[fx, 0, -x / z * fx], [0, fy, -y / z * fy]]
     const double m = -1. / z;
     const double t00 = m * K.fx, t02 = m * (-x / z * K.fx), t11 = m * K.fy, t12 = m * (-y / z * K.fy);
 #pragma unroll
     for (int c = 0; c < 3; c++) {
-      A[0][c] = t00 * R[0][c] + t02 * R[2][c];
-      A[1][c] = t11 * R[1][c] + t12 * R[2][c];
+      A[0][c] = t00 * R[c] + t02 * R[6 + c];
+      A[1][c] = t11 * R[3 + c] + t12 * R[6 + c];
       A[2][c] = 0.0;
     }
   }

@@ -15,16 +15,17 @@
 // glibc: both are evaluated in double and rounded to float, which is the correctly rounded float result except for double-rounding
 // cases, i.e. within an ulp of any faithful float libm.
 // cv::SVD is not available where this library is built; the null vector of the 4x4 comes from this project's own one-sided
-// Jacobi in double on the float matrix (tri_null_vector), rounded to float.  x3D does not depend on the sign of the vector.
+// Jacobi in double on the float matrix (tri_null_vector on jacobi_internal.h), rounded to float.  x3D does not depend on the sign of the vector.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
 
 #include "../../include/orbfe.h"
+#include "jacobi_internal.h"
 
 #define TRI_HD __host__ __device__ __forceinline__   // a call that is not inlined would pass the 4x4 through memory
-#define TRI_JACOBI_SWEEPS 30   // cap; a 4x4 converges in 4-6 sweeps
+#define TRI_JACOBI_EPS 0x1p-50   // "orthogonal to working precision" of the float 4x4; a 4x4 converges in 4-6 sweeps
 
 // ---- cv::Mat helpers (the evaluation order of frustum_kernels.hip)
 // (R^T * x)[r]: Rwc = Rcw.t(), then the gemm's float dot in index order (:196, :279)
@@ -60,10 +61,8 @@ TRI_HD bool tri_rotate(double& a0p, double& a1p, double& a2p, double& a3p, doubl
   const double alpha = a0p * a0p + a1p * a1p + a2p * a2p + a3p * a3p;
   const double beta = a0q * a0q + a1q * a1q + a2q * a2q + a3q * a3q;
   const double gamma = a0p * a0q + a1p * a1q + a2p * a2q + a3p * a3q;
-  if (!(fabs(gamma) > 0x1p-50 * sqrt(alpha * beta))) return false;   // orthogonal to working precision (also gamma == 0, nan)
-  const double zeta = (beta - alpha) / (2.0 * gamma);
-  const double t = (zeta < 0.0 ? -1.0 : 1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
-  const double c = 1.0 / sqrt(1.0 + t * t), s = c * t;
+  double c, s;
+  if (!jacobi_onesided_rotation(alpha, beta, gamma, TRI_JACOBI_EPS, c, s)) return false;
   double x;
   x = a0p; a0p = c * x - s * a0q; a0q = s * x + c * a0q;
   x = a1p; a1p = c * x - s * a1q; a1q = s * x + c * a1q;
@@ -84,7 +83,7 @@ TRI_HD void tri_null_vector(const float* A, float* v) {
   double a20 = A[8], a21 = A[9], a22 = A[10], a23 = A[11], a30 = A[12], a31 = A[13], a32 = A[14], a33 = A[15];
   double v00 = 1, v01 = 0, v02 = 0, v03 = 0, v10 = 0, v11 = 1, v12 = 0, v13 = 0;
   double v20 = 0, v21 = 0, v22 = 1, v23 = 0, v30 = 0, v31 = 0, v32 = 0, v33 = 1;
-  for (int sweep = 0; sweep < TRI_JACOBI_SWEEPS; sweep++) {
+  for (int sweep = 0; sweep < JACOBI_SWEEPS; sweep++) {
     bool rotated = false;
     rotated |= tri_rotate(a00, a10, a20, a30, a01, a11, a21, a31, v00, v10, v20, v30, v01, v11, v21, v31);   // (0, 1)
     rotated |= tri_rotate(a00, a10, a20, a30, a02, a12, a22, a32, v00, v10, v20, v30, v02, v12, v22, v32);   // (0, 2)
@@ -96,8 +95,8 @@ TRI_HD void tri_null_vector(const float* A, float* v) {
   }
   const double n0 = a00 * a00 + a10 * a10 + a20 * a20 + a30 * a30, n1 = a01 * a01 + a11 * a11 + a21 * a21 + a31 * a31;
   const double n2 = a02 * a02 + a12 * a12 + a22 * a22 + a32 * a32, n3 = a03 * a03 + a13 * a13 + a23 * a23 + a33 * a33;
-  // the first of equal norms.  The column is taken by 0 / 1 weights (exact: V's entries are finite, one weight is 1), not by selects
-  // or an index: nothing of V may live in scratch memory
+  // the first of equal norms, its column taken by 0 / 1 weights: jacobi_first_min written out (the call moves instructions of the
+  // kernel's tail, and this listing is held to the last line)
   int j = 0;
   double m = n0;
   if (n1 < m) { m = n1; j = 1; }

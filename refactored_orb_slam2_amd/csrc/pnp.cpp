@@ -23,16 +23,8 @@ extern "C" int orbfe_pnp_ransac_parameters(int N, double probability, int min_in
   if (n_min < min_inliers) n_min = min_inliers;
   if (n_min < min_set) n_min = min_set;
   if (epsilon < (float)n_min / N) epsilon = (float)n_min / N;
-  int n_iterations;
-  if (n_min == N) {
-    n_iterations = 1;
-  } else {
-    const double v = ceil(log(1 - probability) / log(1 - pow(epsilon, 3)));   // pow(float, int) is double; epsilon >= 1 gives log(<= 0)
-    // the reference's int conversion without its overflow: below 1 the max() underneath decides, above max_iterations the min()
-    n_iterations = !(v >= 1.0) ? 1 : (v >= (double)max_iterations ? max_iterations : (int)v);
-  }
   *min_inliers_out = n_min;
-  *iterations_out = std::max(1, std::min(n_iterations, max_iterations));
+  *iterations_out = ransac_iterations(n_min == N, probability, epsilon, max_iterations);
   *epsilon_out = epsilon;
   return ORBFE_OK;
 }

@@ -17,10 +17,10 @@
 // it, so both sides compute the same bits.
 //
 // The legacy CvMat routines are not available where this library is built:
-//   cvSVD of a symmetric matrix (PW0tPW0, MtM)   cyclic two-sided Jacobi in double: pnp_jacobi_serial for the 3x3, pnp_jacobi12 for
+//   cvSVD of a symmetric matrix (PW0tPW0, MtM)   cyclic two-sided Jacobi in double: jacobi_twosided_mem for the 3x3, pnp_jacobi12 for
 //                                                 the 12x12 (each of the 11 rounds of a sweep rotates six disjoint pairs in the
 //                                                 round-robin order, spread over the lanes); eigenvalues ordered by magnitude
-//   cvInvert(CV_SVD) 3x3, cvSolve(CV_SVD) 6xk,   one-sided (Hestenes) Jacobi on the columns, A = W V^T with orthogonal columns w_j:
+//   cvInvert(CV_SVD) 3x3, cvSolve(CV_SVD) 6xk,   one-sided (Hestenes) Jacobi on the columns (jacobi_onesided_mem), A = W V^T, orthogonal w_j:
 //   cvSVD of ABt                                  A^+ = V diag(1 / |w_j|^2) W^T, U V^T = sum_j (w_j / |w_j|) v_j^T.  On a full-column-
 //                                                 rank matrix that is the unique least-squares solution.  There is no threshold: a
 //                                                 zero singular value is 0 / 0 and what follows is NaN (a coplanar set).
@@ -32,10 +32,10 @@
 #include <stdint.h>
 
 #include "../../include/orbfe.h"
+#include "jacobi_internal.h"
 
 #define PNP_HD __host__ __device__ __forceinline__
-#define PNP_JACOBI_SWEEPS 30   // cap; the 12x12 converges in 8-12 sweeps, the small ones in 4-6
-#define PNP_EPS 0x1p-53
+#define PNP_EPS 0x1p-53   // both convergence tests; the 12x12 converges in 8-12 sweeps, the small ones in 4-6
 
 #if defined(__HIP_DEVICE_COMPILE__)
 // the lanes of one wave: LDS operations of a wave complete in order, the fences keep the compiler from moving them
@@ -89,71 +89,6 @@ PNP_HD bool pnp_is_inlier(const double* R, const double* t, const PnpCamera& K, 
   return error2 < p.max_err;
 }
 
-// c, s of the rotation that annihilates the coupling g of two entries a, b (a_pp, a_qq / |w_p|^2, |w_q|^2)
-PNP_HD void pnp_rotation(double a, double b, double g, double& c, double& s) {
-  const double theta = (b - a) / (2.0 * g);
-  const double t = (theta < 0.0 ? -1.0 : 1.0) / (fabs(theta) + sqrt(1.0 + theta * theta));
-  c = 1.0 / sqrt(1.0 + t * t);
-  s = c * t;
-}
-
-// cyclic two-sided Jacobi of a symmetric n x n in memory, one lane; V (n x n) receives the eigenvectors in its columns
-PNP_HD void pnp_jacobi_serial(double* A, double* V, int n) {
-  for (int i = 0; i < n * n; i++) V[i] = (i / n == i % n) ? 1.0 : 0.0;
-  for (int sweep = 0; sweep < PNP_JACOBI_SWEEPS; sweep++) {
-    bool rotated = false;
-    for (int p = 0; p < n - 1; p++)
-      for (int q = p + 1; q < n; q++) {
-        const double apq = A[p * n + q], app = A[p * n + p], aqq = A[q * n + q];
-        if (!(fabs(apq) > PNP_EPS * (fabs(app) + fabs(aqq)))) continue;
-        double c, s;
-        pnp_rotation(app, aqq, apq, c, s);
-        for (int k = 0; k < n; k++) {
-          double x = A[k * n + p], y = A[k * n + q];
-          A[k * n + p] = c * x - s * y; A[k * n + q] = s * x + c * y;
-          x = V[k * n + p]; y = V[k * n + q];
-          V[k * n + p] = c * x - s * y; V[k * n + q] = s * x + c * y;
-        }
-        for (int k = 0; k < n; k++) {
-          const double x = A[p * n + k], y = A[q * n + k];
-          A[p * n + k] = c * x - s * y; A[q * n + k] = s * x + c * y;
-        }
-        A[p * n + q] = 0.0; A[q * n + p] = 0.0;
-        rotated = true;
-      }
-    if (!rotated) break;
-  }
-}
-
-// one-sided Jacobi on the k columns of W (m x k, row-major): on return the columns are orthogonal and A = W V^T; one lane
-PNP_HD void pnp_svd_onesided(double* W, double* V, int m, int k) {
-  for (int i = 0; i < k * k; i++) V[i] = (i / k == i % k) ? 1.0 : 0.0;
-  for (int sweep = 0; sweep < PNP_JACOBI_SWEEPS; sweep++) {
-    bool rotated = false;
-    for (int p = 0; p < k - 1; p++)
-      for (int q = p + 1; q < k; q++) {
-        double alpha = 0.0, beta = 0.0, gamma = 0.0;
-        for (int r = 0; r < m; r++) {
-          const double x = W[r * k + p], y = W[r * k + q];
-          alpha += x * x; beta += y * y; gamma += x * y;
-        }
-        if (!(fabs(gamma) > PNP_EPS * sqrt(alpha * beta))) continue;
-        double c, s;
-        pnp_rotation(alpha, beta, gamma, c, s);
-        for (int r = 0; r < m; r++) {
-          const double x = W[r * k + p], y = W[r * k + q];
-          W[r * k + p] = c * x - s * y; W[r * k + q] = s * x + c * y;
-        }
-        for (int r = 0; r < k; r++) {
-          const double x = V[r * k + p], y = V[r * k + q];
-          V[r * k + p] = c * x - s * y; V[r * k + q] = s * x + c * y;
-        }
-        rotated = true;
-      }
-    if (!rotated) break;
-  }
-}
-
 // the pair j (0..5) of round r (0..10) of the round-robin order on 12 indices: index 11 stays, the others turn
 PNP_HD void pnp_round_pair(int r, int j, int& p, int& q) {
   int a, b;
@@ -168,7 +103,7 @@ PNP_HD void pnp_jacobi12(PnpWork* w, int lane, int nl) {
   double* A = w->A;
   double* V = w->V;
   for (int e = lane; e < 144; e += nl) V[e] = (e / 12 == e % 12) ? 1.0 : 0.0;
-  for (int sweep = 0; sweep < PNP_JACOBI_SWEEPS; sweep++) {
+  for (int sweep = 0; sweep < JACOBI_SWEEPS; sweep++) {
     if (lane == 0) w->rot = 0;
     PNP_SYNC();
     for (int r = 0; r < 11; r++) {
@@ -176,9 +111,9 @@ PNP_HD void pnp_jacobi12(PnpWork* w, int lane, int nl) {
         int p, q;
         pnp_round_pair(r, j, p, q);
         const double apq = A[p * 12 + q], app = A[p * 12 + p], aqq = A[q * 12 + q];
-        double c = 1.0, s = 0.0;
-        if (fabs(apq) > PNP_EPS * (fabs(app) + fabs(aqq))) {
-          pnp_rotation(app, aqq, apq, c, s);
+        double t, c = 1.0, s = 0.0;
+        if (!jacobi_diagonal(app, aqq, apq, PNP_EPS)) {
+          jacobi_rotation(app, aqq, apq, t, c, s);
           w->rot = 1;
         }
         w->cs[2 * j] = c; w->cs[2 * j + 1] = s;
@@ -238,7 +173,7 @@ PNP_HD void pnp_control_points(PnpWork* w, const orbfe_pnp_point* pts, const int
   }
   double* S = w->S;
   S[0] = s00; S[1] = s01; S[2] = s02; S[3] = s01; S[4] = s11; S[5] = s12; S[6] = s02; S[7] = s12; S[8] = s22;
-  pnp_jacobi_serial(S, w->SV, 3);
+  jacobi_twosided_mem(S, w->SV, 3, PNP_EPS, JACOBI_SWEEPS);
   // dc descending, uct rows = the eigenvectors (cvSVD orders singular values, i.e. magnitudes)
   int o0 = 0, o1 = 1, o2 = 2, x;
   if (fabs(S[4 * o1]) > fabs(S[4 * o0])) { x = o0; o0 = o1; o1 = x; }
@@ -253,7 +188,7 @@ PNP_HD void pnp_control_points(PnpWork* w, const orbfe_pnp_point* pts, const int
   // CC (:394-396), its inverse through A^+ = V diag(1 / |w_j|^2) W^T
   for (int i = 0; i < 3; i++)
     for (int j = 1; j < 4; j++) S[3 * i + j - 1] = w->cws[3 * j + i] - w->cws[i];
-  pnp_svd_onesided(S, w->SV, 3, 3);
+  jacobi_onesided_mem(S, w->SV, 3, 3, PNP_EPS, JACOBI_SWEEPS);
   double inv[3];
 #pragma unroll
   for (int j = 0; j < 3; j++) inv[j] = 1.0 / (S[j] * S[j] + S[3 + j] * S[3 + j] + S[6 + j] * S[6 + j]);
@@ -337,7 +272,7 @@ PNP_HD void pnp_start(PnpWork* w, const PnpCamera& K, const orbfe_pnp_point* pts
       const int col = s == 0 ? (j == 0 ? 0 : j == 1 ? 1 : j == 2 ? 3 : 6) : j;   // :639-642, :670-672, :702-706
       T.W[i * k + j] = L[10 * i + col];
     }
-  pnp_svd_onesided(T.W, T.Vk, 6, k);
+  jacobi_onesided_mem(T.W, T.Vk, 6, k, PNP_EPS, JACOBI_SWEEPS);
   for (int j = 0; j < k; j++) {
     double wr = 0.0, ww = 0.0;
     for (int r = 0; r < 6; r++) {
@@ -442,7 +377,7 @@ PNP_HD void pnp_start(PnpWork* w, const PnpCamera& K, const orbfe_pnp_point* pts
   }
 #pragma unroll
   for (int e = 0; e < 9; e++) T.W[e] = abt[e];
-  pnp_svd_onesided(T.W, T.Vk, 3, 3);   // ABt = W V^T; R = U V^T (:578-580)
+  jacobi_onesided_mem(T.W, T.Vk, 3, 3, PNP_EPS, JACOBI_SWEEPS);   // ABt = W V^T; R = U V^T (:578-580)
   double is[3];
 #pragma unroll
   for (int j = 0; j < 3; j++) is[j] = 1.0 / sqrt(T.W[j] * T.W[j] + T.W[3 + j] * T.W[3 + j] + T.W[6 + j] * T.W[6 + j]);

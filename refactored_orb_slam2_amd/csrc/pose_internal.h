@@ -97,25 +97,31 @@ __host__ __device__ inline PoseSE3 pose_from_Tcw(const float* T) {
   return p;
 }
 
-// Converter::toCvMat(SE3Quat): to_homogeneous_matrix (Eigen toRotationMatrix), double -> float
-__host__ __device__ inline void pose_to_Tcw(const PoseSE3& p, float* T) {
+// Eigen toRotationMatrix of the pose's quaternion, row-major with `stride` elements from row to row, each entry stored as a double or
+// rounded to float.  With `translation` the rows are those of [R | t].  The statements stand in the order of the stores: a caller's
+// listing depends on it.
+template <class T>
+__host__ __device__ inline void pose_rotation(const PoseSE3& p, T* R, int stride = 3, bool translation = false) {
   const double tx = 2.0 * p.qx, ty = 2.0 * p.qy, tz = 2.0 * p.qz;
   const double twx = tx * p.qw, twy = ty * p.qw, twz = tz * p.qw;
   const double txx = tx * p.qx, txy = ty * p.qx, txz = tz * p.qx;
   const double tyy = ty * p.qy, tyz = tz * p.qy, tzz = tz * p.qz;
-  T[0] = (float)(1.0 - (tyy + tzz));
-  T[1] = (float)(txy - twz);
-  T[2] = (float)(txz + twy);
-  T[3] = (float)p.tx;
-  T[4] = (float)(txy + twz);
-  T[5] = (float)(1.0 - (txx + tzz));
-  T[6] = (float)(tyz - twx);
-  T[7] = (float)p.ty;
-  T[8] = (float)(txz - twy);
-  T[9] = (float)(tyz + twx);
-  T[10] = (float)(1.0 - (txx + tyy));
-  T[11] = (float)p.tz;
+  R[0] = (T)(1.0 - (tyy + tzz));
+  R[1] = (T)(txy - twz);
+  R[2] = (T)(txz + twy);
+  if (translation) R[3] = (T)p.tx;
+  R[stride] = (T)(txy + twz);
+  R[stride + 1] = (T)(1.0 - (txx + tzz));
+  R[stride + 2] = (T)(tyz - twx);
+  if (translation) R[stride + 3] = (T)p.ty;
+  R[2 * stride] = (T)(txz - twy);
+  R[2 * stride + 1] = (T)(tyz + twx);
+  R[2 * stride + 2] = (T)(1.0 - (txx + tyy));
+  if (translation) R[2 * stride + 3] = (T)p.tz;
 }
+
+// Converter::toCvMat(SE3Quat): to_homogeneous_matrix, double -> float: the 12 floats of [R | t]
+__host__ __device__ inline void pose_to_Tcw(const PoseSE3& p, float* T) { pose_rotation(p, T, 4, true); }
 
 // Eigen _transformVector: uv = q.vec x v; uv += uv; v + w uv + q.vec x uv
 __host__ __device__ inline void pose_rotate(const PoseSE3& p, double vx, double vy, double vz, double* ox, double* oy, double* oz) {

@@ -18,15 +18,7 @@ extern "C" int orbfe_sim3_ransac_iterations(int N, double probability, int min_i
     return ORBFE_ERR_INVALID;
   }
   const float epsilon = (float)min_inliers / N;
-  int n_iterations;
-  if (min_inliers == N) {
-    n_iterations = 1;
-  } else {
-    const double v = ceil(log(1 - probability) / log(1 - pow(epsilon, 3)));   // epsilon == 0: log(1) == 0 and the quotient is -inf
-    // the reference's int conversion without its overflow: below 1 the max() underneath decides, above max_iterations the min()
-    n_iterations = !(v >= 1.0) ? 1 : (v >= (double)max_iterations ? max_iterations : (int)v);
-  }
-  return std::max(1, std::min(n_iterations, max_iterations));
+  return ransac_iterations(min_inliers == N, probability, epsilon, max_iterations);
 }
 
 extern "C" int orbfe_sim3_solve_batch_device(int P, const orbfe_sim3_view* d_view1, const orbfe_sim3_view* d_view2,

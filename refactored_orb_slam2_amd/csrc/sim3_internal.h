@@ -10,7 +10,7 @@
 // scalar in double, Mat::dot and cv::norm accumulate in double in element order.  What the file keeps in double stays double: the
 // ten sums of N (:241-250), ang (:266), nom / den (:282-294).
 // cv::eigen is not available where this library is built.  The eigenvector of the largest eigenvalue of the symmetric 4x4 N comes
-// from this project's own cyclic two-sided Jacobi in double on the float matrix (sim3_top_eigenvector), rounded to float as
+// from this project's own cyclic two-sided Jacobi in double on the float matrix (sim3_top_eigenvector on jacobi_internal.h), rounded to float as
 // cv::eigen's float output is.  q and -q give the same rotation through the atan2 form of :266-273 (the axis flips and the angle
 // 2 * ang becomes 2 * pi - 2 * ang), so the sign of the vector does not matter.  cv::Rodrigues works in double on the float vector and
 // rounds the matrix to float; so does sim3_rodrigues.
@@ -22,9 +22,10 @@
 #include <stdint.h>
 
 #include "../../include/orbfe.h"
+#include "jacobi_internal.h"
 
 #define SIM3_HD __host__ __device__ __forceinline__   // a call that is not inlined would pass the matrices through memory
-#define SIM3_JACOBI_SWEEPS 30   // cap; a symmetric 4x4 converges in 4-7 sweeps
+#define SIM3_JACOBI_EPS 0x1p-53   // "diagonal to working precision"; a symmetric 4x4 converges in 4-7 sweeps
 
 struct Sim3Prepared {   // one correspondence as iterate and CheckInliers read it: 48 bytes
   float c1[3], c2[3];   // mvX3Dc1[i], mvX3Dc2[i]
@@ -66,10 +67,9 @@ SIM3_HD void sim3_prepare(const orbfe_sim3_view& V1, const orbfe_sim3_view& V2, 
 // two other indices (a_pk, a_qk, a_pl, a_ql), plus columns p and q of V.  Returns whether it rotated.
 SIM3_HD bool sim3_rotate(double& app, double& aqq, double& apq, double& apk, double& aqk, double& apl, double& aql, double& v0p,
                          double& v1p, double& v2p, double& v3p, double& v0q, double& v1q, double& v2q, double& v3q) {
-  if (!(fabs(apq) > 0x1p-53 * (fabs(app) + fabs(aqq)))) return false;   // diagonal to working precision (also apq == 0, nan)
-  const double theta = (aqq - app) / (2.0 * apq);
-  const double t = (theta < 0.0 ? -1.0 : 1.0) / (fabs(theta) + sqrt(1.0 + theta * theta));
-  const double c = 1.0 / sqrt(1.0 + t * t), s = c * t;
+  if (jacobi_diagonal(app, aqq, apq, SIM3_JACOBI_EPS)) return false;
+  double t, c, s;
+  jacobi_rotation(app, aqq, apq, t, c, s);
   app -= t * apq;
   aqq += t * apq;
   apq = 0.0;
@@ -91,7 +91,7 @@ SIM3_HD void sim3_top_eigenvector(float n00, float n01, float n02, float n03, fl
   double a00 = n00, a01 = n01, a02 = n02, a03 = n03, a11 = n11, a12 = n12, a13 = n13, a22 = n22, a23 = n23, a33 = n33;
   double v00 = 1, v01 = 0, v02 = 0, v03 = 0, v10 = 0, v11 = 1, v12 = 0, v13 = 0;
   double v20 = 0, v21 = 0, v22 = 1, v23 = 0, v30 = 0, v31 = 0, v32 = 0, v33 = 1;
-  for (int sweep = 0; sweep < SIM3_JACOBI_SWEEPS; sweep++) {
+  for (int sweep = 0; sweep < JACOBI_SWEEPS; sweep++) {
     bool rotated = false;
     rotated |= sim3_rotate(a00, a11, a01, a02, a12, a03, a13, v00, v10, v20, v30, v01, v11, v21, v31);   // (0, 1)
     rotated |= sim3_rotate(a00, a22, a02, a01, a12, a03, a23, v00, v10, v20, v30, v02, v12, v22, v32);   // (0, 2)
@@ -101,17 +101,14 @@ SIM3_HD void sim3_top_eigenvector(float n00, float n01, float n02, float n03, fl
     rotated |= sim3_rotate(a22, a33, a23, a02, a03, a12, a13, v02, v12, v22, v32, v03, v13, v23, v33);   // (2, 3)
     if (!rotated) break;
   }
-  // the first of equal eigenvalues; the column is taken by 0 / 1 weights, not by an index (mapping_internal.h: tri_null_vector)
-  int j = 0;
-  double m = a00;
-  if (a11 > m) { m = a11; j = 1; }
-  if (a22 > m) { m = a22; j = 2; }
-  if (a33 > m) { m = a33; j = 3; }
-  const double s0 = j == 0 ? 1.0 : 0.0, s1 = j == 1 ? 1.0 : 0.0, s2 = j == 2 ? 1.0 : 0.0, s3 = j == 3 ? 1.0 : 0.0;
-  q[0] = (float)(v00 * s0 + v01 * s1 + v02 * s2 + v03 * s3);
-  q[1] = (float)(v10 * s0 + v11 * s1 + v12 * s2 + v13 * s3);
-  q[2] = (float)(v20 * s0 + v21 * s1 + v22 * s2 + v23 * s3);
-  q[3] = (float)(v30 * s0 + v31 * s1 + v32 * s2 + v33 * s3);
+  // the first of equal eigenvalues; the column is taken by 0 / 1 weights, not by an index
+  const double d[4] = {a00, a11, a22, a33};
+  double s[4];
+  jacobi_first_max(d, s);
+  q[0] = (float)(v00 * s[0] + v01 * s[1] + v02 * s[2] + v03 * s[3]);
+  q[1] = (float)(v10 * s[0] + v11 * s[1] + v12 * s[2] + v13 * s[3]);
+  q[2] = (float)(v20 * s[0] + v21 * s[1] + v22 * s[2] + v23 * s[3]);
+  q[3] = (float)(v30 * s[0] + v31 * s[1] + v32 * s[2] + v33 * s[3]);
 }
 
 // cv::Rodrigues of a float rotation vector into a float matrix: theta, the unit axis and the matrix in double, rounded once
