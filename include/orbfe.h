@@ -120,6 +120,9 @@ int orbfe_device_download(void* h_dst, const void* d_src, size_t bytes);
  *   bundle adjustment   the limits of the local bundle adjustment, and 1 .. 20 iterations (ORBFE_BA_MAX_ITERATIONS, with its reason;
  *                       orbfe_bundle_adjustment, orbfe_bundle_adjustment_batch_device; pinned by tests/test_ba_cpu.py and
  *                       tests/test_ba_gpu.py)
+ *   global bundle       ONE map of at most 2 048 keyframes (any number free), 1 048 575 points and 8 388 600 edges, 1 .. 20
+ *   adjustment          iterations (the ORBFE_GBA_MAX_* constants, each with its reason; orbfe_global_bundle_adjustment,
+ *                       orbfe_global_bundle_adjustment_device; pinned by tests/test_gba_cpu.py and tests/test_gba_gpu.py)
  *   initial map         at most 4 096 keypoints a frame (ORBFE_INIT_MAX_MATCHES) and 65 535 problems per launch, 1 .. 20 iterations,
  *                       q >= 1, min_points >= 0 (orbfe_create_initial_map, orbfe_create_initial_map_batch_device; pinned by
  *                       tests/test_ba_cpu.py and tests/test_ba_gpu.py)
@@ -1136,6 +1139,59 @@ int orbfe_bundle_adjustment_batch_device(int P, const orbfe_pose_camera* d_camer
                                          const orbfe_lba_edge* d_edges, int kf_cap, int point_cap, int edge_cap, int n_iterations,
                                          int flags, float* d_poses_out, float* d_points_out, orbfe_ba_result* d_result,
                                          void* d_workspace, size_t workspace_bytes, void* stream);
+
+/* ---- Global bundle adjustment beyond one workgroup (LoopClosing::RunGlobalBundleAdjustment's call of BundleAdjustment) ----------------
+ * The same function, graph, records, edge order, arithmetic (csrc/lba_internal.h) and result record as orbfe_bundle_adjustment, for
+ * ONE map too large for one workgroup: every phase of a trial is a launch over the whole device (csrc/gba_kernels.hip), the
+ * reduced system is factored by a blocked dense L L^T over tiles of ORBFE_GBA_TILE_KEYFRAMES row blocks, and a one-workgroup
+ * control kernel keeps the Levenberg bookkeeping on the device.  Every sum keeps the owner and the order of the one-workgroup form,
+ * so a problem within the ORBFE_LBA_MAX_* limits gives the same bytes from both (pinned by tests/test_gba_gpu.py).
+ * The host reads one control record per trial (pinned memory, one stream synchronisation) and enqueues the next trial's launches:
+ * BOTH forms below are therefore SYNCHRONOUS on their stream -- they return when the outputs are written.
+ * Not taken over: the stop flag is not read between iterations; no fill-reducing ordering; one problem per call.
+ * Deterministic: no floating-point atomics; no CPU fallback.
+ * Limits, each refused with ORBFE_ERR_INVALID one step past it, before a device is looked for (pinned by tests/test_gba_cpu.py):
+ *   ORBFE_GBA_MAX_KEYFRAMES   2 048 keyframes, free and fixed: the reduced system of 12 288 unknowns is 1.2 GB of workspace
+ *   ORBFE_GBA_MAX_POINTS      1 048 575 points: 277 MB of per-point blocks
+ *   ORBFE_GBA_MAX_EDGES       8 388 600 edges (eight per point at the point cap): 4.3 GB of per-edge blocks, and every edge index
+ *                             times the widest per-edge record stays an int
+ *   ORBFE_BA_MAX_ITERATIONS   as above
+ * and a constant that is NOT a limit, stated so that tests can stand on its edges:
+ *   ORBFE_GBA_TILE_KEYFRAMES  8 row blocks (48 rows) per tile of the factorisation: three tiles of doubles fit the 64 KB of LDS a
+ *                             workgroup gets without asking, and 16 x 16 lanes hold 3 x 3 entries each */
+#define ORBFE_GBA_MAX_KEYFRAMES 2048
+#define ORBFE_GBA_MAX_POINTS 1048575
+#define ORBFE_GBA_MAX_EDGES 8388600
+#define ORBFE_GBA_TILE_KEYFRAMES 8
+/* One problem.  HOST pointers, synchronous, on the calling thread's current device.  Arguments, result record and validation rules
+ * as orbfe_bundle_adjustment's (edges in any order, sorted here as there; the same pair twice is refused), against the limits above:
+ * any number of the keyframes may be free.  The workspace is allocated for the call.
+ * Limits (ORBFE_ERR_INVALID): 0 <= n_kf <= ORBFE_GBA_MAX_KEYFRAMES, 0 <= n_points <= ORBFE_GBA_MAX_POINTS, 0 <= n_edges <=
+ * ORBFE_GBA_MAX_EDGES, 1 <= n_iterations <= ORBFE_BA_MAX_ITERATIONS, flags outside ORBFE_BA_ROBUST, every edge's kf and point in
+ * range, inv_sigma2 finite and > 0. */
+int orbfe_global_bundle_adjustment(const orbfe_pose_camera* camera, const float* poses, const uint8_t* fixed, int n_kf,
+                                   const float* points, int n_points, const orbfe_lba_edge* edges, int n_edges, int n_iterations,
+                                   int flags, float* poses_out, float* points_out, orbfe_ba_result* result);
+/* The workspace of one problem of at most kf_cap keyframes, point_cap points and edge_cap edges.  HOST pointer.
+ * Limits (ORBFE_ERR_INVALID): the caps >= 0 and within the ORBFE_GBA_MAX_*, null bytes. */
+int orbfe_gba_workspace_bytes(int kf_cap, int point_cap, int edge_cap, size_t* bytes);
+/* One problem from arrays in HBM.  DEVICE pointers; SYNCHRONOUS on `stream` (NULL: the NULL stream), see above.  d_points: records
+ * of point_stride bytes that start with the position; d_edges: point by point, keyframes ascending, as the batch forms take them;
+ * d_result: one record in HBM.  A problem whose edge list breaks that rule, names an index out of range or carries an inv_sigma2
+ * that is not finite and > 0 is refused on the device: rounds = -1, poses and points copied through, nothing else written.
+ * d_workspace: workspace_bytes >= what orbfe_gba_workspace_bytes states for (n_kf, n_points, n_edges), 256-byte aligned; its
+ * contents do not matter and are not kept.  Inputs are not modified.
+ * Limits (ORBFE_ERR_INVALID): as orbfe_global_bundle_adjustment, point_stride >= 12 and a multiple of 4, records 4-byte aligned,
+ * d_result 8-byte, null pointers (the arrays of a count of 0 may be null). */
+int orbfe_global_bundle_adjustment_device(const orbfe_pose_camera* d_camera, const float* d_poses, const uint8_t* d_fixed, int n_kf,
+                                          const uint8_t* d_points, int point_stride, int n_points, const orbfe_lba_edge* d_edges,
+                                          int n_edges, int n_iterations, int flags, float* d_poses_out, float* d_points_out,
+                                          orbfe_ba_result* d_result, void* d_workspace, size_t workspace_bytes, void* stream);
+/* Measurement only (tools/gba_rate.py): copies the calling thread's sums of stream-event times per phase, in milliseconds, to ms
+ * (7 floats: plan, build, Dinv / Schur, factorisation, solves, update / chi2, control read-back; NULL: not copied), clears them, and
+ * switches the timing of this thread's later calls of the two forms above on (enable != 0) or off.  Timing synchronises the stream
+ * after every phase: the sums are the phases' device times, and a timed call is slower than an untimed one. */
+int orbfe_debug_gba_phases(int enable, float* ms);
 
 /* ---- KeyFrameDatabase (L/src/KeyFrameDatabase.cc, D/src/ScoringObject.cpp: L1) -----------------------------------------------------
  * The first step of both place-recognition chains: DetectRelocalizationCandidates in front of orbfe_search_by_bow .. the pose

@@ -26,7 +26,9 @@
 //   Map:      mMutexMapUpdate
 //
 // BundleAdjustment and GlobalBundleAdjustemnt (Optimizer.cc:43-231) are the adapters for orbfe_bundle_adjustment, with the
-// reference's signatures, unit-tested by tests/cpp_ba.  Members used beyond the above:
+// reference's signatures, unit-tested by tests/cpp_ba.  A host that defines ORBFE_HOST_GLOBAL_BA_ACROSS_DEVICE before it includes
+// this header gets, for a map beyond the ORBFE_LBA_MAX_* limits of that one-workgroup form, orbfe_global_bundle_adjustment instead
+// of the refusal (unit-tested by tests/cpp_gba); the default keeps what every existing host sees.  Members used beyond the above:
 //   KeyFrame: mTcwGBA, mnBAGlobalForKF
 //   MapPoint: mPosGBA, mnBAGlobalForKF
 //   Map:      GetAllKeyFrames(), GetAllMapPoints()
@@ -477,8 +479,20 @@ void BundleAdjustment(const std::vector<KeyFrameT*>& vpKFs, const std::vector<Ma
   const int n_kf = (int)B.vpKF.size(), n_points = (int)B.vpMP.size(), n_edges = (int)B.edges.size();
   std::vector<float> poses_out(B.poses.size()), points_out(B.points.size());
   orbfe_ba_result res;
-  const int rc = orbfe_bundle_adjustment(&B.cam, B.poses.data(), B.fixed.data(), n_kf, B.points.data(), n_points, B.edges.data(), n_edges,
-                                         nIterations, bRobust ? ORBFE_BA_ROBUST : 0, poses_out.data(), points_out.data(), &res);
+  // Without ORBFE_HOST_GLOBAL_BA_ACROSS_DEVICE every map goes to the one-workgroup form, which refuses one beyond its limits, as
+  // before (tests/cpp_ba pins that).  With it, a map within the ORBFE_LBA_MAX_* limits still goes there and any other to the form
+  // that spreads one problem over the device (profiles/global_bundle_adjustment.md has both on one scene at the limit)
+#ifdef ORBFE_HOST_GLOBAL_BA_ACROSS_DEVICE
+  int n_free = 0;
+  for (const uint8_t f : B.fixed) n_free += f ? 0 : 1;
+  const bool one_workgroup = n_free <= ORBFE_LBA_MAX_FREE && n_kf <= ORBFE_LBA_MAX_KEYFRAMES && n_points <= ORBFE_LBA_MAX_POINTS &&
+                             n_edges <= ORBFE_LBA_MAX_EDGES;
+#else
+  const bool one_workgroup = true;
+#endif
+  const int rc = (one_workgroup ? orbfe_bundle_adjustment : orbfe_global_bundle_adjustment)(
+      &B.cam, B.poses.data(), B.fixed.data(), n_kf, B.points.data(), n_points, B.edges.data(), n_edges, nIterations,
+      bRobust ? ORBFE_BA_ROBUST : 0, poses_out.data(), points_out.data(), &res);
   if (rc != ORBFE_OK) {
     fprintf(stderr, "orbfe BundleAdjustment: %s (code %d)\n", orbfe_last_error(), rc);
     return;

@@ -32,6 +32,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import BA_MAX_ITERATIONS, BA_RESULT_DTYPE, BA_ROBUST
+from ._lib import GBA_MAX_EDGES, GBA_MAX_KEYFRAMES, GBA_MAX_POINTS, GBA_TILE_KEYFRAMES
 from ._lib import (LBA_DROPPED, LBA_EDGE_DTYPE, LBA_ERASE, LBA_FIRST_ROUND_ONLY, LBA_PROBLEM_DTYPE, LBA_RESULT_DTYPE)
 from ._lib import (EG_DONE, EG_EDGE_DTYPE, EG_FACTOR_FAILED, EG_FIX_SCALE, EG_LOOP_CONNECTION, EG_NORMAL, EG_PROBLEM_DTYPE, EG_REFUSED,
                    EG_RESULT_DTYPE, EG_SIM3_DTYPE, EG_VERTEX_DTYPE)
@@ -42,6 +43,8 @@ __all__ = ["POSE_CAMERA_DTYPE", "POSE_RESULT_DTYPE", "POSE_DISCARD", "pose_camer
            "LBA_EDGE_DTYPE", "LBA_PROBLEM_DTYPE", "LBA_RESULT_DTYPE", "LBA_FIRST_ROUND_ONLY", "LBA_ERASE", "LBA_DROPPED",
            "local_bundle_adjustment", "local_bundle_adjustment_batch", "lba_workspace_bytes",
            "BA_RESULT_DTYPE", "BA_ROBUST", "BA_MAX_ITERATIONS", "bundle_adjustment", "bundle_adjustment_batch",
+           "GBA_MAX_KEYFRAMES", "GBA_MAX_POINTS", "GBA_MAX_EDGES", "GBA_TILE_KEYFRAMES", "global_bundle_adjustment",
+           "global_bundle_adjustment_device", "gba_workspace_bytes",
            "EG_SIM3_DTYPE", "EG_VERTEX_DTYPE", "EG_EDGE_DTYPE", "EG_PROBLEM_DTYPE", "EG_RESULT_DTYPE", "EG_FIX_SCALE", "EG_NORMAL",
            "EG_LOOP_CONNECTION", "EG_DONE", "EG_FACTOR_FAILED", "EG_REFUSED", "essential_graph", "essential_graph_batch",
            "essential_graph_envelope_blocks", "essential_graph_workspace_bytes"]
@@ -216,6 +219,47 @@ def bundle_adjustment_batch(camera, problems, poses, fixed, points, edges, kf_ca
         int(point_cap), int(edge_cap), int(n_iterations), BA_ROBUST if robust else 0, _lib.ptr(poses_out), _lib.ptr(points_out),
         _lib.ptr(result), _lib.ptr(workspace), int(workspace.numel()) * int(workspace.element_size()), _lib.stream_handle(stream)),
         "orbfe_bundle_adjustment_batch_device")
+
+
+def global_bundle_adjustment(camera, poses, fixed, points, edges, n_iterations: int = 5, robust: bool = True):
+    """orbfe_global_bundle_adjustment: bundle_adjustment for ONE map of up to GBA_MAX_KEYFRAMES keyframes, any number of them free,
+    across the whole device.  Arguments and return value as bundle_adjustment's; a problem both take gives the same bytes."""
+    cam = np.ascontiguousarray(camera, POSE_CAMERA_DTYPE).reshape(1)
+    poses = np.ascontiguousarray(np.asarray(poses, np.float32).reshape(-1, 12))
+    fixed = np.ascontiguousarray(fixed, np.uint8).reshape(-1)
+    points = np.ascontiguousarray(np.asarray(points, np.float32).reshape(-1, 3))
+    edges = np.ascontiguousarray(edges, LBA_EDGE_DTYPE).reshape(-1)
+    if len(fixed) != len(poses):
+        raise ValueError("poses and fixed must have one entry per keyframe")
+    poses_out, points_out = np.zeros_like(poses), np.zeros_like(points)
+    res = np.zeros(1, BA_RESULT_DTYPE)
+    opt = lambda a: _lib.ptr(a) if len(a) else None
+    _lib.check(_lib.lib().orbfe_global_bundle_adjustment(_lib.ptr(cam), opt(poses), opt(fixed), len(poses), opt(points), len(points),
+                                                         opt(edges), len(edges), int(n_iterations), BA_ROBUST if robust else 0,
+                                                         opt(poses_out), opt(points_out), _lib.ptr(res)), "orbfe_global_bundle_adjustment")
+    return poses_out, points_out, res[0]
+
+
+def gba_workspace_bytes(kf_cap: int, point_cap: int, edge_cap: int) -> int:
+    """orbfe_gba_workspace_bytes: the workspace of one problem of at most kf_cap keyframes, point_cap points and edge_cap edges."""
+    n = C.c_size_t(0)
+    _lib.check(_lib.lib().orbfe_gba_workspace_bytes(int(kf_cap), int(point_cap), int(edge_cap), C.byref(n)), "orbfe_gba_workspace_bytes")
+    return int(n.value)
+
+
+def global_bundle_adjustment_device(camera, poses, fixed, points, edges, poses_out, points_out, result, workspace, n_iterations: int = 5,
+                                    robust: bool = True, stream=None):
+    """orbfe_global_bundle_adjustment_device on torch CUDA tensors: camera (88) u8 = one POSE_CAMERA_DTYPE record, poses (K,12) f32,
+    fixed (K) u8, points (M,stride) u8 whose records start with the position (or (M,3) f32), edges (E,24) u8 = LBA_EDGE_DTYPE, listed
+    point by point with keyframes ascending; poses_out (K,12) f32, points_out (M,3) f32, result (40) u8 = one BA_RESULT_DTYPE record,
+    workspace: u8 of at least gba_workspace_bytes(K, M, E) bytes.  Synchronous on `stream` (a torch.cuda.Stream, or None for the NULL
+    stream): the host reads one control record per trial."""
+    stride = int(points.shape[1]) * int(points.element_size()) if points.dim() == 2 else 12
+    _lib.check(_lib.lib().orbfe_global_bundle_adjustment_device(
+        _lib.ptr(camera), _lib.ptr(poses), _lib.ptr(fixed), int(poses.shape[0]), _lib.ptr(points), stride, int(points.shape[0]),
+        _lib.ptr(edges), int(edges.shape[0]), int(n_iterations), BA_ROBUST if robust else 0, _lib.ptr(poses_out), _lib.ptr(points_out),
+        _lib.ptr(result), _lib.ptr(workspace), int(workspace.numel()) * int(workspace.element_size()), _lib.stream_handle(stream)),
+        "orbfe_global_bundle_adjustment_device")
 
 
 def essential_graph_envelope_blocks(n_kf: int, fixed, edges) -> int:
