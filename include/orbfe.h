@@ -1588,6 +1588,87 @@ int orbfe_bow_transform_device(orbfe_vocabulary* v, const uint8_t* d_desc, int n
 int orbfe_compute_bow(orbfe_vocabulary* v, const uint8_t* desc, int n, int levelsup, int32_t* word_id,
                       int32_t* node_id, double* weight, int32_t* bow_ids, double* bow_vals, int* n_bow,
                       orbfe_featvec_node* fv_nodes, int32_t* fv_idx, int* n_fv_nodes);
+/* A handle's tree in the layout orbfe_vocabulary_create takes (orbfe_vocabulary_info gives n_nodes); every output is optional.
+ * For this and the two save functions EVERY handle, loaded ones included, keeps a host copy of its tree beside the device arrays:
+ * 45 bytes per node, about 48 MB for ORBvoc.txt. */
+int orbfe_vocabulary_nodes(const orbfe_vocabulary* v, int32_t* parent, uint8_t* is_leaf, uint8_t* desc, double* weight);
+/* ORBVocabulary::saveToTextFile / saveToBinaryFile (L/src/ORBVocabulary.cc:131-150, :217-243) of a tree given as arrays; host only, no
+ * device needed.  The binary file is the reference's byte for byte (float weights).  The text file is what loadFromTextFile and
+ * orbfe_vocabulary_load_text read; DEVIATION: the weight is written with 17 significant digits so that it reads back as the same
+ * double, where the reference's stream writes six and loses the rest. */
+int orbfe_vocabulary_write_text(const char* path, int k, int L, int scoring, int weighting, int n_nodes, const int32_t* parent,
+                                const uint8_t* is_leaf, const uint8_t* desc, const double* weight);
+int orbfe_vocabulary_write_binary(const char* path, int k, int L, int scoring, int weighting, int n_nodes, const int32_t* parent,
+                                  const uint8_t* is_leaf, const uint8_t* desc, const double* weight);
+/* export, then write */
+int orbfe_vocabulary_save_text(const orbfe_vocabulary* v, const char* path);
+int orbfe_vocabulary_save_binary(const orbfe_vocabulary* v, const char* path);
+
+/* ------------------------------------------------------------------- DBoW2::TemplatedVocabulary::create on the device */
+/* Trains a vocabulary from descriptors: hierarchical k-medians in Hamming space with k-means++ seeding, the bit-majority mean
+ * (FORB::meanValue) and IDF weights -- HKmeansStep, initiateClustersKMpp, createWords and setNodeWeights of
+ * Source/ThirdParty/DBoW2/DBoW2-local/include/DBoW2/TemplatedVocabulary.h:640-994 in their literal form.  Every value is an integer
+ * (or a double that is exact), so the tree equals a plain reading of the reference bit for bit; the weights are log((double)NDocs /
+ * Ni) with the host's libm, Ni from the full transform descent of every training feature over the finished tree, NDocs counting
+ * empty images too; TF and BINARY give every word weight 1; inner nodes have weight 0, and so has a word with Ni == 0.
+ * A node with n <= k features is one cluster per feature, in order; a child is clustered only below level L and with more than one
+ * member, so leaves above level L are normal.  Node ids are the reference's creation order (a node's children get consecutive ids
+ * when the node is processed; nodes are processed depth first), word ids count leaves in id order.
+ * Three DEVIATIONS from the reference:
+ *   1. draws          the reference pulls rand() lazily from one stream in depth-first order; the number of draws per node depends
+ *                     on the data, which a level-parallel schedule cannot reproduce.  Each node takes its draws from a counter-based
+ *                     generator keyed by (seed, level, path, j): level = the current_level of its HKmeansStep (1 for the root's),
+ *                     path = the base-k number of the child indices from the root (0 for the root), j = the node's draw counter,
+ *                     0 for the first centre; a cut of 0.0 is drawn again with the next j.  The value is
+ *                     splitmix64(splitmix64(splitmix64(splitmix64(seed) ^ level) ^ path) ^ j) >> 33, in 0 .. RAND_MAX = 2^31 - 1
+ *                     (orbfe_vocabulary_training_draw).  The distribution is the reference's, the sequence is not.
+ *   2. empty cluster  when a group loses all its members the reference releases the mean and then reads through a null pointer
+ *                     in FORB::distance.  Here an empty cluster keeps the centre it had; it stays a node, possibly one no feature
+ *                     reaches, and every mean step that met one is counted in n_empty_clusters.
+ *   3. iteration cap  the reference has none; here a node stops after max_iterations association rounds (default
+ *                     ORBFE_VOCAB_TRAIN_MAX_ITERATIONS) with the association it has and is counted in n_capped_nodes.
+ * Segments (nodes) of at least wide_min descriptors are walked by a grid of workgroups with one launch pair per round; smaller ones
+ * are held by one workgroup from seeding to convergence.  wide_min never changes a result; a small value costs workspace (one
+ * 1 KiB block of counters per cluster of every wide segment).  There is no CPU path: ORBFE_ERR_NO_DEVICE without a device.
+ * ORBFE_ERR_INVALID (with an error string, before the device is looked for): k outside 2..20, L outside 1..10, scoring outside
+ * 0..5, weighting outside 0..3, fewer than 1 or more than 2^30 descriptors, n_images < 1, image_start not monotone from 0, a
+ * workspace smaller than orbfe_vocabulary_train_workspace_bytes asks for, null pointers. */
+#define ORBFE_VOCAB_TRAIN_MAX_ITERATIONS 1000
+typedef struct orbfe_vocab_train_config {
+  int32_t k, L;                 /* 2..20, 1..10: what loadFromTextFile accepts */
+  int32_t scoring, weighting;   /* 0..5, 0..3 */
+  uint64_t seed;
+  int32_t max_iterations;       /* 0: ORBFE_VOCAB_TRAIN_MAX_ITERATIONS */
+  int32_t wide_min;             /* segments of at least this many descriptors take the wide form; 0: the library's choice;
+                                   clamped to what the narrow form can hold.  Never changes a result. */
+} orbfe_vocab_train_config;    /* 32 bytes */
+typedef struct orbfe_vocab_train_stats {
+  int32_t n_nodes, n_words, n_kmeans_nodes, n_trivial_nodes, n_short_seedings, n_empty_clusters, n_capped_nodes,
+          max_rounds, nodes_per_level[11];
+} orbfe_vocab_train_stats;     /* 76 bytes; nodes_per_level[0] = 1, the root; max_rounds counts associations of one node */
+/* the 31-bit draw of deviation 1; host only, needs no device */
+uint32_t orbfe_vocabulary_training_draw(uint64_t seed, uint32_t level, uint64_t path, uint32_t j);
+int orbfe_vocabulary_train_workspace_bytes(const orbfe_vocab_train_config* cfg, int64_t n_desc, int n_images, size_t* bytes);
+/* HOST pointers, synchronous: desc = image_start[n_images] x 32 bytes, the images ragged and concatenated (image i holds features
+ * image_start[i] .. image_start[i + 1] - 1).  device < 0: the current one; the calling thread's current device is the same after
+ * the call as before it.  leaf_node (optional, [n_desc]): the node, in final ids, of
+ * the deepest group training feature i ended in.  stats is optional.  *vocabulary is an ordinary handle, usable at once by
+ * orbfe_bow_transform_device and everything downstream. */
+int orbfe_vocabulary_train(const orbfe_vocab_train_config* cfg, const uint8_t* desc, const int32_t* image_start, int n_images,
+                           int device, int32_t* leaf_node, orbfe_vocab_train_stats* stats, orbfe_vocabulary** vocabulary);
+/* DEVICE pointers of the calling thread's CURRENT device (the call runs there and does not check where the pointers live), as
+ * orbfe_extract_batch_device leaves them: d_desc = [n_frames][cap][32] (16-byte aligned), d_n = [n_frames] counts;
+ * whatever lies behind a frame's count is not read.  d_workspace: 256-byte aligned, at least what
+ * orbfe_vocabulary_train_workspace_bytes gives for the sum of the counts (n_frames * cap always suffices).  d_leaf_node: optional,
+ * [sum of counts], features in frame order.  Synchronous: the host reads one control word per round of a level and the node table
+ * per level.  stream: NULL = a stream of the call's own; work queued on `stream` before the call is waited for. */
+int orbfe_vocabulary_train_device(const orbfe_vocab_train_config* cfg, const uint8_t* d_desc, const int32_t* d_n, int n_frames, int cap,
+                                  void* d_workspace, size_t workspace_bytes, int32_t* d_leaf_node, void* stream,
+                                  orbfe_vocab_train_stats* stats, orbfe_vocabulary** vocabulary);
+/* Per level of the calling thread's last training call (at most max_levels entries, *n_levels written): wall milliseconds, the
+ * association rounds of its slowest node, and how many segments took the wide form, the narrow form and the trivial case. */
+int orbfe_debug_vocabulary_train_levels(int max_levels, double* ms, int32_t* rounds, int32_t* wide_segments, int32_t* narrow_segments,
+                                        int32_t* trivial_segments, int* n_levels);
 
 /* ------------------------------------------------------------------------------- batched-sequence mode: record gather */
 /* Independent frames shard over the GPUs of a node in contiguous chunks of the frame range (the reference

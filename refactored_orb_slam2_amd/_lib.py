@@ -85,6 +85,20 @@ class Calibration(C.Structure):
                 ("reserved", C.c_int32)]
 
 
+class VocabTrainConfig(C.Structure):
+    """orbfe_vocab_train_config (include/orbfe.h); 32 bytes"""
+    _fields_ = [("k", C.c_int32), ("L", C.c_int32), ("scoring", C.c_int32), ("weighting", C.c_int32), ("seed", C.c_uint64),
+                ("max_iterations", C.c_int32), ("wide_min", C.c_int32)]
+
+
+# orbfe_vocab_train_stats (include/orbfe.h)
+VOCAB_TRAIN_STATS_DTYPE = np.dtype([("n_nodes", "<i4"), ("n_words", "<i4"), ("n_kmeans_nodes", "<i4"), ("n_trivial_nodes", "<i4"),
+                                    ("n_short_seedings", "<i4"), ("n_empty_clusters", "<i4"), ("n_capped_nodes", "<i4"),
+                                    ("max_rounds", "<i4"), ("nodes_per_level", "<i4", (11,))])
+assert C.sizeof(VocabTrainConfig) == 32 and VOCAB_TRAIN_STATS_DTYPE.itemsize == 76
+VOCAB_TRAIN_MAX_ITERATIONS = 1000
+VOCAB_TRAIN_CHUNK = 1024   # positions per workgroup of the wide form; the most the narrow form holds (csrc/vocab_train_internal.h)
+
 DEPTH_NONE, DEPTH_U16, DEPTH_F32 = 0, 1, 2
 # orbfe_pose_camera / orbfe_pose_result (Optimizer::PoseOptimization, include/orbfe.h)
 POSE_CAMERA_DTYPE = np.dtype([("fx", "<f4"), ("fy", "<f4"), ("cx", "<f4"), ("cy", "<f4"), ("mbf", "<f4"), ("n_levels", "<i4"),
@@ -293,6 +307,9 @@ EXPORTS = [
     "orbfe_essential_graph_envelope_blocks", "orbfe_essential_graph", "orbfe_essential_graph_workspace_bytes",
     "orbfe_essential_graph_batch_device", "orbfe_sim3_correct_points", "orbfe_sim3_correct_points_device",
     "orbfe_pnp_ransac_parameters", "orbfe_pnp_solve", "orbfe_pnp_solve_batch_device",
+    "orbfe_vocabulary_nodes", "orbfe_vocabulary_write_text", "orbfe_vocabulary_write_binary", "orbfe_vocabulary_save_text",
+    "orbfe_vocabulary_save_binary", "orbfe_vocabulary_training_draw", "orbfe_vocabulary_train_workspace_bytes", "orbfe_vocabulary_train",
+    "orbfe_vocabulary_train_device", "orbfe_debug_vocabulary_train_levels",
 ]
 
 
@@ -454,9 +471,21 @@ def lib():
     L.orbfe_pnp_ransac_parameters.argtypes = [ci, C.c_double, ci, ci, ci, cf, vp, vp, vp]
     L.orbfe_pnp_solve.argtypes = [vp, vp, ci, vp, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp]
     L.orbfe_pnp_solve_batch_device.argtypes = [ci, vp, vp, vp, ci, vp, vp, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    ptc = C.POINTER(VocabTrainConfig)
+    L.orbfe_vocabulary_nodes.argtypes = [vp, vp, vp, vp, vp]
+    L.orbfe_vocabulary_write_text.argtypes = [C.c_char_p, ci, ci, ci, ci, ci, vp, vp, vp, vp]
+    L.orbfe_vocabulary_write_binary.argtypes = [C.c_char_p, ci, ci, ci, ci, ci, vp, vp, vp, vp]
+    L.orbfe_vocabulary_save_text.argtypes = [vp, C.c_char_p]
+    L.orbfe_vocabulary_save_binary.argtypes = [vp, C.c_char_p]
+    L.orbfe_vocabulary_training_draw.argtypes = [C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint32]
+    L.orbfe_vocabulary_train_workspace_bytes.argtypes = [ptc, i64, ci, C.POINTER(sz)]
+    L.orbfe_vocabulary_train.argtypes = [ptc, vp, vp, ci, ci, vp, vp, C.POINTER(vp)]
+    L.orbfe_vocabulary_train_device.argtypes = [ptc, vp, vp, ci, ci, vp, sz, vp, vp, vp, C.POINTER(vp)]
+    L.orbfe_debug_vocabulary_train_levels.argtypes = [ci, vp, vp, vp, vp, vp, pi]
     for name in EXPORTS:
         if name != "orbfe_last_error":
             getattr(L, name).restype = ci
+    L.orbfe_vocabulary_training_draw.restype = C.c_uint32
     _lib = L
     return L
 

@@ -25,6 +25,10 @@ struct orbfe_vocabulary {
   void *d_in = nullptr, *d_ow = nullptr, *d_on = nullptr, *d_owt = nullptr;
   int cap = 0;
   std::mutex mu;
+  // the tree as orbfe_vocabulary_create took it, for orbfe_vocabulary_nodes and the two save functions
+  std::vector<int32_t> h_parent;
+  std::vector<uint8_t> h_leaf, h_desc;
+  std::vector<double> h_weight;
 };
 
 static void vfree(orbfe_vocabulary* v) {
@@ -72,6 +76,10 @@ extern "C" int orbfe_vocabulary_create(int k, int L, int scoring, int weighting,
   orbfe_vocabulary* v = new orbfe_vocabulary();
   v->device = device; v->k = k; v->L = L; v->scoring = scoring; v->weighting = weighting;
   v->n_nodes = n_nodes; v->n_words = n_words;
+  v->h_parent.assign(parent, parent + n_nodes); v->h_parent[0] = 0;
+  v->h_leaf.assign(is_leaf, is_leaf + n_nodes);
+  v->h_desc.assign(desc, desc + (size_t)n_nodes * 32);
+  v->h_weight.assign(weight, weight + n_nodes);
   auto up = [&](void** d, const void* h, size_t bytes) -> int {
     HIPCHK(hipMalloc(d, bytes ? bytes : 16));
     HIPCHK(hipMemcpy(*d, h, bytes, hipMemcpyHostToDevice));
@@ -194,6 +202,89 @@ extern "C" int orbfe_vocabulary_info(const orbfe_vocabulary* v, int* k, int* L, 
   if (n_nodes) *n_nodes = v->n_nodes;
   if (n_words) *n_words = v->n_words;
   return ORBFE_OK;
+}
+
+extern "C" int orbfe_vocabulary_nodes(const orbfe_vocabulary* v, int32_t* parent, uint8_t* is_leaf, uint8_t* desc, double* weight) {
+  if (!v) return ORBFE_ERR_INVALID;
+  if (parent) memcpy(parent, v->h_parent.data(), sizeof(int32_t) * v->n_nodes);
+  if (is_leaf) memcpy(is_leaf, v->h_leaf.data(), v->n_nodes);
+  if (desc) memcpy(desc, v->h_desc.data(), (size_t)v->n_nodes * 32);
+  if (weight) memcpy(weight, v->h_weight.data(), sizeof(double) * v->n_nodes);
+  return ORBFE_OK;
+}
+
+static bool writable_tree(const char* path, int n_nodes, const int32_t* parent, const uint8_t* is_leaf, const uint8_t* desc,
+                          const double* weight) {
+  if (path && n_nodes >= 1 && parent && is_leaf && desc && weight) return true;
+  orbfe_set_error("vocabulary writer: null pointer or no node");
+  return false;
+}
+
+// ORBVocabulary::saveToTextFile (L/src/ORBVocabulary.cc:131-150) with one deviation: the weight is written with 17 significant digits,
+// so that it reads back as the same double (the reference's stream writes six).
+extern "C" int orbfe_vocabulary_write_text(const char* path, int k, int L, int scoring, int weighting, int n_nodes, const int32_t* parent,
+                                           const uint8_t* is_leaf, const uint8_t* desc, const double* weight) {
+  if (!writable_tree(path, n_nodes, parent, is_leaf, desc, weight)) return ORBFE_ERR_INVALID;
+  FILE* f = fopen(path, "w");
+  if (!f) {
+    orbfe_set_error("cannot write vocabulary %s", path);
+    return ORBFE_ERR_INVALID;
+  }
+  fprintf(f, "%d %d %d %d\n", k, L, scoring, weighting);
+  for (int i = 1; i < n_nodes; i++) {
+    fprintf(f, "%d %d ", parent[i], is_leaf[i] ? 1 : 0);
+    for (int b = 0; b < 32; b++) fprintf(f, "%d ", (int)desc[(size_t)i * 32 + b]);
+    fprintf(f, "%.17g\n", weight[i]);
+  }
+  const bool bad = ferror(f) != 0;
+  if (fclose(f) != 0 || bad) {
+    orbfe_set_error("writing vocabulary %s failed", path);
+    return ORBFE_ERR_INVALID;
+  }
+  return ORBFE_OK;
+}
+
+// ORBVocabulary::saveToBinaryFile (L/src/ORBVocabulary.cc:217-243), byte for byte: the records orbfe_vocabulary_load_binary reads
+extern "C" int orbfe_vocabulary_write_binary(const char* path, int k, int L, int scoring, int weighting, int n_nodes, const int32_t* parent,
+                                             const uint8_t* is_leaf, const uint8_t* desc, const double* weight) {
+  if (!writable_tree(path, n_nodes, parent, is_leaf, desc, weight)) return ORBFE_ERR_INVALID;
+  FILE* f = fopen(path, "wb");
+  if (!f) {
+    orbfe_set_error("cannot write vocabulary %s", path);
+    return ORBFE_ERR_INVALID;
+  }
+  const uint32_t hdr[2] = {(uint32_t)n_nodes, 4 + 32 + 4 + 1};
+  const int32_t kl[4] = {k, L, scoring, weighting};
+  fwrite(hdr, 4, 2, f);
+  fwrite(kl, 4, 4, f);
+  for (int i = 1; i < n_nodes; i++) {
+    uint8_t rec[41];
+    const uint32_t pid = (uint32_t)parent[i];
+    const float w = (float)weight[i];
+    memcpy(rec, &pid, 4);
+    memcpy(rec + 4, desc + (size_t)i * 32, 32);
+    memcpy(rec + 36, &w, 4);
+    rec[40] = is_leaf[i] ? 1 : 0;
+    fwrite(rec, 1, 41, f);
+  }
+  const bool bad = ferror(f) != 0;
+  if (fclose(f) != 0 || bad) {
+    orbfe_set_error("writing vocabulary %s failed", path);
+    return ORBFE_ERR_INVALID;
+  }
+  return ORBFE_OK;
+}
+
+extern "C" int orbfe_vocabulary_save_text(const orbfe_vocabulary* v, const char* path) {
+  if (!v) return ORBFE_ERR_INVALID;
+  return orbfe_vocabulary_write_text(path, v->k, v->L, v->scoring, v->weighting, v->n_nodes, v->h_parent.data(), v->h_leaf.data(),
+                                     v->h_desc.data(), v->h_weight.data());
+}
+
+extern "C" int orbfe_vocabulary_save_binary(const orbfe_vocabulary* v, const char* path) {
+  if (!v) return ORBFE_ERR_INVALID;
+  return orbfe_vocabulary_write_binary(path, v->k, v->L, v->scoring, v->weighting, v->n_nodes, v->h_parent.data(), v->h_leaf.data(),
+                                       v->h_desc.data(), v->h_weight.data());
 }
 
 static VocabDev dev_view(const orbfe_vocabulary* v) {
