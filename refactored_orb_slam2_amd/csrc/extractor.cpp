@@ -239,7 +239,7 @@ static int blur_coef(int in, int out, int len) {
     if (reflect101_host(out + t, len) == in) c += taps[t + 3];
   return c;   // two taps fold onto one sample at an edge (<= 96); on lines of two or three samples more do, and the sum leaves int8
 }
-// Band matrices of gauss_blur7_mfma_kernel (extract_kernels.hip) as v_mfma_i32_16x16x64_i8 operands: lane (q = lane >> 4,
+// Band matrices of gauss_blur7_mfma_kernel (pyramid_kernels.hip) as v_mfma_i32_16x16x64_i8 operands: lane (q = lane >> 4,
 // n = lane & 15) holds 16 bytes.  Horizontal, strip chunk c, column group g: byte j <-> input column 48c - 16 + 16q + j, output
 // column 48c - 12 + 16g + n (strip c = output columns [48c - 12, 48c + 36): every tap inside the 64-byte segment); the level's
 // left and right REFLECT_101 borders are folded into the first and last chunks' matrices.  Vertical, row group b of a window:
@@ -303,7 +303,7 @@ static int build_plan(orbfe_extractor* e, int w, int h) {
     }
     g.pitch = (g.w + 63) & ~63;
     // rows padded to 8: the blurred planes are stored in 16 x 8 tiles; 256 spare bytes behind them: where gauss_blur7_mfma's
-    // lanes outside the level put their dword (extract_kernels.hip)
+    // lanes outside the level put their dword (pyramid_kernels.hip)
     g.plane = ((size_t)g.pitch * ((g.h + 7) & ~7) + 256 + 255) & ~(size_t)255;
     g.off = off;  // per-image offsets; the buffer is level-major: level block = plane * cap_images
     off += g.plane;
@@ -1299,7 +1299,7 @@ extern "C" int orbfe_debug_blurred(orbfe_extractor* e, int image, int level, uin
   HIPCHK(hipSetDevice(e->device));
   const LevelGeom& g = e->lg[level];
   HIPCHK(hipStreamSynchronize(e->stream));
-  // the blurred planes are stored in 16 x 8 pixel tiles (one 128-byte line each, extract_kernels.hip): untile on the host
+  // the blurred planes are stored in 16 x 8 pixel tiles (one 128-byte line each, pyramid_kernels.hip): untile on the host
   const int hp = (g.h + 7) & ~7;
   std::vector<uint8_t> tiled((size_t)g.pitch * hp);
   HIPCHK(hipMemcpy(tiled.data(), level_ptr(e, e->d_blur, level, image), tiled.size(), hipMemcpyDeviceToHost));

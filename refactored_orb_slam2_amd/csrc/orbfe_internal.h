@@ -158,7 +158,7 @@ struct BlurMfmaParams {
   int use;                            // the handle asked for this kernel (orbfe_debug_blur_kernel)
 };
 
-// launchers (extract_kernels.hip)
+// launchers, one unit per stage: pyramid_kernels.hip (resize, blur), fast_kernels.hip, octree_kernels.hip, describe_kernels.hip
 void orbfe_launch_resize(const uint8_t* src, int spitch, size_t simg, uint8_t* dst, int dpitch, size_t dimg, int dw,
                          int dh, const ResizeTap* xt, const ResizeTap* yt, int n_images, int mode, hipStream_t s);   // mode: 0 direct gathers, 1 LDS-staged, 2 LDS-staged + 8-byte windows
 void orbfe_launch_fast_cells(const PyrView& pyr, const CellDesc* cells, const FastGroup* groups, int n_groups, int total_cells,
@@ -172,3 +172,6 @@ void orbfe_launch_blur_level(const PyrView& src, const PyrView& dst, const BlurT
                              int n_images, hipStream_t s);
 void orbfe_launch_describe(const DescribeParams& p, int n_images, hipStream_t s);
 size_t orbfe_octree_lds_bytes(int max_nodes, int lds_keys);
+// the band matrices of blur_level_kernel, filled beside their device table (pyramid_kernels.hip); orbfe_upload_pattern_floats()
+// (describe_kernels.hip, the one upload extractor.cpp calls) fills the describe tables and then calls this
+int orbfe_upload_blur_bands();

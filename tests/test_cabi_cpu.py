@@ -118,7 +118,8 @@ def test_pipeline_handle_validates_and_has_no_cpu_fallback(L):
 
 
 def test_no_hot_kernel_uses_scratch_memory():
-    """The compiler's own resource report (tools/scratch_check.sh as a test): no kernel spills registers, and none keeps anything in
+    """The compiler's own resource report (tools/scratch_check.sh as a test): no kernel spills vector registers, none spills scalar registers
+    beyond the counts listed below, and none keeps anything in
     scratch (private) memory except the three rare-path resolvers.  A by-value struct indexed with a per-lane value lives there -- 164
     bytes per thread of it were the whole time of the track-query kernels in rounds 3-5 (DESIGN lesson 58); this keeps it from coming back."""
     import glob, re, shutil, subprocess
@@ -127,6 +128,11 @@ def test_no_hot_kernel_uses_scratch_memory():
         pytest.skip("no hipcc")
     csrc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "refactored_orb_slam2_amd", "csrc")
     allowed = {"proj_resolve_kernel": 20, "bow_finish_kernel": 16, "init_resolve_kernel": 16}   # bytes per lane, rare paths only
+    # scalar registers the compiler parks in lanes of a vector register (no memory traffic): the kernels that have some today, with
+    # today's counts -- a kernel that is not listed spills none, and a listed one no more than this
+    sgpr_spills = {"_Z9ba_kernel": 78, "_Z10lba_kernel": 107, "essential_graph_kernelILi6E": 84, "essential_graph_kernelILi7E": 127,
+                   "fast_cells_kernelILi64ELi3E": 9, "fast_cells_kernelILi64ELi7E": 9, "fast_cells_kernelILi96ELi7E": 10,
+                   "proj_resolve_kernel": 25, "optimize_sim3_kernel": 52, "pose_optimize_kernel": 22}
     seen = 0
     for src in sorted(glob.glob(os.path.join(csrc, "*.hip"))):
         r = subprocess.run([hipcc, "-O3", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "--offload-arch=gfx950",
@@ -148,4 +154,7 @@ def test_no_hot_kernel_uses_scratch_memory():
                 assert val <= limit, f"{os.path.basename(src)}: {name} keeps {val} bytes per lane in scratch memory"
             elif what.startswith("VGPRs"):
                 assert val == 0, f"{os.path.basename(src)}: {name} spills {val} vector registers"
+            else:
+                limit = max([v for k, v in sgpr_spills.items() if k in name] + [0])
+                assert val <= limit, f"{os.path.basename(src)}: {name} spills {val} scalar registers (allowed: {limit})"
     assert seen >= 30   # every kernel of the library was looked at

@@ -1,6 +1,6 @@
 #!/bin/bash
 # A/B builds of liborbfe.so for kernel experiments: tools/ab_build.sh <name> "<extra -D flags>" [file.hip | file.cpp ...]
-# Recompiles the named .hip files (default: extract_kernels.hip) with the extra flags and links them with the objects of the
+# Recompiles the named .hip files (default: the extractor's four kernel units) with the extra flags and links them with the objects of the
 # regular build into refactored_orb_slam2_amd/csrc/_ab/liborbfe_<name>.so (git-ignored; travels to the GPU box).
 # NOTE: runs `make` first -- called on a `git stash`ed tree it rebuilds liborbfe.so from the stashed sources; run `make` again after
 # `git stash pop` (an A/B of "old vs new" was once old vs old that way).
@@ -8,7 +8,7 @@
 set -e
 cd "$(dirname "$0")/../refactored_orb_slam2_amd/csrc"
 name=$1; extra=$2; shift 2 || true
-files=${@:-extract_kernels.hip}
+files=${@:-pyramid_kernels.hip fast_kernels.hip octree_kernels.hip describe_kernels.hip}
 make -s
 mkdir -p _ab/obj_$name
 objs=""

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """The gfx950 listing of orient_describe8_kernel, read on a machine without a GPU: tools/describe_isa.py [-D...] [--dump FILE] [--asm LISTING]
 
-Compiles extract_kernels.hip to assembly with the Makefile's flags (or reads a listing made that way, --asm), cuts the kernel out and reports, as one JSON line,
+Compiles describe_kernels.hip to assembly with the Makefile's flags (or reads a listing made that way, --asm), cuts the kernel out and reports, as one JSON line,
   * the register budget (VGPRs, SGPRs, scratch bytes),
   * its two per-keypoint loops (the innermost loops that request windows: phase 1, the moments, and phase 3, BRIEF): the static
     instruction count, and the EXECUTED PATH of one full iteration, taken as the longest way through the loop body from its header
@@ -24,7 +24,7 @@ KERNEL = "_Z23orient_describe8_kernel14DescribeParams"
 
 def listing(extra=()):
     hipcc = "/opt/rocm/bin/hipcc" if os.path.exists("/opt/rocm/bin/hipcc") else "hipcc"
-    r = subprocess.run([hipcc] + FLAGS + list(extra) + ["extract_kernels.hip", "-o", "-"], capture_output=True, text=True, cwd=CSRC, timeout=900)
+    r = subprocess.run([hipcc] + FLAGS + list(extra) + ["describe_kernels.hip", "-o", "-"], capture_output=True, text=True, cwd=CSRC, timeout=900)
     if r.returncode != 0:
         raise RuntimeError(r.stderr[-2000:])
     return r.stdout

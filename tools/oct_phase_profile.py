@@ -1,5 +1,5 @@
 """Per-phase cycle breakdown of octree_select_kernel, per level, on one of bench.py's content kinds (default uniform_noise).
-Needs a library built with -DFC_TIMING=1 (tools/ab_build.sh timing "-DFC_TIMING=1" extract_kernels.hip; ORBFE_AB_LIB=timing)."""
+Needs a library built with -DFC_TIMING=1 (tools/ab_build.sh timing "-DFC_TIMING=1"; ORBFE_AB_LIB=timing)."""
 import ctypes as C, numpy as np, sys, os
 sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
 import torch

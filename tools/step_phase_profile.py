@@ -1,7 +1,7 @@
 """Per-phase wave-cycle breakdown of fast_cells_kernel and orient_describe8_kernel INSIDE the overlapped bench step (bench.py's
 StepRig: 256 stereo frames, three handle sets, left | right extractor on two streams, the matching half beside them) and, for
 comparison, with every kernel alone on the chip (one stream, one set).  Needs a -DFC_TIMING=1 build:
-  tools/ab_build.sh timing "-DFC_TIMING=1" extract_kernels.hip;  ORBFE_AB_LIB=timing python tools/step_phase_profile.py"""
+  tools/ab_build.sh timing "-DFC_TIMING=1";  ORBFE_AB_LIB=timing python tools/step_phase_profile.py"""
 import ctypes as C, os, sys
 ROOT = os.environ.get("GRAFT_REPO_ROOT", "/root/repo")
 sys.path.insert(0, ROOT)
