@@ -138,6 +138,9 @@ int orbfe_device_download(void* h_dst, const void* d_src, size_t bytes);
  *   essential graph     at most 32 768 vertices, 262 144 edges and 131 072 envelope blocks per problem, 65 535 problems per launch,
  *                       16 777 216 points per map correction (the ORBFE_EG_MAX_* constants, each with its reason; pinned by
  *                       tests/test_egraph_cpu.py and tests/test_egraph_gpu.py)
+ *   essential graph     ONE graph of at most 32 768 vertices, 262 144 edges and 4 194 304 envelope blocks (the ORBFE_EGRID_MAX_*
+ *   across the device   constants, each with its reason; orbfe_essential_graph_grid, orbfe_essential_graph_grid_device; pinned by
+ *                       tests/test_egraph_grid_cpu.py and tests/test_egraph_grid_gpu.py)
  * Each limit up to the covisibility graph's is pinned at its largest accepted and its first refused value by tests/test_limits_gpu.py (levels: also
  * tests/test_cabi_cpu.py; depth maps: tests/test_frames_cpu.py and tests/test_frames_gpu.py; rectification:
  * tests/test_rectify_cpu.py and tests/test_rectify_gpu.py; pose optimisation: tests/test_pose_cpu.py).
@@ -1987,7 +1990,8 @@ int orbfe_create_initial_map_batch_device(int P, const orbfe_pose_camera* d_came
  * what keeps it small: a spanning tree and covisibility links join keyframes of nearby ids, so the envelope is a band plus the few
  * rows that carry a loop edge.  No fill-reducing reordering is applied.  A pivot that is not > 0 fails the trial (g2o's ok2 = false):
  * the estimates are left alone, lambda grows, and ORBFE_EG_FACTOR_FAILED is reported in the result's status.
- * One workgroup per problem; a multi-workgroup form of one problem does not exist.  Deterministic: no floating-point atomics, every
+ * One workgroup per problem here; ONE graph across the whole device is orbfe_essential_graph_grid below, which gives the same bytes
+ * and takes envelopes 32 times as large.  Deterministic: no floating-point atomics, every
  * sum has one owner that walks a sorted list; a problem's bytes depend on its own rows only.  No CPU fallback.
  * Limits, each refused with ORBFE_ERR_INVALID one step past it (a per-problem ORBFE_EG_REFUSED on the batch form; pinned by
  * tests/test_egraph_cpu.py and tests/test_egraph_gpu.py):
@@ -2062,6 +2066,63 @@ int orbfe_essential_graph_batch_device(int P, const orbfe_eg_problem* d_problems
                                        const orbfe_eg_edge* d_edges, int kf_cap, int edge_cap, int env_cap, int flags,
                                        orbfe_eg_sim3* d_sim3_out, float* d_poses_out, orbfe_eg_result* d_result, void* d_workspace,
                                        size_t workspace_bytes, void* stream);
+
+/* ---- the same optimisation of ONE graph across the whole device --------------------------------------------------------------------
+ * A loop closure has one graph, and one workgroup walks the blocks of its row envelope one after the other (two barriers each).  Here
+ * every phase of a trial is a launch over the grid (csrc/egraph_grid_kernels.hip) and the launch boundary is the only grid-wide
+ * synchronisation.  The factorisation runs the same up-looking step per block -- a workgroup per block -- level by level: block (r, c)
+ * needs row r's blocks before c and the whole of row c, which gives every block a level (csrc/egraph_grid_internal.h; at most
+ * 2 n_free + 1 levels, computed once per call on the host from the rows' first blocks), and every level is one launch over its
+ * blocks, so every block whose inputs are complete is in flight.  The two triangular solves stay one workgroup in one launch.
+ * Records, validation rules, flags and results are those of orbfe_essential_graph, and so are the BYTES of sim3_out, poses_out and
+ * the whole result record for a graph both forms take: csrc/egraph_steps.h states every per-item step once for both kernels, every
+ * sum keeps its owner and its order, and a one-workgroup control kernel sums the per-edge chi2 and the computeScale terms in the
+ * order the one workgroup's lanes would have.  No floating-point atomics, no matrix-core arithmetic, no fill-reducing ordering: the
+ * caller's vertex order stays the elimination order.  Both forms are SYNCHRONOUS on their stream: the host reads one control record
+ * per trial from pinned memory, at most 20 iterations x 10 trials.  No CPU fallback.
+ * Limits, each refused with ORBFE_ERR_INVALID one step past it, before a device is looked for (pinned by
+ * tests/test_egraph_grid_cpu.py and tests/test_egraph_grid_gpu.py):
+ *   ORBFE_EGRID_MAX_KEYFRAMES        32 768 vertices and
+ *   ORBFE_EGRID_MAX_EDGES            262 144 edges: the records and their workspace are those of the one-workgroup form
+ *   ORBFE_EGRID_MAX_ENVELOPE_BLOCKS  4 194 304 blocks of 7 x 7 doubles: 1.6 GB of workspace -- the dense envelope of 2 895 free
+ *                                    keyframes -- and 34 MB of level plan; block counts stay within 32 bits, element offsets are
+ *                                    64-bit
+ *   records                          as above */
+#define ORBFE_EGRID_MAX_KEYFRAMES 32768
+#define ORBFE_EGRID_MAX_EDGES 262144
+#define ORBFE_EGRID_MAX_ENVELOPE_BLOCKS 4194304
+/* One graph.  HOST pointers, synchronous.  Arguments, results and limits as orbfe_essential_graph's, with
+ * ORBFE_EGRID_MAX_ENVELOPE_BLOCKS in place of ORBFE_EG_MAX_ENVELOPE_BLOCKS; the workspace is allocated for the call. */
+int orbfe_essential_graph_grid(const orbfe_eg_vertex* vertices, int n_kf, const orbfe_eg_edge* edges, int n_edges, int flags,
+                               orbfe_eg_sim3* sim3_out, float* poses_out, orbfe_eg_result* result);
+/* The bytes of workspace of a graph of at most kf_cap vertices, edge_cap edges and env_cap envelope blocks
+ * (orbfe_essential_graph_envelope_blocks states a graph's).  Monotonic in every cap.
+ * Limits (ORBFE_ERR_INVALID): the caps >= 0 and within the ORBFE_EGRID_MAX_*, null bytes. */
+int orbfe_essential_graph_grid_workspace_bytes(int kf_cap, int edge_cap, int64_t env_cap, size_t* bytes);
+/* The same on DEVICE pointers, SYNCHRONOUS on `stream` (NULL: the NULL stream); the inputs are not modified.  d_workspace: 256-byte
+ * aligned; its contents mean nothing before or after.  Its size states the envelope it holds: at least
+ * orbfe_essential_graph_grid_workspace_bytes(n_kf, n_edges, 0) bytes or the call is refused with ORBFE_ERR_INVALID, and
+ * orbfe_essential_graph_grid_workspace_bytes(n_kf, n_edges, blocks) for a graph of `blocks` envelope blocks.  A graph that breaks a
+ * rule only the device can see -- a record or a derived measurement beyond the limits above, an envelope the workspace does not hold
+ * or one beyond ORBFE_EGRID_MAX_ENVELOPE_BLOCKS -- comes back with ORBFE_OK, status ORBFE_EG_REFUSED in d_result and its Scw and
+ * their poses written through, as the batch form's do.
+ * Limits (ORBFE_ERR_INVALID): the counts, flags outside ORBFE_EG_FIX_SCALE, null pointers with a count > 0, null d_result,
+ * misaligned records (vertices, sim3_out, result: 8 bytes; the others: 4), a workspace that is null, misaligned or too small. */
+int orbfe_essential_graph_grid_device(const orbfe_eg_vertex* d_vertices, int n_kf, const orbfe_eg_edge* d_edges, int n_edges, int flags,
+                                      orbfe_eg_sim3* d_sim3_out, float* d_poses_out, orbfe_eg_result* d_result, void* d_workspace,
+                                      size_t workspace_bytes, void* stream);
+/* Measurement only (tools/egraph_rate.py): copies the calling thread's sums of stream-event times per phase, in milliseconds, to ms
+ * (9 floats: prepare, the host's level plan with its two copies, linearise, build, factorisation, solves, update / chi2 / control
+ * kernel, control read-back, and last the level count of the latest call; NULL: not copied), clears them, and switches the timing of
+ * this thread's later calls of the two forms above on (enable != 0) or off.  Timing synchronises the stream after every phase: the
+ * sums are the phases' device times, and a timed call is slower than an untimed one. */
+int orbfe_debug_egrid_phases(int enable, float* ms);
+/* Test only: the level plan of the factorisation from first[n_free], the first row block of every row's envelope (0 <= first[r] <= r).
+ * block_level: one int per envelope block, row by row with columns ascending; *n_levels: the level count.  HOST pointers, no device.
+ * Limits (ORBFE_ERR_INVALID): n_free outside 0 .. ORBFE_EGRID_MAX_KEYFRAMES, a first[r] out of range, more than
+ * ORBFE_EGRID_MAX_ENVELOPE_BLOCKS blocks, null pointers. */
+int orbfe_debug_egrid_level_plan(const int32_t* first, int n_free, int32_t* block_level, int32_t* n_levels);
+
 /* The map correction of OptimizeEssentialGraph (:1014-1042, :1332-1361) and the neighbour propagation of CorrectLoop
  * (L/src/LoopClosing.cc:445-475): points_out[p] = to[ref[p]]^-1 .map( from[ref[p]].map(points[p]) ), with Eigen's quaternion-vector
  * product, the float position widened to double and rounded once to float at the end (Converter::toCvMat).  ref[p] < 0: the point

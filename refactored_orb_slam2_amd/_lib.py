@@ -249,6 +249,9 @@ EG_MAX_KEYFRAMES, EG_MAX_EDGES, EG_MAX_ENVELOPE_BLOCKS, EG_MAX_PROBLEMS, EG_MAX_
 EG_FIX_SCALE = 1
 EG_NORMAL, EG_LOOP_CONNECTION = 0, 1
 EG_DONE, EG_FACTOR_FAILED, EG_REFUSED = 0, 1, -1
+# the ORBFE_EGRID_* constants (one graph across the device, include/orbfe.h); EGRID_PHASES: the floats of orbfe_debug_egrid_phases
+EGRID_MAX_KEYFRAMES, EGRID_MAX_EDGES, EGRID_MAX_ENVELOPE_BLOCKS = 32768, 262144, 4194304
+EGRID_PHASES = ("prepare", "plan", "linearise", "build", "factor", "solve", "update", "control", "levels")
 
 
 class RectifyCamera(C.Structure):
@@ -306,6 +309,8 @@ EXPORTS = [
     "orbfe_create_initial_map", "orbfe_initial_map_workspace_bytes", "orbfe_create_initial_map_batch_device",
     "orbfe_essential_graph_envelope_blocks", "orbfe_essential_graph", "orbfe_essential_graph_workspace_bytes",
     "orbfe_essential_graph_batch_device", "orbfe_sim3_correct_points", "orbfe_sim3_correct_points_device",
+    "orbfe_essential_graph_grid", "orbfe_essential_graph_grid_workspace_bytes", "orbfe_essential_graph_grid_device",
+    "orbfe_debug_egrid_phases", "orbfe_debug_egrid_level_plan",
     "orbfe_pnp_ransac_parameters", "orbfe_pnp_solve", "orbfe_pnp_solve_batch_device",
     "orbfe_vocabulary_nodes", "orbfe_vocabulary_write_text", "orbfe_vocabulary_write_binary", "orbfe_vocabulary_save_text",
     "orbfe_vocabulary_save_binary", "orbfe_vocabulary_training_draw", "orbfe_vocabulary_train_workspace_bytes", "orbfe_vocabulary_train",
@@ -466,6 +471,11 @@ def lib():
     L.orbfe_essential_graph.argtypes = [vp, ci, vp, ci, ci, vp, vp, vp]
     L.orbfe_essential_graph_workspace_bytes.argtypes = [ci, ci, ci, ci, C.POINTER(sz)]
     L.orbfe_essential_graph_batch_device.argtypes = [ci, vp, vp, vp, ci, ci, ci, ci, vp, vp, vp, vp, sz, vp]
+    L.orbfe_essential_graph_grid.argtypes = [vp, ci, vp, ci, ci, vp, vp, vp]
+    L.orbfe_essential_graph_grid_workspace_bytes.argtypes = [ci, ci, i64, C.POINTER(sz)]
+    L.orbfe_essential_graph_grid_device.argtypes = [vp, ci, vp, ci, ci, vp, vp, vp, vp, sz, vp]
+    L.orbfe_debug_egrid_phases.argtypes = [ci, vp]
+    L.orbfe_debug_egrid_level_plan.argtypes = [vp, ci, vp, vp]
     L.orbfe_sim3_correct_points.argtypes = [vp, ci, vp, vp, vp, ci, vp]
     L.orbfe_sim3_correct_points_device.argtypes = [vp, ci, vp, vp, ci, vp, ci, vp, vp]
     L.orbfe_pnp_ransac_parameters.argtypes = [ci, C.c_double, ci, ci, ci, cf, vp, vp, vp]

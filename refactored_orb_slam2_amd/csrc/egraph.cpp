@@ -7,12 +7,12 @@
 
 #include <vector>
 
-#include "egraph_internal.h"
+#include "egraph_grid_internal.h"
 #include "host_internal.h"
 
 static const char* WHO = "essential graph";
 
-static bool counts_ok(const char* who, int n_kf, int n_edges) {
+bool eg_counts_ok(const char* who, int n_kf, int n_edges) {
   if (n_kf < 0 || n_kf > ORBFE_EG_MAX_KEYFRAMES || n_edges < 0 || n_edges > ORBFE_EG_MAX_EDGES) {
     orbfe_set_error("%s: n_kf %d (0 .. %d), n_edges %d (0 .. %d)", who, n_kf, ORBFE_EG_MAX_KEYFRAMES, n_edges, ORBFE_EG_MAX_EDGES);
     return false;
@@ -58,7 +58,7 @@ extern "C" int orbfe_essential_graph_envelope_blocks(int n_kf, const uint8_t* fi
     orbfe_set_error("%s: blocks and, with n_edges > 0, edges are required", who);
     return ORBFE_ERR_INVALID;
   }
-  if (!counts_ok(who, n_kf, n_edges) || !edges_ok(who, edges, n_edges, n_kf)) return ORBFE_ERR_INVALID;
+  if (!eg_counts_ok(who, n_kf, n_edges) || !edges_ok(who, edges, n_edges, n_kf)) return ORBFE_ERR_INVALID;
   *blocks = envelope(n_kf, fixed, edges, n_edges);
   return ORBFE_OK;
 }
@@ -117,32 +117,33 @@ extern "C" int orbfe_essential_graph_batch_device(int P, const orbfe_eg_problem*
   return hip_status("essential graph batch: kernel launch failed", hipGetLastError());
 }
 
-extern "C" int orbfe_essential_graph(const orbfe_eg_vertex* vertices, int n_kf, const orbfe_eg_edge* edges, int n_edges, int flags,
-                                     orbfe_eg_sim3* sim3_out, float* poses_out, orbfe_eg_result* result) {
+// what both host forms of one graph check before a device is looked for (egraph_grid_internal.h)
+int eg_validate_host_graph(const char* who, const orbfe_eg_vertex* vertices, int n_kf, const orbfe_eg_edge* edges, int n_edges, int flags,
+                           const void* sim3_out, const void* poses_out, const void* result, int64_t* env) {
   if (!result) {
-    orbfe_set_error("%s: result is required", WHO);
+    orbfe_set_error("%s: result is required", who);
     return ORBFE_ERR_INVALID;
   }
-  if (!counts_ok(WHO, n_kf, n_edges)) return ORBFE_ERR_INVALID;
+  if (!eg_counts_ok(who, n_kf, n_edges)) return ORBFE_ERR_INVALID;
   if (flags & ~ORBFE_EG_FIX_SCALE) {
-    orbfe_set_error("%s: flags %d", WHO, flags);
+    orbfe_set_error("%s: flags %d", who, flags);
     return ORBFE_ERR_INVALID;
   }
   if ((n_kf > 0 && (!vertices || !sim3_out || !poses_out)) || (n_edges > 0 && !edges)) {
-    orbfe_set_error("%s: the arrays of a count > 0 are required", WHO);
+    orbfe_set_error("%s: the arrays of a count > 0 are required", who);
     return ORBFE_ERR_INVALID;
   }
-  if (!edges_ok(WHO, edges, n_edges, n_kf)) return ORBFE_ERR_INVALID;
+  if (!edges_ok(who, edges, n_edges, n_kf)) return ORBFE_ERR_INVALID;
   const bool se3 = (flags & ORBFE_EG_FIX_SCALE) != 0;
   std::vector<uint8_t> fixed(n_kf);
   for (int k = 0; k < n_kf; k++) {
     const orbfe_eg_vertex& v = vertices[k];
     if (!eg_record_ok(v.Scw) || !eg_record_ok(v.Snc)) {
-      orbfe_set_error("%s: vertex %d: a record must be finite with s > 0 and a quaternion of non-zero norm", WHO, k);
+      orbfe_set_error("%s: vertex %d: a record must be finite with s > 0 and a quaternion of non-zero norm", who, k);
       return ORBFE_ERR_INVALID;
     }
     if (se3 && (!eg_unit_scale(v.Scw.s) || !eg_unit_scale(v.Snc.s))) {
-      orbfe_set_error("%s: vertex %d: scales %.17g, %.17g with a fixed scale (|s - 1| <= 1e-3)", WHO, k, v.Scw.s, v.Snc.s);
+      orbfe_set_error("%s: vertex %d: scales %.17g, %.17g with a fixed scale (|s - 1| <= 1e-3)", who, k, v.Scw.s, v.Snc.s);
       return ORBFE_ERR_INVALID;
     }
     fixed[k] = v.fixed ? 1 : 0;
@@ -153,11 +154,19 @@ extern "C" int orbfe_essential_graph(const orbfe_eg_vertex* vertices, int n_kf, 
       const bool loop = E.kind == ORBFE_EG_LOOP_CONNECTION;
       const double s = eg_measurement_scale(loop ? vertices[E.i].Scw.s : vertices[E.i].Snc.s, loop ? vertices[E.j].Scw.s : vertices[E.j].Snc.s);
       if (!eg_unit_scale(s)) {
-        orbfe_set_error("%s: edge %d: its measurement has scale %.17g with a fixed scale (|s - 1| <= 1e-3)", WHO, e, s);
+        orbfe_set_error("%s: edge %d: its measurement has scale %.17g with a fixed scale (|s - 1| <= 1e-3)", who, e, s);
         return ORBFE_ERR_INVALID;
       }
     }
-  const int64_t env = envelope(n_kf, fixed.data(), edges, n_edges);
+  *env = envelope(n_kf, fixed.data(), edges, n_edges);
+  return ORBFE_OK;
+}
+
+extern "C" int orbfe_essential_graph(const orbfe_eg_vertex* vertices, int n_kf, const orbfe_eg_edge* edges, int n_edges, int flags,
+                                     orbfe_eg_sim3* sim3_out, float* poses_out, orbfe_eg_result* result) {
+  int64_t env = 0;
+  int rc;
+  if ((rc = eg_validate_host_graph(WHO, vertices, n_kf, edges, n_edges, flags, sim3_out, poses_out, result, &env))) return rc;
   if (env > ORBFE_EG_MAX_ENVELOPE_BLOCKS) {
     orbfe_set_error("%s: the row envelope has %lld blocks (0 .. %d): list the keyframes by ascending mnId", WHO, (long long)env,
                     ORBFE_EG_MAX_ENVELOPE_BLOCKS);
@@ -177,7 +186,6 @@ extern "C" int orbfe_essential_graph(const orbfe_eg_vertex* vertices, int n_kf, 
                o_e = c.in((size_t)n_edges * sizeof(orbfe_eg_edge));
   const size_t o_res = c.out(sizeof(orbfe_eg_result)), o_s = c.out((size_t)n_kf * sizeof(orbfe_eg_sim3)), o_p = c.out((size_t)n_kf * 48);
   const size_t ws_bytes = eg_ws_bytes(n_kf, n_edges, (int)env);
-  int rc;
   if ((rc = c.open())) return rc;
   if (ws_bytes && (rc = hip_status("essential graph: workspace", hipMalloc(&ws.p, ws_bytes)))) return rc;
   uint8_t *const h = c.host(0), *const d = c.dev(0);

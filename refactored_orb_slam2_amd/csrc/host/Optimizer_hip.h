@@ -36,8 +36,11 @@
 // rescale -- on orbfe_create_initial_map.  Members used beyond the above: KeyFrame::N, MapPoint::GetIndexInKeyFrame(KeyFrame*).
 //
 // OptimizeEssentialGraph (Optimizer.cc:1366, both forms) is the adapter for orbfe_essential_graph and orbfe_sim3_correct_points, with
-// the reference's signature, split into a marshal and an apply half and unit-tested by tests/cpp/test_egraph_dropin.cpp.  Members used
-// beyond the above:
+// the reference's signature, split into a marshal and an apply half and unit-tested by tests/cpp/test_egraph_dropin.cpp.  A host that
+// defines ORBFE_HOST_ESSENTIAL_GRAPH_ACROSS_DEVICE before it includes this header gets orbfe_essential_graph_grid -- one graph across
+// the whole device, the same bytes -- for a graph beyond ORBFE_EG_MAX_ENVELOPE_BLOCKS instead of the refusal, and for every graph
+// from the measured crossover kEssentialGraphGridFromBlocks on (unit-tested by tests/cpp_egraph_grid); the default keeps what every
+// existing host sees.  Members used beyond the above:
 //   KeyFrame: GetRotation(), GetTranslation(), GetParent(), hasChild(KeyFrame*), GetLoopEdges(), GetCovisiblesByWeight(int),
 //             GetWeight(KeyFrame*)
 //   MapPoint: mnCorrectedByKF, mnCorrectedReference, GetReferenceKeyFrame(), and what MapPoint_hip.h names
@@ -739,6 +742,25 @@ void OptimizeEssentialGraphApply(EssentialGraphProblem<KeyFrameT, MapPointT>& B,
   UpdateNormalAndDepth(moved);
 }
 
+// The envelope blocks from which OptimizeEssentialGraph, compiled with ORBFE_HOST_ESSENTIAL_GRAPH_ACROSS_DEVICE, hands a graph to
+// orbfe_essential_graph_grid: the measured crossover of the two forms (profiles/essential_graph.md; one MI355X, tools/egraph_rate.py
+// on graphs of band 20, Sim3 / SE3, one workgroup against across the device).  At 66 blocks (12 keyframes) the one-workgroup form
+// is the faster one, 3.5 / 1.6 ms against 3.9 / 2.8 ms; at 190 blocks (20 keyframes) the form across the device is, 6.0 / 4.3 ms
+// against 9.3 / 5.0 ms, and it stays so at every larger size measured (609 blocks: 2.5 / 2.1 times; 41 769 blocks: 4.0 / 3.6 times).
+constexpr int64_t kEssentialGraphGridFromBlocks = 190;
+
+// Whether the form across the device is the one for problem B: by its envelope (orbfe_essential_graph_envelope_blocks) against the
+// constant above.  Needs no device.
+template <class KeyFrameT, class MapPointT>
+bool EssentialGraphAcrossDevice(const EssentialGraphProblem<KeyFrameT, MapPointT>& B) {
+  std::vector<uint8_t> fixed(B.vertices.size());
+  for (size_t k = 0; k < B.vertices.size(); k++) fixed[k] = B.vertices[k].fixed ? 1 : 0;
+  int64_t blocks = 0;
+  if (orbfe_essential_graph_envelope_blocks((int)B.vertices.size(), fixed.data(), B.edges.data(), (int)B.edges.size(), &blocks) != ORBFE_OK)
+    return false;
+  return blocks >= kEssentialGraphGridFromBlocks;
+}
+
 // void Optimizer::OptimizeEssentialGraph(Map* pMap, KeyFrame* pLoopKF, KeyFrame* pCurKF, const LoopClosing::KeyFrameAndPose&
 // NonCorrectedSim3, const LoopClosing::KeyFrameAndPose& CorrectedSim3, const map<KeyFrame*, set<KeyFrame*>>& LoopConnections, const
 // bool& bFixScale).  Two library calls: the graph, then the map correction.  Errors (no device, a graph beyond the library's limits,
@@ -753,8 +775,19 @@ void OptimizeEssentialGraph(MapT* pMap, KeyFrameT* pLoopKF, KeyFrameT* pCurKF, c
   std::vector<orbfe_eg_sim3> sim3_out((size_t)n_kf), vScw((size_t)n_kf);
   std::vector<float> poses_out((size_t)12 * n_kf), points_out((size_t)3 * n_pt);
   orbfe_eg_result res;
-  int rc = orbfe_essential_graph(B.vertices.data(), n_kf, B.edges.data(), (int)B.edges.size(), bFixScale ? ORBFE_EG_FIX_SCALE : 0,
-                                 sim3_out.data(), poses_out.data(), &res);
+  const int n_edges = (int)B.edges.size(), flags = bFixScale ? ORBFE_EG_FIX_SCALE : 0;
+  // Without ORBFE_HOST_ESSENTIAL_GRAPH_ACROSS_DEVICE every graph goes to the one-workgroup form, which refuses one beyond its envelope
+  // limit, as every existing host sees.  With it, the form across the device takes such a graph -- and every graph from the crossover
+  // on: the two forms give the same bytes, so the choice is only a matter of time.  A graph whose envelope cannot be counted (a limit
+  // broken) goes to the one-workgroup form, which reports it.
+  bool across_device = false;
+#ifdef ORBFE_HOST_ESSENTIAL_GRAPH_ACROSS_DEVICE
+  across_device = EssentialGraphAcrossDevice(B);
+#endif
+  int rc = across_device ? orbfe_essential_graph_grid(B.vertices.data(), n_kf, B.edges.data(), n_edges, flags, sim3_out.data(),
+                                                      poses_out.data(), &res)
+                         : orbfe_essential_graph(B.vertices.data(), n_kf, B.edges.data(), n_edges, flags, sim3_out.data(),
+                                                 poses_out.data(), &res);
   if (rc == ORBFE_OK) {
     for (int k = 0; k < n_kf; k++) vScw[k] = B.vertices[k].Scw;
     rc = orbfe_sim3_correct_points(B.points.data(), n_pt, B.ref.data(), vScw.data(), sim3_out.data(), n_kf, points_out.data());

@@ -22,6 +22,10 @@ essential_graph is the call of LoopClosing::CorrectLoop on host arrays (Optimize
 the SE3 form with fix_scale); essential_graph_batch optimises ragged graphs that lie in device tensors in one launch
 (egraph_kernels.hip, one workgroup per graph) with a workspace of essential_graph_workspace_bytes(...) bytes, whose env_cap
 essential_graph_envelope_blocks(...) states per graph.  The vertex order is the elimination order: list keyframes by ascending mnId.
+essential_graph_grid is the same call for ONE graph across the whole device (egraph_grid_kernels.hip: every phase of a trial a
+launch, the factorisation level by level with a workgroup per block): the same bytes for a graph both take, envelopes 32 times as
+large, and the form a loop closure wants -- it has one graph.  essential_graph_grid_device takes device tensors and a workspace of
+essential_graph_grid_workspace_bytes(...) bytes; both are synchronous.
 The map correction behind it is sim3.correct_points.
 """
 from __future__ import annotations
@@ -36,6 +40,7 @@ from ._lib import GBA_MAX_EDGES, GBA_MAX_KEYFRAMES, GBA_MAX_POINTS, GBA_TILE_KEY
 from ._lib import (LBA_DROPPED, LBA_EDGE_DTYPE, LBA_ERASE, LBA_FIRST_ROUND_ONLY, LBA_PROBLEM_DTYPE, LBA_RESULT_DTYPE)
 from ._lib import (EG_DONE, EG_EDGE_DTYPE, EG_FACTOR_FAILED, EG_FIX_SCALE, EG_LOOP_CONNECTION, EG_NORMAL, EG_PROBLEM_DTYPE, EG_REFUSED,
                    EG_RESULT_DTYPE, EG_SIM3_DTYPE, EG_VERTEX_DTYPE)
+from ._lib import EGRID_MAX_EDGES, EGRID_MAX_ENVELOPE_BLOCKS, EGRID_MAX_KEYFRAMES
 from ._lib import OPTSIM3_PAIR_DTYPE, OPTSIM3_RESULT_DTYPE, POSE_CAMERA_DTYPE, POSE_DISCARD, POSE_RESULT_DTYPE, SIM3_VIEW_DTYPE
 
 __all__ = ["POSE_CAMERA_DTYPE", "POSE_RESULT_DTYPE", "POSE_DISCARD", "pose_camera", "pose_optimization", "pose_optimization_batch",
@@ -47,7 +52,9 @@ __all__ = ["POSE_CAMERA_DTYPE", "POSE_RESULT_DTYPE", "POSE_DISCARD", "pose_camer
            "global_bundle_adjustment_device", "gba_workspace_bytes",
            "EG_SIM3_DTYPE", "EG_VERTEX_DTYPE", "EG_EDGE_DTYPE", "EG_PROBLEM_DTYPE", "EG_RESULT_DTYPE", "EG_FIX_SCALE", "EG_NORMAL",
            "EG_LOOP_CONNECTION", "EG_DONE", "EG_FACTOR_FAILED", "EG_REFUSED", "essential_graph", "essential_graph_batch",
-           "essential_graph_envelope_blocks", "essential_graph_workspace_bytes"]
+           "essential_graph_envelope_blocks", "essential_graph_workspace_bytes",
+           "EGRID_MAX_KEYFRAMES", "EGRID_MAX_EDGES", "EGRID_MAX_ENVELOPE_BLOCKS", "essential_graph_grid", "essential_graph_grid_device",
+           "essential_graph_grid_workspace_bytes"]
 
 
 def pose_camera(fx, fy, cx, cy, mbf, inv_level_sigma2) -> np.ndarray:
@@ -311,3 +318,38 @@ def essential_graph_batch(problems, vertices, edges, kf_cap, edge_cap, env_cap, 
         P, _lib.ptr(problems), _lib.ptr(vertices), _lib.ptr(edges), int(kf_cap), int(edge_cap), int(env_cap),
         EG_FIX_SCALE if fix_scale else 0, _lib.ptr(sim3_out), _lib.ptr(poses_out), _lib.ptr(result), _lib.ptr(workspace),
         int(workspace.numel()) * int(workspace.element_size()), _lib.stream_handle(stream)), "orbfe_essential_graph_batch_device")
+
+
+def essential_graph_grid(vertices, edges, fix_scale: bool = False):
+    """orbfe_essential_graph_grid: essential_graph for ONE graph across the whole device, with envelopes of up to
+    EGRID_MAX_ENVELOPE_BLOCKS blocks.  Arguments and return value as essential_graph's; a graph both take gives the same bytes."""
+    vertices = np.ascontiguousarray(vertices, EG_VERTEX_DTYPE).reshape(-1)
+    edges = np.ascontiguousarray(edges, EG_EDGE_DTYPE).reshape(-1)
+    sim3_out = np.zeros(len(vertices), EG_SIM3_DTYPE)
+    poses_out = np.zeros((len(vertices), 12), np.float32)
+    res = np.zeros(1, EG_RESULT_DTYPE)
+    opt = lambda a: _lib.ptr(a) if len(a) else None
+    _lib.check(_lib.lib().orbfe_essential_graph_grid(opt(vertices), len(vertices), opt(edges), len(edges), EG_FIX_SCALE if fix_scale else 0,
+                                                     opt(sim3_out), opt(poses_out), _lib.ptr(res)), "orbfe_essential_graph_grid")
+    return sim3_out, poses_out, res[0]
+
+
+def essential_graph_grid_workspace_bytes(kf_cap: int, edge_cap: int, env_cap: int) -> int:
+    """orbfe_essential_graph_grid_workspace_bytes: the workspace of one graph of at most kf_cap vertices, edge_cap edges and env_cap
+    envelope blocks (essential_graph_envelope_blocks states a graph's)."""
+    n = C.c_size_t(0)
+    _lib.check(_lib.lib().orbfe_essential_graph_grid_workspace_bytes(int(kf_cap), int(edge_cap), int(env_cap), C.byref(n)),
+               "orbfe_essential_graph_grid_workspace_bytes")
+    return int(n.value)
+
+
+def essential_graph_grid_device(vertices, edges, sim3_out, poses_out, result, workspace, fix_scale: bool = False, stream=None):
+    """orbfe_essential_graph_grid_device on torch CUDA tensors: vertices (K,136) u8 = EG_VERTEX_DTYPE, edges (E,12) u8 = EG_EDGE_DTYPE;
+    sim3_out (K,8) f64 = EG_SIM3_DTYPE, poses_out (K,12) f32, result (48) u8 = one EG_RESULT_DTYPE record, workspace: u8 of at least
+    essential_graph_grid_workspace_bytes(K, E, blocks) bytes for a graph of `blocks` envelope blocks -- a graph it does not hold comes
+    back with status EG_REFUSED.  Synchronous on `stream` (a torch.cuda.Stream, or None for the NULL stream): the host reads one
+    control record per trial."""
+    _lib.check(_lib.lib().orbfe_essential_graph_grid_device(
+        _lib.ptr(vertices), int(vertices.shape[0]), _lib.ptr(edges), int(edges.shape[0]), EG_FIX_SCALE if fix_scale else 0,
+        _lib.ptr(sim3_out), _lib.ptr(poses_out), _lib.ptr(result), _lib.ptr(workspace),
+        int(workspace.numel()) * int(workspace.element_size()), _lib.stream_handle(stream)), "orbfe_essential_graph_grid_device")
