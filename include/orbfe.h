@@ -123,6 +123,9 @@ int orbfe_device_download(void* h_dst, const void* d_src, size_t bytes);
  *   global bundle       ONE map of at most 2 048 keyframes (any number free), 1 048 575 points and 8 388 600 edges, 1 .. 20
  *   adjustment          iterations (the ORBFE_GBA_MAX_* constants, each with its reason; orbfe_global_bundle_adjustment,
  *                       orbfe_global_bundle_adjustment_device; pinned by tests/test_gba_cpu.py and tests/test_gba_gpu.py)
+ *   map update behind   at most 65 536 keyframes and as many rows of adjusted poses, 16 777 216 points and as many rows of adjusted
+ *   that adjustment     points (the ORBFE_GBA_MAP_MAX_* constants, each with its reason; orbfe_gba_update_map,
+ *                       orbfe_gba_update_map_device; pinned by tests/test_gba_map_cpu.py and tests/test_gba_map_gpu.py)
  *   initial map         at most 4 096 keypoints a frame (ORBFE_INIT_MAX_MATCHES) and 65 535 problems per launch, 1 .. 20 iterations,
  *                       q >= 1, min_points >= 0 (orbfe_create_initial_map, orbfe_create_initial_map_batch_device; pinned by
  *                       tests/test_ba_cpu.py and tests/test_ba_gpu.py)
@@ -1195,6 +1198,77 @@ int orbfe_global_bundle_adjustment_device(const orbfe_pose_camera* d_camera, con
  * switches the timing of this thread's later calls of the two forms above on (enable != 0) or off.  Timing synchronises the stream
  * after every phase: the sums are the phases' device times, and a timed call is slower than an untimed one. */
 int orbfe_debug_gba_phases(int enable, float* ms);
+
+/* ---- The map update behind the global bundle adjustment (LoopClosing::RunGlobalBundleAdjustment, L/src/LoopClosing.cc:648-703) ---------
+ * What the reference does with mTcwGBA / mPosGBA once the adjustment has finished.  Keyframes: a breadth-first walk of the spanning
+ * tree from the map's origins; a keyframe the adjustment did not optimise (local mapping inserted it meanwhile) gets
+ * mTcwGBA = (Tcw * parent.Twc) * parent.mTcwGBA, the bracket from the poses before the walk, and every keyframe reached gets
+ * SetPose(mTcwGBA) (L/src/KeyFrame.cc:75-88: Twc and the stereo centre Cw with it).  Points: one the adjustment optimised takes its
+ * mPosGBA; any other moves with its reference keyframe, Xw' = Rwc_new * (Rcw_before * Xw + tcw_before) + twc_new; a bad point stays.
+ * UpdateNormalAndDepth is not part of this block.  The arithmetic is csrc/gba_map_internal.h's reading of cv::Mat (float dots in index
+ * order, zeros and ones of a 4 x 4 operand included, double epilogue), bit for bit the numpy reading of tests/np_gba_map.py.
+ * On the device a keyframe's pose is a function of its parent's alone, so the walk becomes a rule per keyframe: an optimised one takes
+ * its row of gba_poses; another one follows its parent in the round after the parent is done.  Three launches over the keyframes
+ * (csrc/gba_map_kernels.hip: Tchildc per keyframe; ONE workgroup that loops rounds behind a barrier until a round makes no progress;
+ * SetPose per keyframe) and one thread per point; no workspace, no host read-back, no floating-point atomics (the counts of the
+ * result record are integer atomics).  A round of the chain costs 2 us while few keyframes wait and up to 10 us when 65 535 do
+ * (profiles/gba_map_update.md): a chain of 64 under a map of 1 048 575 points is 0.14 ms, the worst chain the limit admits 0.5 - 0.7 s.
+ * Rules the data decides, the same in both forms:
+ *   a keyframe whose chain of parents does not end in an optimised keyframe -- an origin that is not optimised, a cycle, a parent that
+ *   is itself unreached -- is ORBFE_GBA_MAP_KF_UNREACHED: its record carries its old pose with that pose's Twc and Cw.  DEVIATION: the
+ *   reference reads an empty mTcwGBA there;
+ *   a point whose reference keyframe is unreached stays (the reference's `continue`, :688).
+ * Non-finite poses are not refused: they go through the arithmetic as it is.
+ * Limits, each refused with ORBFE_ERR_INVALID one step past it, before a device is looked for (pinned by tests/test_gba_map_cpu.py):
+ *   ORBFE_GBA_MAP_MAX_KEYFRAMES  65 536 keyframes (32 times ORBFE_GBA_MAX_KEYFRAMES: the map keeps growing while the adjustment runs
+ *                                and across loops): a lane of the chain's one workgroup of 1 024 keeps its keyframes in one 64-bit
+ *                                mask, and the done-marks of all of them are 8 KB of LDS; also the most rows of gba_poses
+ *   ORBFE_GBA_MAP_MAX_POINTS     16 777 216 points, the limit of orbfe_sim3_correct_points: the staging block of the host form
+ *                                (32 bytes a point in and out, 12 a row of gba_points) stays under 1 GB; also the most rows of
+ *                                gba_points */
+#define ORBFE_GBA_MAP_MAX_KEYFRAMES 65536
+#define ORBFE_GBA_MAP_MAX_POINTS 16777216
+#define ORBFE_GBA_MAP_KF_OPTIMISED 0  /* mnBAGlobalForKF == nLoopKF: the row of gba_poses */
+#define ORBFE_GBA_MAP_KF_PROPAGATED 1 /* the correction of its parent */
+#define ORBFE_GBA_MAP_KF_UNREACHED 2  /* see above: the old pose */
+typedef struct orbfe_gba_map_keyframe { /* 112 bytes, 8-byte aligned */
+  float Tcw[12];  /* the pose after the update, rows of [R | t] (mTcwGBA; the old pose of an unreached keyframe) */
+  float Twc[12];  /* SetPose's inverse of it, rows of [Rwc | Ow] */
+  float Cw[3];    /* SetPose's stereo centre */
+  int32_t status; /* ORBFE_GBA_MAP_KF_* */
+} orbfe_gba_map_keyframe;
+typedef struct orbfe_gba_map_result { /* 32 bytes */
+  int32_t n_optimised, n_propagated, n_unreached; /* keyframes per status */
+  int32_t n_taken, n_moved, n_left;               /* points that took gba_points, moved with their keyframe, stayed */
+  int32_t rounds;                                 /* propagation rounds that made progress: the longest chain of propagated keyframes */
+  int32_t reserved;
+} orbfe_gba_map_result;
+/* HOST pointers, synchronous, on the calling thread's current device: one upload, the launches, one download.
+ * poses[n_kf][12]: the current Tcw, rows of [R | t] as orbfe_global_bundle_adjustment takes them; parent[n_kf]: the row of the
+ * spanning-tree parent, -1 for an origin; kf_gba_row[n_kf]: >= 0 for an optimised keyframe, its row of gba_poses[n_gba_kf][12], -1
+ * for one that is not; half_baseline: mHalfBaseline, one value for the map.  points[n_points][3]; point_gba_row[n_points]: >= 0 takes
+ * that row of gba_points[n_gba_points][3]; ref[n_points]: the row of the reference keyframe, -1 for a point that stays (a bad one);
+ * point_gba_row wins over ref.  kf_out[n_kf], points_out[n_points][3], one result record.  Inputs are not modified.
+ * Limits (ORBFE_ERR_INVALID): 0 <= n_kf, n_gba_kf <= ORBFE_GBA_MAP_MAX_KEYFRAMES; 0 <= n_points, n_gba_points <=
+ * ORBFE_GBA_MAP_MAX_POINTS; parent and ref in -1 .. n_kf - 1, kf_gba_row in -1 .. n_gba_kf - 1, point_gba_row in -1 .. n_gba_points - 1;
+ * null arrays with a count > 0, null result; kf_out 8-byte, every other array 4-byte aligned; an output that is an input
+ * or another output. */
+int orbfe_gba_update_map(const float* poses, const int32_t* parent, const int32_t* kf_gba_row, int n_kf, const float* gba_poses,
+                         int n_gba_kf, float half_baseline, const float* points, const int32_t* point_gba_row, const int32_t* ref,
+                         int n_points, const float* gba_points, int n_gba_points, orbfe_gba_map_keyframe* kf_out, float* points_out,
+                         orbfe_gba_map_result* result);
+/* The same on DEVICE pointers, asynchronous on `stream` (NULL: the NULL stream): d_gba_poses / d_gba_points may be the d_poses_out /
+ * d_points_out of orbfe_global_bundle_adjustment_device, so the chain needs no copy.  d_points: records of point_stride bytes that
+ * start with the position.  A parent, ref or row the host cannot check is never read out of bounds: a parent or ref outside
+ * 0 .. n_kf - 1 is no parent / no reference keyframe, a kf_gba_row >= n_gba_kf makes the keyframe unreached, a point_gba_row >=
+ * n_gba_points makes the point stay; every negative row reads as -1.
+ * Limits (ORBFE_ERR_INVALID): the counts, the null pointers, the alignment and the aliasing as above; point_stride >= 12 and a
+ * multiple of 4. */
+int orbfe_gba_update_map_device(const float* d_poses, const int32_t* d_parent, const int32_t* d_kf_gba_row, int n_kf,
+                                const float* d_gba_poses, int n_gba_kf, float half_baseline, const uint8_t* d_points, int point_stride,
+                                const int32_t* d_point_gba_row, const int32_t* d_ref, int n_points, const float* d_gba_points,
+                                int n_gba_points, orbfe_gba_map_keyframe* d_kf_out, float* d_points_out, orbfe_gba_map_result* d_result,
+                                void* stream);
 
 /* ---- KeyFrameDatabase (L/src/KeyFrameDatabase.cc, D/src/ScoringObject.cpp: L1) -----------------------------------------------------
  * The first step of both place-recognition chains: DetectRelocalizationCandidates in front of orbfe_search_by_bow .. the pose

@@ -190,6 +190,14 @@ BA_ROBUST = 1
 # the ORBFE_GBA_* constants (the global bundle adjustment across the device, include/orbfe.h); the tile is no limit
 GBA_MAX_KEYFRAMES, GBA_MAX_POINTS, GBA_MAX_EDGES = 2048, 1048575, 8388600
 GBA_TILE_KEYFRAMES = 8
+# orbfe_gba_map_keyframe / orbfe_gba_map_result and the ORBFE_GBA_MAP_* constants (the map update behind the global bundle adjustment,
+# LoopClosing::RunGlobalBundleAdjustment, include/orbfe.h)
+GBA_MAP_KEYFRAME_DTYPE = np.dtype([("Tcw", "<f4", (12,)), ("Twc", "<f4", (12,)), ("Cw", "<f4", (3,)), ("status", "<i4")])
+GBA_MAP_RESULT_DTYPE = np.dtype([("n_optimised", "<i4"), ("n_propagated", "<i4"), ("n_unreached", "<i4"), ("n_taken", "<i4"),
+                                 ("n_moved", "<i4"), ("n_left", "<i4"), ("rounds", "<i4"), ("reserved", "<i4")])
+assert GBA_MAP_KEYFRAME_DTYPE.itemsize == 112 and GBA_MAP_RESULT_DTYPE.itemsize == 32
+GBA_MAP_MAX_KEYFRAMES, GBA_MAP_MAX_POINTS = 65536, 16777216
+GBA_MAP_KF_OPTIMISED, GBA_MAP_KF_PROPAGATED, GBA_MAP_KF_UNREACHED = 0, 1, 2
 # orbfe_initial_map_result and the ORBFE_IMAP_* reason bits (Tracking::CreateInitialMapMonocular, include/orbfe.h)
 INITIAL_MAP_RESULT_DTYPE = np.dtype([("n_points", "<i4"), ("tracked", "<i4"), ("median_depth", "<f4"), ("success", "<i4"), ("reason", "<i4"),
                                      ("reserved", "<i4", (3,)), ("ba", BA_RESULT_DTYPE)])
@@ -300,6 +308,7 @@ EXPORTS = [
     "orbfe_local_bundle_adjustment", "orbfe_lba_workspace_bytes", "orbfe_local_bundle_adjustment_batch_device",
     "orbfe_bundle_adjustment", "orbfe_bundle_adjustment_batch_device",
     "orbfe_global_bundle_adjustment", "orbfe_gba_workspace_bytes", "orbfe_global_bundle_adjustment_device", "orbfe_debug_gba_phases",
+    "orbfe_gba_update_map", "orbfe_gba_update_map_device",
     "orbfe_kfdb_create", "orbfe_kfdb_destroy", "orbfe_kfdb_clear", "orbfe_kfdb_size", "orbfe_kfdb_slots", "orbfe_kfdb_add", "orbfe_kfdb_erase",
     "orbfe_kfdb_set_covisibles", "orbfe_kfdb_score", "orbfe_kfdb_detect_relocalization", "orbfe_kfdb_detect_loop",
     "orbfe_kfdb_detect_relocalization_device", "orbfe_kfdb_detect_loop_device", "orbfe_debug_kfdb_arrangement",
@@ -439,6 +448,8 @@ def lib():
     L.orbfe_gba_workspace_bytes.argtypes = [ci, ci, ci, C.POINTER(sz)]
     L.orbfe_debug_gba_phases.argtypes = [ci, vp]
     L.orbfe_global_bundle_adjustment_device.argtypes = [vp, vp, vp, ci, vp, ci, ci, vp, ci, ci, ci, vp, vp, vp, vp, sz, vp]
+    L.orbfe_gba_update_map.argtypes = [vp, vp, vp, ci, vp, ci, cf, vp, vp, vp, ci, vp, ci, vp, vp, vp]
+    L.orbfe_gba_update_map_device.argtypes = [vp, vp, vp, ci, vp, ci, cf, vp, ci, vp, vp, ci, vp, ci, vp, vp, vp, vp]
     i64 = C.c_int64
     L.orbfe_kfdb_create.argtypes = [ci, ci, ci, C.POINTER(vp)]
     L.orbfe_debug_kfdb_arrangement.argtypes = [ci]

@@ -27,6 +27,11 @@ launch, the factorisation level by level with a workgroup per block): the same b
 large, and the form a loop closure wants -- it has one graph.  essential_graph_grid_device takes device tensors and a workspace of
 essential_graph_grid_workspace_bytes(...) bytes; both are synchronous.
 The map correction behind it is sim3.correct_points.
+
+gba_update_map is what LoopClosing::RunGlobalBundleAdjustment does with the adjustment's result (L/src/LoopClosing.cc:648-703): the
+correction of every keyframe the adjustment did not see through the spanning tree, SetPose's Twc and Cw of every keyframe, and every
+map point either replaced or moved with its reference keyframe (gba_map_kernels.hip).  gba_update_map_device takes device tensors --
+the two output tables of global_bundle_adjustment_device as they lie -- and is asynchronous on its stream.
 """
 from __future__ import annotations
 
@@ -37,6 +42,8 @@ import numpy as np
 from . import _lib
 from ._lib import BA_MAX_ITERATIONS, BA_RESULT_DTYPE, BA_ROBUST
 from ._lib import GBA_MAX_EDGES, GBA_MAX_KEYFRAMES, GBA_MAX_POINTS, GBA_TILE_KEYFRAMES
+from ._lib import (GBA_MAP_KEYFRAME_DTYPE, GBA_MAP_KF_OPTIMISED, GBA_MAP_KF_PROPAGATED, GBA_MAP_KF_UNREACHED, GBA_MAP_MAX_KEYFRAMES,
+                   GBA_MAP_MAX_POINTS, GBA_MAP_RESULT_DTYPE)
 from ._lib import (LBA_DROPPED, LBA_EDGE_DTYPE, LBA_ERASE, LBA_FIRST_ROUND_ONLY, LBA_PROBLEM_DTYPE, LBA_RESULT_DTYPE)
 from ._lib import (EG_DONE, EG_EDGE_DTYPE, EG_FACTOR_FAILED, EG_FIX_SCALE, EG_LOOP_CONNECTION, EG_NORMAL, EG_PROBLEM_DTYPE, EG_REFUSED,
                    EG_RESULT_DTYPE, EG_SIM3_DTYPE, EG_VERTEX_DTYPE)
@@ -50,6 +57,8 @@ __all__ = ["POSE_CAMERA_DTYPE", "POSE_RESULT_DTYPE", "POSE_DISCARD", "pose_camer
            "BA_RESULT_DTYPE", "BA_ROBUST", "BA_MAX_ITERATIONS", "bundle_adjustment", "bundle_adjustment_batch",
            "GBA_MAX_KEYFRAMES", "GBA_MAX_POINTS", "GBA_MAX_EDGES", "GBA_TILE_KEYFRAMES", "global_bundle_adjustment",
            "global_bundle_adjustment_device", "gba_workspace_bytes",
+           "GBA_MAP_KEYFRAME_DTYPE", "GBA_MAP_RESULT_DTYPE", "GBA_MAP_MAX_KEYFRAMES", "GBA_MAP_MAX_POINTS", "GBA_MAP_KF_OPTIMISED",
+           "GBA_MAP_KF_PROPAGATED", "GBA_MAP_KF_UNREACHED", "gba_update_map", "gba_update_map_device",
            "EG_SIM3_DTYPE", "EG_VERTEX_DTYPE", "EG_EDGE_DTYPE", "EG_PROBLEM_DTYPE", "EG_RESULT_DTYPE", "EG_FIX_SCALE", "EG_NORMAL",
            "EG_LOOP_CONNECTION", "EG_DONE", "EG_FACTOR_FAILED", "EG_REFUSED", "essential_graph", "essential_graph_batch",
            "essential_graph_envelope_blocks", "essential_graph_workspace_bytes",
@@ -353,3 +362,48 @@ def essential_graph_grid_device(vertices, edges, sim3_out, poses_out, result, wo
         _lib.ptr(vertices), int(vertices.shape[0]), _lib.ptr(edges), int(edges.shape[0]), EG_FIX_SCALE if fix_scale else 0,
         _lib.ptr(sim3_out), _lib.ptr(poses_out), _lib.ptr(result), _lib.ptr(workspace),
         int(workspace.numel()) * int(workspace.element_size()), _lib.stream_handle(stream)), "orbfe_essential_graph_grid_device")
+
+
+def gba_update_map(poses, parent, kf_gba_row, gba_poses, half_baseline, points, point_gba_row, ref, gba_points):
+    """orbfe_gba_update_map: the map update of LoopClosing::RunGlobalBundleAdjustment (L/src/LoopClosing.cc:648-703) behind
+    global_bundle_adjustment.  poses: (n_kf, 12) float32, the current Tcw; parent: (n_kf) int32, the row of the spanning-tree parent or -1
+    for an origin; kf_gba_row: (n_kf) int32, the row of gba_poses (m, 12) of an optimised keyframe or -1; half_baseline: mHalfBaseline;
+    points: (n, 3) float32; point_gba_row: (n) int32, the row of gba_points (q, 3) of an optimised point or -1; ref: (n) int32, the row of
+    the reference keyframe or -1 for a point that stays.  Returns (keyframes, points_out, result): GBA_MAP_KEYFRAME_DTYPE (n_kf) with
+    the new Tcw, SetPose's Twc and Cw and a GBA_MAP_KF_* status; (n, 3) float32; one GBA_MAP_RESULT_DTYPE record."""
+    poses = np.ascontiguousarray(np.asarray(poses, np.float32).reshape(-1, 12))
+    parent = np.ascontiguousarray(parent, np.int32).reshape(-1)
+    kf_gba_row = np.ascontiguousarray(kf_gba_row, np.int32).reshape(-1)
+    gba_poses = np.ascontiguousarray(np.asarray(gba_poses, np.float32).reshape(-1, 12))
+    points = np.ascontiguousarray(np.asarray(points, np.float32).reshape(-1, 3))
+    point_gba_row = np.ascontiguousarray(point_gba_row, np.int32).reshape(-1)
+    ref = np.ascontiguousarray(ref, np.int32).reshape(-1)
+    gba_points = np.ascontiguousarray(np.asarray(gba_points, np.float32).reshape(-1, 3))
+    if len(parent) != len(poses) or len(kf_gba_row) != len(poses):
+        raise ValueError("poses, parent and kf_gba_row must have one entry per keyframe")
+    if len(point_gba_row) != len(points) or len(ref) != len(points):
+        raise ValueError("points, point_gba_row and ref must have one entry per point")
+    kf_out = np.zeros(len(poses), GBA_MAP_KEYFRAME_DTYPE)
+    points_out = np.zeros_like(points)
+    res = np.zeros(1, GBA_MAP_RESULT_DTYPE)
+    opt = lambda a: _lib.ptr(a) if len(a) else None
+    _lib.check(_lib.lib().orbfe_gba_update_map(opt(poses), opt(parent), opt(kf_gba_row), len(poses), opt(gba_poses), len(gba_poses),
+                                               float(half_baseline), opt(points), opt(point_gba_row), opt(ref), len(points),
+                                               opt(gba_points), len(gba_points), opt(kf_out), opt(points_out), _lib.ptr(res)),
+               "orbfe_gba_update_map")
+    return kf_out, points_out, res[0]
+
+
+def gba_update_map_device(poses, parent, kf_gba_row, gba_poses, half_baseline, points, point_gba_row, ref, gba_points, kf_out,
+                          points_out, result, stream=None):
+    """orbfe_gba_update_map_device on torch CUDA tensors: poses (K,12) f32, parent (K) i32, kf_gba_row (K) i32, gba_poses (G,12) f32 --
+    the poses_out of global_bundle_adjustment_device as it lies --, points (M,stride) u8 whose records start with the position (or
+    (M,3) f32), point_gba_row (M) i32, ref (M) i32, gba_points (Q,3) f32 -- its points_out --; kf_out (K,112) u8 =
+    GBA_MAP_KEYFRAME_DTYPE, points_out (M,3) f32, result (32) u8 = one GBA_MAP_RESULT_DTYPE record.  Asynchronous on `stream` (a
+    torch.cuda.Stream, or None for the NULL stream)."""
+    stride = int(points.shape[1]) * int(points.element_size()) if points.dim() == 2 else 12
+    _lib.check(_lib.lib().orbfe_gba_update_map_device(
+        _lib.ptr(poses), _lib.ptr(parent), _lib.ptr(kf_gba_row), int(poses.shape[0]), _lib.ptr(gba_poses), int(gba_poses.shape[0]),
+        float(half_baseline), _lib.ptr(points), stride, _lib.ptr(point_gba_row), _lib.ptr(ref), int(points.shape[0]), _lib.ptr(gba_points),
+        int(gba_points.shape[0]), _lib.ptr(kf_out), _lib.ptr(points_out), _lib.ptr(result), _lib.stream_handle(stream)),
+        "orbfe_gba_update_map_device")
