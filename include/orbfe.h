@@ -672,6 +672,53 @@ int orbfe_kf_search(const orbfe_frame_view* keyframe, const float* inv_level_sig
                     const orbfe_kf_point* points, int n_points, int mode, int check_orientation, int max_dist,
                     uint8_t* blocked, orbfe_kf_result* results, int* n_matches);
 
+/* ---- all Fuse calls of LocalMapping::SearchInNeighbors in one batch (L/src/LocalMapping.cc:425-509) --------------------------
+ * A fuse batch keeps K target keyframes in HBM with their grids built once, and one table of candidate map points that persists
+ * between calls.  Row (k, i) -- point i searched in target k -- is, all 24 bytes, what orbfe_kf_search(targets[k], target k's
+ * 1 / sigma2 table, cams[k], point i, mode) returns, whatever K is, wherever the row stands in the batch and whether a full or a
+ * partial search computed it; a row skipped by the mask or by the point's own `skip` holds what that call writes for a skipped
+ * point (-1, 256, -1, 0, 0, 0).  The K calls of the reference depend on each other only through the map: MapPoint::Replace can
+ * change the surviving point's descriptor (ComputeDistinctiveDescriptors), so the caller searches everything once, replays the
+ * targets in order on its map and, before it enters target k + 1, searches again the points whose descriptor changed, in the
+ * targets from k + 1 on (the partial search below).  mode: ORBFE_KF_FUSE or ORBFE_KF_FUSE_SIM3.
+ * Limits (ORBFE_ERR_INVALID, checked before a device is looked for): K >= 0 and n_points >= 0 (0 launches nothing), at most 65 535
+ * keypoints per target, K x n_points within
+ * int32_t, n_levels 1 .. ORBFE_MAX_LEVELS per target, point_idx strictly ascending and within the table, first_target 0 .. K, no
+ * null pointer where a count is positive.  No CPU fallback (ORBFE_ERR_NO_DEVICE).  Pinned by tests/test_neighbors_cpu.py and
+ * tests/test_neighbors_gpu.py. */
+typedef struct orbfe_fuse_batch orbfe_fuse_batch;
+/* targets[k]: mvKeysUn, mDescriptors, mvuRight (or NULL) and the bounds of target k; cams[k] its camera; inv_level_sigma2 + k *
+ * ORBFE_MAX_LEVELS: its own mvInvLevelSigma2, cams[k].n_levels floats read (ORBFE_KF_FUSE; may be NULL for ORBFE_KF_FUSE_SIM3).
+ * Everything is copied: one packed upload, one grid-build launch for all K (targets whose image bounds differ -- several cameras --
+ * get a launch each: the grid geometry is a launch constant).  HOST pointers, synchronous. */
+int orbfe_fuse_batch_create(int K, const orbfe_frame_view* targets, const orbfe_kf_camera* cams, const float* inv_level_sigma2,
+                            int mode, orbfe_fuse_batch** out);
+/* The same with the arrays already in HBM, target k at offset k * cap (keypoints, descriptors x 32, u_right; d_u_right may be NULL,
+ * a keypoint without a right coordinate holds a negative value), d_n[k] <= cap keypoints each, 1 <= cap <= 65 535.  The arrays are
+ * BORROWED: they stay the caller's and must outlive the handle unchanged.  The grids are built on `stream` (NULL: the handle's own);
+ * searches on another stream are the caller's to order behind it. */
+int orbfe_fuse_batch_create_device(int K, const orbfe_keypoint* d_keys, const uint8_t* d_desc, const float* d_u_right, const int32_t* d_n,
+                                   int cap, float min_x, float max_x, float min_y, float max_y, const orbfe_kf_camera* d_cams,
+                                   const float* d_inv_level_sigma2, int mode, void* stream, orbfe_fuse_batch** out);
+/* A batch lives for one keyframe: a destroyed handle leaves its stream, device blocks and pinned mirrors to the next handle the
+ * calling thread creates (allocating them costs more than the searches); orbfe_thread_release() frees what is left, and a thread
+ * that ends without calling it keeps them until the process ends, as it keeps its implicit matcher handle.  Destroy waits for the
+ * handle's own stream and for the work it enqueued on the caller's streams (an event behind each), not for the rest of the device, so
+ * the blocks change hands idle.  A handle serialises its own calls (internal mutex). */
+int orbfe_fuse_batch_destroy(orbfe_fuse_batch* b);
+/* point_idx == NULL: `points` (n_points records) REPLACES the resident table and every row (k >= first_target, i) is searched;
+ * n_idx is ignored.  point_idx != NULL (n_idx entries, strictly ascending, n_points = the resident table's size): points[j] replaces
+ * record point_idx[j] and only the rows (k >= first_target, i in point_idx) are searched.  skip: NULL, or K x n_points bytes, non-zero
+ * = the row is known to be skipped (NULL, bad, already in that keyframe); it only saves work.  results: K x n_points, row (k, i) at
+ * k * n_points + i; only searched rows are written, every other byte is left as it was.  HOST pointers, synchronous. */
+int orbfe_fuse_batch_search(orbfe_fuse_batch* b, const orbfe_kf_point* points, int n_points, const int32_t* point_idx, int n_idx,
+                            int first_target, const uint8_t* skip, orbfe_kf_result* results);
+/* The same with the records, the index list, the mask and the results in HBM, asynchronous on `stream` (NULL: the handle's own); the
+ * host form makes the same launches between its packed upload and download.  An index outside the table, which only the host form
+ * can refuse, is dropped. */
+int orbfe_fuse_batch_search_device(orbfe_fuse_batch* b, const orbfe_kf_point* d_points, int n_points, const int32_t* d_point_idx,
+                                   int n_idx, int first_target, const uint8_t* d_skip, orbfe_kf_result* d_results, void* stream);
+
 /* SearchForTriangulation(KeyFrame *pKF1, KeyFrame *pKF2, cv::Mat F12, vMatchedPairs, bOnlyStereo) (L/src/ORBmatcher.cc:614-764)
  * with CheckDistEpipolarLine (:137-159).  The epipole (:622-630) is computed by the caller. */
 typedef struct orbfe_epipolar {

@@ -324,6 +324,8 @@ EXPORTS = [
     "orbfe_vocabulary_nodes", "orbfe_vocabulary_write_text", "orbfe_vocabulary_write_binary", "orbfe_vocabulary_save_text",
     "orbfe_vocabulary_save_binary", "orbfe_vocabulary_training_draw", "orbfe_vocabulary_train_workspace_bytes", "orbfe_vocabulary_train",
     "orbfe_vocabulary_train_device", "orbfe_debug_vocabulary_train_levels",
+    "orbfe_fuse_batch_create", "orbfe_fuse_batch_create_device", "orbfe_fuse_batch_destroy", "orbfe_fuse_batch_search",
+    "orbfe_fuse_batch_search_device",
 ]
 
 
@@ -410,6 +412,11 @@ def lib():
     L.orbfe_compute_bow.argtypes = [vp, vp, ci, ci, vp, vp, vp, vp, vp, pi, vp, vp, pi]
     L.orbfe_proj_best.argtypes = [C.POINTER(FrameView), vp, ci, ci, vp, ci, vp, vp]
     L.orbfe_kf_search.argtypes = [C.POINTER(FrameView), vp, vp, vp, ci, ci, ci, ci, vp, vp, pi]
+    L.orbfe_fuse_batch_create.argtypes = [ci, vp, vp, vp, ci, C.POINTER(vp)]
+    L.orbfe_fuse_batch_create_device.argtypes = [ci, vp, vp, vp, vp, ci, cf, cf, cf, cf, vp, vp, ci, vp, C.POINTER(vp)]
+    L.orbfe_fuse_batch_destroy.argtypes = [vp]
+    L.orbfe_fuse_batch_search.argtypes = [vp, vp, ci, vp, ci, ci, vp, vp]
+    L.orbfe_fuse_batch_search_device.argtypes = [vp, vp, ci, vp, ci, ci, vp, vp, vp]
     L.orbfe_search_for_triangulation.argtypes = [vp, vp, vp, vp, ci, vp, ci, vp, vp, vp, vp, vp, ci, vp, ci, vp, vp, ci, ci, vp, pi]
     L.orbfe_search_by_bow_kf.argtypes = [vp, vp, vp, ci, vp, ci, vp, vp, vp, vp, ci, vp, ci, vp, cf, ci, vp, pi]
     L.orbfe_search_by_bow.argtypes = [vp, vp, vp, ci, vp, ci, vp, vp, vp, ci, vp, ci, vp, cf, ci, vp, pi]

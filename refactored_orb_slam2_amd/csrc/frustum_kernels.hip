@@ -5,58 +5,17 @@
 #include <hip/hip_runtime.h>
 
 #include "match_internal.h"
+#include "search_device.h"   // WAVE, predict_scale, kf_project
 
 #define FQ_THREADS 256
-#define WAVE 64
 #define MP_DW (int)(sizeof(orbfe_map_point) / 4)   // 18
 #define Q_DW (int)(sizeof(orbfe_query) / 4)        // 17
 #define TR_DW (int)(sizeof(orbfe_track) / 4)       // 6
 static_assert(sizeof(orbfe_last_point) == 60 && sizeof(orbfe_track_pose) == 160 && sizeof(orbfe_unproject_cam) == 64, "record layout");
 static_assert(sizeof(orbfe_map_point) == 72 && sizeof(orbfe_query) == 68 && sizeof(orbfe_track) == 24, "record layout");
 
-// glibc 2.35 logf (__logf_data, LOGF_TABLE_BITS = 4): {invc, logc} pairs.  Same constants as the oracle's oo_logf; the
-// arithmetic below is the same double sequence (compiled with -ffp-contract=off).
-__device__ const double g_logf_tab[32] = {
-    0x1.661ec79f8f3bep+0, -0x1.57bf7808caadep-2, 0x1.571ed4aaf883dp+0, -0x1.2bef0a7c06ddbp-2,
-    0x1.49539f0f010b0p+0, -0x1.01eae7f513a67p-2, 0x1.3c995b0b80385p+0, -0x1.b31d8a68224e9p-3,
-    0x1.30d190c8864a5p+0, -0x1.6574f0ac07758p-3, 0x1.25e227b0b8ea0p+0, -0x1.1aa2bc79c8100p-3,
-    0x1.1bb4a4a1a343fp+0, -0x1.a4e76ce8c0e5ep-4, 0x1.12358f08ae5bap+0, -0x1.1973c5a611cccp-4,
-    0x1.0953f419900a7p+0, -0x1.252f438e10c1ep-5, 0x1.0000000000000p+0, 0x0.0p+0,
-    0x1.e608cfd9a47acp-1, 0x1.aa5aa5df25984p-5,  0x1.ca4b31f026aa0p-1, 0x1.c5e53aa362eb4p-4,
-    0x1.b2036576afce6p-1, 0x1.526e57720db08p-3,  0x1.9c2d163a1aa2dp-1, 0x1.bc2860d224770p-3,
-    0x1.886e6037841edp-1, 0x1.1058bc8a07ee1p-2,  0x1.767dcf5534862p-1, 0x1.4043057b6ee09p-2};
-
-// MapPoint::PredictScale.  Inputs logf does not map to a finite value (ratio 0, subnormal, inf, nan, negative) make the
-// reference's float->int conversion produce INT_MIN on x86-64 (cvttss2si), hence level 0 after the clamp.
-__device__ __forceinline__ int predict_scale(float max_distance, float dist, float log_scale_factor, int n_levels) {
-  const float ratio = max_distance / dist;
-  const uint32_t ix = __float_as_uint(ratio);
-  float l;
-  if (ix == 0x3f800000u) {
-    l = 0.0f;
-  } else if (ix - 0x00800000u >= 0x7f800000u - 0x00800000u) {
-    return 0;
-  } else {
-    const uint32_t tmp = ix - 0x3f330000u;
-    const int i = (int)((tmp >> 19) & 15u);
-    const int k = (int32_t)tmp >> 23;
-    const uint32_t iz = ix - (tmp & (0x1ffu << 23));
-    const double z = (double)__uint_as_float(iz);
-    const double r = z * g_logf_tab[2 * i] - 1.0;
-    const double y0 = g_logf_tab[2 * i + 1] + (double)k * 0x1.62e42fefa39efp-1;
-    const double r2 = r * r;
-    double y = 0x1.5575b0be00b6ap-2 * r + -0x1.ffffef20a4123p-2;
-    y = -0x1.00ea348b88334p-2 * r2 + y;
-    y = y * r2 + (y0 + r);
-    l = (float)y;
-  }
-  const float c = ceilf(l / log_scale_factor);
-  if (!(c >= -2147483648.0f && c < 2147483648.0f)) return 0;  // INT_MIN -> clamped to 0
-  int nScale = (int)c;
-  if (nScale < 0) nScale = 0;
-  else if (nScale >= n_levels) nScale = n_levels - 1;
-  return nScale;
-}
+// predict_scale (MapPoint::PredictScale with glibc's logf) and kf_project, the projection prologue of the keyframe-rate searches, are
+// stated in search_device.h: fuse_kernels.hip runs them too.
 
 // One thread per local map point; a block stages its 256 records through LDS so that the 72-byte inputs and the 68-byte
 // queries move as coalesced dwords.
@@ -351,10 +310,8 @@ __global__ __launch_bounds__(TQS_T) void track_queries_stereo_kernel(TqsFrame B,
 }
 
 // ---- projection prologue of Fuse / Fuse(Sim3) / SearchBySim3 / SearchByProjection(KF,Scw) / SearchByProjection(Frame,KF,...)
-// (L/src/ORBmatcher.cc:785-816, 925-977, 1075-1113 & 1155-1192, 296-345, 1406-1437): thread per candidate map point.  Every
-// float expression is written in the operation order of the mode's reference lines (`1 / z` is a float division, `1.0 / z` a
-// double one; Fuse multiplies X * invz first, the relocalisation search fx * xc first); cv::Mat products are the small-matrix
-// gemm (float dot, double alpha/beta epilogue), cv::norm / Mat::dot accumulate in double -- as in frustum_queries_kernel.
+// (L/src/ORBmatcher.cc:785-816, 925-977, 1075-1113 & 1155-1192, 296-345, 1406-1437): thread per candidate map point, kf_project of
+// search_device.h on the camera record staged in LDS.
 static_assert(sizeof(orbfe_kf_camera) == 220 && sizeof(orbfe_kf_point) == 72 && sizeof(orbfe_kf_result) == 24, "record layout");
 __global__ __launch_bounds__(256) void kf_queries_kernel(const orbfe_kf_camera* __restrict__ camp, const orbfe_kf_point* __restrict__ points,
                                                          int n, int mode, orbfe_query* __restrict__ queries,
@@ -372,72 +329,7 @@ __global__ __launch_bounds__(256) void kf_queries_kernel(const orbfe_kf_camera* 
   for (int j = 0; j < Q_DW; j++) qw[j] = 0u;
   orbfe_kf_result res;
   res.best_idx = -1; res.best_dist = 256; res.level = -1; res.u = 0.f; res.v = 0.f; res.u_r = 0.f;
-  if (!mp.skip) {
-    float Pc[3];
-#pragma unroll
-    for (int r = 0; r < 3; r++) {
-      const float t = cam.R[3 * r] * mp.pos[0] + cam.R[3 * r + 1] * mp.pos[1] + cam.R[3 * r + 2] * mp.pos[2];
-      Pc[r] = (float)((double)t * 1.0 + (double)cam.t[r] * 1.0);
-    }
-    if (mode == ORBFE_KF_SIM3) {   // p3Dc2 = sR21 * p3Dc1 + t21 (:1075) / p3Dc1 = sR12 * p3Dc2 + t12 (:1155)
-      float P2[3];
-#pragma unroll
-      for (int r = 0; r < 3; r++) {
-        const float t = cam.R2[3 * r] * Pc[0] + cam.R2[3 * r + 1] * Pc[1] + cam.R2[3 * r + 2] * Pc[2];
-        P2[r] = (float)((double)t * 1.0 + (double)cam.t2[r] * 1.0);
-      }
-      Pc[0] = P2[0]; Pc[1] = P2[1]; Pc[2] = P2[2];
-    }
-    bool ok = mode == ORBFE_KF_RELOC || !(Pc[2] < 0.0f);   // "Depth must be positive"; the relocalisation search has no such test
-    float invz = 0.f, u = 0.f, v = 0.f;
-    if (ok) {
-      if (mode == ORBFE_KF_FUSE || mode == ORBFE_KF_LOOP) invz = 1.0f / Pc[2];        // `1 / z`   (:797, :317)
-      else invz = (float)(1.0 / (double)Pc[2]);                                        // `1.0 / z` (:945, :1083, :1163, :1413)
-      if (mode == ORBFE_KF_RELOC) {                                                    // fx * xc * invzc + cx (:1415-1416)
-        u = cam.fx * Pc[0] * invz + cam.cx;
-        v = cam.fy * Pc[1] * invz + cam.cy;
-        ok = !(u < cam.min_x || u > cam.max_x) && !(v < cam.min_y || v > cam.max_y);   // :1418-1421
-      } else {                                                                         // x = X * invz; u = fx * x + cx
-        const float x = Pc[0] * invz, y = Pc[1] * invz;
-        u = cam.fx * x + cam.cx;
-        v = cam.fy * y + cam.cy;
-        ok = u >= cam.min_x && u < cam.max_x && v >= cam.min_y && v < cam.max_y;       // KeyFrame::IsInImage (KeyFrame.cc:569-571)
-      }
-    }
-    if (ok) {
-      const float maxDistance = 1.2f * mp.max_distance, minDistance = 0.8f * mp.min_distance;   // Get{Max,Min}DistanceInvariance
-      double s = 0.0, dot = 0.0;
-      if (mode == ORBFE_KF_SIM3) {
-#pragma unroll
-        for (int k = 0; k < 3; k++) s += (double)Pc[k] * (double)Pc[k];   // cv::norm(p3Dc2) (:1097)
-      } else {
-#pragma unroll
-        for (int k = 0; k < 3; k++) {
-          const float PO = mp.pos[k] - cam.Ow[k];
-          s += (double)PO * (double)PO;
-          dot += (double)PO * (double)mp.normal[k];
-        }
-      }
-      const float dist3D = (float)sqrt(s);
-      ok = !(dist3D < minDistance || dist3D > maxDistance);
-      if (ok && (mode == ORBFE_KF_FUSE || mode == ORBFE_KF_FUSE_SIM3 || mode == ORBFE_KF_LOOP))
-        ok = !(dot < 0.5 * (double)dist3D);   // "Viewing angle must be less than 60 deg": PO.dot(Pn) < 0.5 * dist
-      if (ok) {
-        const int level = predict_scale(mp.max_distance, dist3D, cam.log_scale_factor, cam.n_levels);
-        q.u = u; q.v = v;
-        q.u_r = u - cam.mbf * invz;   // Fuse :808
-        q.radius = cam.th * cam.scale_factors[level];
-        q.min_level = level - 1;
-        q.max_level = mode == ORBFE_KF_RELOC ? level + 1 : level;
-        q.valid = 1;
-        q.blocks = 1;
-        q.angle = mp.angle;
-#pragma unroll
-        for (int j = 0; j < 8; j++) reinterpret_cast<uint32_t*>(q.desc)[j] = reinterpret_cast<const uint32_t*>(mp.desc)[j];
-        res.level = level; res.u = u; res.v = v; res.u_r = q.u_r;
-      }
-    }
-  }
+  kf_project(cam, mp, mode, q, res);
   queries[i] = q;
   results[i] = res;
 }

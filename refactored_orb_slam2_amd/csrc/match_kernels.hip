@@ -15,44 +15,7 @@
 #include <mutex>
 
 #include "match_internal.h"
-
-#define WAVE 64
-
-__device__ __forceinline__ int hamming256(const uint4 a0, const uint4 a1, const uint4 b0, const uint4 b1) {
-  return __popc(a0.x ^ b0.x) + __popc(a0.y ^ b0.y) + __popc(a0.z ^ b0.z) + __popc(a0.w ^ b0.w) +
-         __popc(a1.x ^ b1.x) + __popc(a1.y ^ b1.y) + __popc(a1.z ^ b1.z) + __popc(a1.w ^ b1.w);
-}
-__device__ __forceinline__ void load_desc(const uint8_t* p, uint4& d0, uint4& d1) {
-  const uint4* q = reinterpret_cast<const uint4*>(p);
-  d0 = q[0];
-  d1 = q[1];
-}
-// descriptors that are only 4-byte aligned (queries embedded in 68-byte records)
-__device__ __forceinline__ void load_desc4(const uint8_t* p, uint4& d0, uint4& d1) {
-  const uint32_t* q = reinterpret_cast<const uint32_t*>(p);
-  d0 = make_uint4(q[0], q[1], q[2], q[3]);
-  d1 = make_uint4(q[4], q[5], q[6], q[7]);
-}
-
-__device__ __forceinline__ unsigned wave_min_u32(unsigned v) {
-  // DPP reduction (row shifts, then row broadcasts): lane 63 ends up with the minimum of all 64 lanes
-#define ORBFE_MIN_STEP(ctrl, rmask) v = min(v, (unsigned)__builtin_amdgcn_update_dpp((int)0xffffffff, (int)v, ctrl, rmask, 0xf, false))
-  ORBFE_MIN_STEP(0x111, 0xf); ORBFE_MIN_STEP(0x112, 0xf); ORBFE_MIN_STEP(0x114, 0xf); ORBFE_MIN_STEP(0x118, 0xf);
-  ORBFE_MIN_STEP(0x142, 0xa); ORBFE_MIN_STEP(0x143, 0xc);
-#undef ORBFE_MIN_STEP
-  return (unsigned)__builtin_amdgcn_readlane((int)v, 63);
-}
-__device__ __forceinline__ int wave_incl_scan_i(int v) {
-  // DPP row shifts + row broadcasts (gfx9): six VALU adds, no LDS crossbar round trips (ds_bpermute) as with __shfl_up
-  v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xf, 0xf, false);  // row_shr:1
-  v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xf, 0xf, false);  // row_shr:2
-  v += __builtin_amdgcn_update_dpp(0, v, 0x114, 0xf, 0xf, false);  // row_shr:4
-  v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xf, 0xf, false);  // row_shr:8
-  v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xa, 0xf, false);  // row_bcast:15 -> rows 1, 3
-  v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xc, 0xf, false);  // row_bcast:31 -> rows 2, 3
-  return v;
-}
-__device__ __forceinline__ int wave_sum_i32(int v) { return __builtin_amdgcn_readlane(wave_incl_scan_i(v), 63); }
+#include "search_device.h"   // WAVE, the wave helpers, hamming256, enumerate_window
 
 // ------------------------------------------------------------------------------------------------ all pairs
 // Thread = one B column (descriptor in registers); a block stages 64 A rows in LDS; stores are coalesced
@@ -353,99 +316,7 @@ __global__ __launch_bounds__(GB_THREADS) void grid_build_global_kernel(FrameBatc
   }
 }
 
-// Enumerates, in the reference's order, the keypoints GetFeaturesInArea returns for query q that also pass the
-// matcher's stereo gate, and calls fn(rank, idx, dist) for each, wave-cooperatively: a chunk of up to 64
-// consecutive grid entries is tested per step, survivors get consecutive ranks.  Returns the survivor count.
-// GATE 0: the matcher's stereo gate |u_r - mvuRight| <= radius (SearchByProjection); 1: none (Fuse(Sim3), SearchBySim3);
-// 2: Fuse's chi-square reprojection gate (L/src/ORBmatcher.cc:833-854) with inv_sigma2 = mvInvLevelSigma2
-template <int GATE = 0, typename Fn>
-__device__ __forceinline__ int enumerate_window(const FrameBatch& F, int f, const orbfe_query& q, const uint4 q0,
-                                                const uint4 q1, Fn fn, const float* inv_sigma2 = nullptr) {
-  const int lane = threadIdx.x & (WAVE - 1);
-  const float x = q.u, y = q.v, r = q.radius;
-  const int nMinCellX = max(0, (int)floorf((x - F.min_x - r) * F.gw_inv));
-  if (nMinCellX >= ORBFE_GRID_COLS) return 0;
-  const int nMaxCellX = min(ORBFE_GRID_COLS - 1, (int)ceilf((x - F.min_x + r) * F.gw_inv));
-  if (nMaxCellX < 0) return 0;
-  const int nMinCellY = max(0, (int)floorf((y - F.min_y - r) * F.gh_inv));
-  if (nMinCellY >= ORBFE_GRID_ROWS) return 0;
-  const int nMaxCellY = min(ORBFE_GRID_ROWS - 1, (int)ceilf((y - F.min_y + r) * F.gh_inv));
-  if (nMaxCellY < 0) return 0;
-  const bool bCheckLevels = (q.min_level > 0) || (q.max_level >= 0);
-  const uint8_t* desc = F.desc + (size_t)f * F.cap * 32;
-  const bool has_ur = F.u_right != nullptr;
-  const int32_t* cs = F.cell_start + (size_t)f * (GRID_CELLS + 1);
-  const uint4* cr = reinterpret_cast<const uint4*>(F.cell_rec) + (size_t)f * F.cap;
-  // The window's cells of one grid column (ix, nMinCellY..nMaxCellY) are adjacent in CSR order.  Lane c fetches
-  // column c's range; the ranges are concatenated (prefix sum) into one flat candidate sequence -- column-major, then
-  // cell row, then ascending index: the reference's enumeration order -- that the wave consumes 64 entries at a time.
-  const int ncol = __builtin_amdgcn_readfirstlane(nMaxCellX - nMinCellX + 1);  // <= 64; the query is wave-uniform
-  int e0c = 0, cntc = 0;
-  if (lane < ncol) {
-    const int ix = nMinCellX + lane;
-    e0c = cs[ix * ORBFE_GRID_ROWS + nMinCellY];
-    cntc = cs[ix * ORBFE_GRID_ROWS + nMaxCellY + 1] - e0c;
-  }
-  const int inclc = wave_incl_scan_i(cntc);
-  const int exclc = inclc - cntc;
-  const int n_entries = __builtin_amdgcn_readlane(inclc, WAVE - 1);
-  int rank0 = 0;
-  for (int base = 0; base < n_entries; base += WAVE) {
-    const int t = base + lane;
-    int ent = -1;
-    for (int c = 0; c < ncol; c++) {
-      const int oc = __builtin_amdgcn_readlane(exclc, c), nc = __builtin_amdgcn_readlane(cntc, c), ec = __builtin_amdgcn_readlane(e0c, c);
-      if (t >= oc && t < oc + nc) ent = ec + (t - oc);
-    }
-    bool ok = false;
-    int idx = 0, oct = 0;
-    if (ent >= 0) {
-      const uint4 rec = cr[ent];
-      idx = (int)(rec.x & 0xFFFFFFu);
-      oct = (int)(rec.x >> 24);
-      const float kx = __int_as_float((int)rec.y), ky = __int_as_float((int)rec.z), kur = __int_as_float((int)rec.w);
-      ok = true;
-      if (bCheckLevels) {
-        if (oct < q.min_level) ok = false;
-        if (q.max_level >= 0 && oct > q.max_level) ok = false;
-      }
-      const float distx = kx - x, disty = ky - y;
-      if (!(fabsf(distx) < r && fabsf(disty) < r)) ok = false;
-      if (GATE == 0) {
-        if (ok && has_ur) {
-          const float u = kur;
-          if (u > 0) {
-            const float er = fabsf(q.u_r - u);
-            if (er > r) ok = false;
-          }
-        }
-      } else if (GATE == 2) {
-        if (ok) {
-          const float kpr = kur;   // -1 without mvuRight
-          const float ex = x - kx, ey = y - ky;
-          const float invs = inv_sigma2[oct & (ORBFE_MAX_LEVELS - 1)];   // the mask only guards memory
-          if (kpr >= 0) {
-            const float er = q.u_r - kpr;
-            const float e2 = ex * ex + ey * ey + er * er;
-            if ((double)(e2 * invs) > 7.8) ok = false;
-          } else {
-            const float e2 = ex * ex + ey * ey;
-            if ((double)(e2 * invs) > 5.99) ok = false;
-          }
-        }
-      }
-    }
-    const unsigned long long m = __ballot(ok);
-    if (ok) {
-      uint4 d0, d1;
-      load_desc(desc + (size_t)idx * 32, d0, d1);
-      const int rank = rank0 + __popcll(m & ((1ull << lane) - 1ull));
-      fn(rank, idx, hamming256(q0, q1, d0, d1), oct);
-    }
-    rank0 += __popcll(m);
-  }
-  return rank0;
-}
+// enumerate_window (search_device.h) walks a query's window in the reference's order, wave-cooperatively.
 
 // One wave per query, independent arg-min (no query blocks another): Fuse, Fuse(Sim3), SearchBySim3.  best = first
 // minimum in GetFeaturesInArea order (strict `dist < bestDist`).

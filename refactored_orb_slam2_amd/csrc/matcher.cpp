@@ -228,7 +228,9 @@ static int tls_matcher(orbfe_matcher** out) {
   *out = t.m;
   return ORBFE_OK;
 }
+void orbfe_fuse_release_spare();   // fuse.cpp: what the thread's last fuse batch left for the next
 extern "C" int orbfe_thread_release(void) {
+  orbfe_fuse_release_spare();
   TlsMatcher& t = t_tls_matcher;
   if (!t.m) return ORBFE_OK;
   orbfe_matcher* m = t.m;

@@ -415,3 +415,97 @@ def compute_stereo_matches(ex_left, ex_right, kps_l, desc_l, kps_r, desc_r, mbf,
                                     _lib.ptr(desc_r), len(kps_r), float(np.float32(mbf)), float(np.float32(mb)), _lib.ptr(ur),
                                     _lib.ptr(depth), C.byref(nm)), "orbfe_stereo_match")
     return nm.value, ur, depth
+
+
+class FuseBatch:
+    """orbfe_fuse_batch: K target keyframes resident in HBM with their grids built once, and one table of candidate map points
+    that persists between searches -- every ORBmatcher::Fuse call of LocalMapping::SearchInNeighbors in one launch, and the rows
+    of a few points again when their descriptors have changed.
+
+    targets: K FrameViews (each with its own image bounds); cameras: K KF_CAMERA_DTYPE records (th inside); inv_level_sigma2: K
+    tables (each target's own mvInvLevelSigma2), required for KF_FUSE."""
+
+    def __init__(self, targets, cameras, inv_level_sigma2=None, mode: int = _lib.KF_FUSE):
+        self._L = _lib.lib()
+        self._h = C.c_void_p(None)
+        self.K = len(targets)
+        self.n_points = 0
+        views = (_lib.FrameView * max(self.K, 1))(*[t.c for t in targets])
+        cams = np.ascontiguousarray(cameras, _lib.KF_CAMERA_DTYPE).reshape(-1)
+        if len(cams) != self.K:
+            raise ValueError("one camera record per target")
+        inv = None
+        if inv_level_sigma2 is not None:
+            inv = np.zeros((max(self.K, 1), 16), np.float32)
+            for k, t in enumerate(inv_level_sigma2):
+                t = np.asarray(t, np.float32).reshape(-1)
+                inv[k, :len(t)] = t
+        self._keep = (targets, views)   # the arrays stay alive until the library has copied them
+        _lib.check(self._L.orbfe_fuse_batch_create(self.K, C.cast(views, C.c_void_p), _lib.ptr(cams), _lib.ptr(inv), int(mode),
+                                                   C.byref(self._h)), "orbfe_fuse_batch_create")
+        self._keep = None
+
+    @classmethod
+    def from_device(cls, kps, desc, u_right, n, bounds, cameras, inv_level_sigma2, mode: int = _lib.KF_FUSE, stream=None):
+        """orbfe_fuse_batch_create_device: torch CUDA tensors kps (K,cap,28) u8, desc (K,cap,32) u8, u_right (K,cap) f32 or None, n (K)
+        i32, cameras (K,220) u8, inv_level_sigma2 (K,16) f32 or None.  The tensors are borrowed: the handle keeps them alive."""
+        self = cls.__new__(cls)
+        self._L = _lib.lib()
+        self._h = C.c_void_p(None)
+        self.K, cap = int(desc.shape[0]), int(desc.shape[1])
+        self.n_points = 0
+        self._keep = (kps, desc, u_right, n, cameras, inv_level_sigma2)
+        _lib.check(self._L.orbfe_fuse_batch_create_device(self.K, _lib.ptr(kps), _lib.ptr(desc), _lib.ptr(u_right), _lib.ptr(n), cap,
+                                                          *[float(b) for b in bounds], _lib.ptr(cameras), _lib.ptr(inv_level_sigma2),
+                                                          int(mode), _lib.stream_handle(stream), C.byref(self._h)),
+                   "orbfe_fuse_batch_create_device")
+        return self
+
+    def search_device(self, points, n_points, point_idx, first_target, skip, results, stream=None):
+        """orbfe_fuse_batch_search_device: torch CUDA tensors (points: KF_POINT records as bytes, point_idx i32 or None, skip u8 or
+        None, results (K, n_points, 24) u8), asynchronous on `stream`."""
+        _lib.check(self._L.orbfe_fuse_batch_search_device(self._h, _lib.ptr(points), int(n_points), _lib.ptr(point_idx),
+                                                          0 if point_idx is None else int(point_idx.numel()), int(first_target),
+                                                          _lib.ptr(skip), _lib.ptr(results), _lib.stream_handle(stream)),
+                   "orbfe_fuse_batch_search_device")
+        if point_idx is None:
+            self.n_points = int(n_points)
+
+    def close(self):
+        if getattr(self, "_h", None) and self._h.value:
+            self._L.orbfe_fuse_batch_destroy(self._h)
+            self._h = C.c_void_p(None)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def search(self, points, point_idx=None, first_target: int = 0, skip=None, results=None, n_points=None):
+        """point_idx None: `points` (KF_POINT_DTYPE) replaces the resident table and every row (k >= first_target, i) is searched.
+        Otherwise points[j] replaces record point_idx[j] (strictly ascending) and only those points' rows are searched.  skip: None
+        or a (K, n_points) byte mask of rows known to be skipped.  results: a (K, n_points) KF_RESULT_DTYPE array to update in
+        place (rows that are not searched keep their bytes); a new zeroed one when None.  Returns results."""
+        pts = np.ascontiguousarray(points, _lib.KF_POINT_DTYPE).reshape(-1)
+        idx = None if point_idx is None else np.ascontiguousarray(point_idx, np.int32).reshape(-1)
+        if n_points is None:
+            n_points = len(pts) if idx is None else self.n_points
+        if idx is not None and len(idx) != len(pts):
+            raise ValueError("one record per index")
+        if results is None:
+            results = np.zeros((self.K, n_points), _lib.KF_RESULT_DTYPE)
+        if results.dtype != _lib.KF_RESULT_DTYPE or results.size != self.K * n_points or not results.flags.c_contiguous:
+            raise ValueError("results: contiguous (K, n_points) KF_RESULT_DTYPE")
+        msk = None
+        if skip is not None:
+            msk = np.ascontiguousarray(skip, np.uint8)
+            if msk.size != self.K * n_points:
+                raise ValueError("skip: (K, n_points) bytes")
+        keep = np.zeros(1, np.int32)   # an empty list still is a list: a non-null pointer
+        idx_ptr = None if idx is None else _lib.ptr(idx if len(idx) else keep)
+        _lib.check(self._L.orbfe_fuse_batch_search(self._h, _lib.ptr(pts), int(n_points), idx_ptr, 0 if idx is None else len(idx),
+                                                   int(first_target), _lib.ptr(msk), _lib.ptr(results)), "orbfe_fuse_batch_search")
+        if idx is None:
+            self.n_points = n_points
+        return results
