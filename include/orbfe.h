@@ -138,6 +138,9 @@ int orbfe_device_download(void* h_dst, const void* d_src, size_t bytes);
  *   covisibility graph  at most 32 768 keyframe rows, 2 048 entries per subject (conn_cap), 65 535 subjects or problems per launch,
  *                       16 777 216 slots and 1 048 576 local keyframes per call, the point and observation limits of the map-point
  *                       refresh (the ORBFE_COV_MAX_* constants, each with its reason; pinned by tests/test_covis_cpu.py)
+ *   local map           at most 65 535 frames per launch, kf_cap <= 2 051, p_cap <= 1 048 576, 16 777 216 also-seen indices, the table
+ *                       limits of the covisibility graph (the ORBFE_LM_MAX_* constants, each with its reason; pinned by
+ *                       tests/test_localmap_cpu.py)
  *   essential graph     at most 32 768 vertices, 262 144 edges and 131 072 envelope blocks per problem, 65 535 problems per launch,
  *                       16 777 216 points per map correction (the ORBFE_EG_MAX_* constants, each with its reason; pinned by
  *                       tests/test_egraph_cpu.py and tests/test_egraph_gpu.py)
@@ -1520,7 +1523,8 @@ int orbfe_refresh_map_points_batch_device(int P, const orbfe_mp_keyframe* d_keyf
  *    [-1, n_kf) (CONNECTIONS), a slot < -1 or >= n_points, a good point whose list lies outside the observation array, an observation
  *    whose kf is outside [0, n_kf), or a kf_order outside [0, n_kf) on an observed row.  Entries behind n_written are never written.
  *    With the caller stay: the reciprocal AddConnection calls, UpdateBestCovisibles of the other keyframes, the spanning-tree parent,
- *    the neighbour / child / parent expansion of UpdateLocalKeyFrames up to 80 keyframes, and clearing bad points out of the frame;
+ *    the neighbour / child / parent expansion of UpdateLocalKeyFrames up to 80 keyframes (or orbfe_local_map* below, which takes it
+ *    and UpdateLocalPoints to the device), and clearing bad points out of the frame;
  *    csrc/host/Covisibility_hip.h replays them in the reference's order.
  *
  * 2. Keyframe culling, one problem per current keyframe: an ordered list of DISTINCT local keyframe rows
@@ -1642,6 +1646,104 @@ int orbfe_covis_cull_keyframes_batch_device(int Q, const orbfe_mp_obs* d_obs, in
                                             const uint8_t* d_point_bad, const int32_t* d_n_obs_weighted, int n_points,
                                             const orbfe_cov_keyframe* d_keyframes, int n_kf, const int32_t* d_local, int n_local_total,
                                             const orbfe_cov_problem* d_problems, orbfe_cov_verdict* d_verdicts, void* stream);
+
+/* ---- The local map of a tracked frame: Tracking::UpdateLocalKeyFrames behind its vote (L/src/Tracking.cc:1161-1214),
+ * Tracking::UpdateLocalPoints (:1090-1113) and the skip flag of Tracking::SearchLocalPoints (:1036-1049, :1057-1060) ----------------------
+ * One frame is one subject of the vote (mode ORBFE_COV_VOTES): the call consumes the vote's headers and entries exactly as
+ * orbfe_covis_count* left them (conn_cap included) and reads, beside the tables the vote read (kf_bad, point_bad, the slot array and
+ * the frame's orbfe_cov_subject), one orbfe_lm_graph row per keyframe row, the children array, and of the orbfe_cov_keyframe table
+ * `slots` and `n_keys` alone.  Per frame, read literally (csrc/localmap_internal.h states it once):
+ *   Expansion.  The list starts as the vote's entries, all marked.  For each VOTED entry in order (the reference takes its end
+ *     iterator before the loop): stop if the list holds more than 80 rows; append and mark the first of best[0 .. n_best) that is
+ *     not bad and not marked (GetBestCovisibilityKeyFrames(10)); append and mark the first child, in the children slice's order
+ *     (std::set<KeyFrame*>: ascending kf_order), that is not bad and not marked; if the parent exists and is not marked append and
+ *     mark it -- its badness is NOT tested -- and END THE OUTER LOOP (the `break` at :1206 leaves the for over keyframes).
+ *     ref_kf = the vote's kf_max (mpReferenceKF; -1 leaves the previous one in place).
+ *   Points.  The local keyframes in list order, their slots in index order: a slot of -1 and a point already marked are passed over;
+ *     a point that is not bad is appended and marked; a bad point is neither.  A keyframe's own badness is not tested.
+ *   Skip.  skip = 1 for a local point that the frame holds in a slot, and for one the caller lists as also seen: the outliers that
+ *     TrackWithMotionModel / TrackReferenceKeyFrame took out of the frame after setting mnLastFrameSeen (:711, :825).  A bad point in
+ *     a frame slot reads as empty (:1041-1042, :1127-1129).
+ * Stated input domain: that of the vote, and a point occupies at most one slot of a keyframe.  Outside it memory safety and
+ * run-to-run determinism are promised and nothing else.  No input is modified.
+ * Status of a frame: OK; EMPTY -- the vote was ORBFE_COV_EMPTY: the header alone is written (ref_kf = -1); the reference returns early
+ * (:1133) and keeps the previous frame's lists, which stays the caller's; OVERFLOW -- more than kf_cap keyframes or p_cap points
+ * exist: the counts are exact, the first cap of the stated order are written and nothing behind them is touched; REFUSED -- decided
+ * by the frame's own workgroup before anything else of the frame is written, no other frame touched, counts 0, ref_kf = -1,
+ * d_n_points = 0: a vote header that is OVERFLOW or REFUSED or whose n_written lies outside 0 .. conn_cap or kf_max outside
+ * [-1, n_kf); a voted row, a best row, a child or a parent outside the table (parent: [-1, n_kf)); n_best outside 0 .. 10; a children
+ * slice, a frame's slot slice or an also-seen slice outside its array; a local keyframe with n_keys < 0 or with n_keys > 0 and a
+ * null or misaligned slot address; a slot of a local keyframe or of the frame < -1 or >= n_points; an also-seen index outside
+ * [0, n_points).
+ * Deterministic: integer LDS atomics only, whose order does not reach the result; a frame's bytes do not depend on S, on its
+ * position in the batch or on the run.  No CPU fallback.
+ * Limits, each refused with ORBFE_ERR_INVALID one step past it, before any device call (pinned by tests/test_localmap_cpu.py):
+ *   ORBFE_LM_MAX_FRAMES          65 535 frames per launch: one workgroup each, the grid limit the other batch forms use
+ *   ORBFE_LM_MAX_KEYFRAMES       = ORBFE_COV_MAX_KEYFRAMES: the same table; the marks are one bit per row in LDS (4 KiB)
+ *   ORBFE_LM_MAX_POINTS          = ORBFE_COV_MAX_POINTS: the same table; the marks are one bit per point in LDS (128 KiB of the 160)
+ *   ORBFE_LM_MAX_TOTAL_SLOTS     = ORBFE_COV_MAX_TOTAL_SLOTS: the slot array of the vote
+ *   ORBFE_LM_MAX_TOTAL_CHILDREN  = ORBFE_COV_MAX_KEYFRAMES: a spanning tree gives a row to one parent
+ *   ORBFE_LM_MAX_TOTAL_SEEN      16 777 216 also-seen indices per call (64 MiB; offsets stay far inside int32)
+ *   ORBFE_LM_MAX_KF_CAP          kf_cap 1 .. ORBFE_COV_MAX_CONN + 3: the list exceeds max(n_voted, 83) by nothing and lives in LDS (8 KiB)
+ *   ORBFE_LM_MAX_P_CAP           p_cap 1 .. ORBFE_COV_MAX_POINTS: a list holds a point once
+ *   ORBFE_LM_MAX_TOTAL_RECORDS   S x p_cap <= 4 194 304 (host form: 288 MiB of records come back in one copy)
+ *   the host form also keeps ORBFE_COV_MAX_KEYS per row and ORBFE_COV_MAX_TOTAL_KEYS over the table, whose slot arrays it stages */
+#define ORBFE_LM_MAX_FRAMES 65535
+#define ORBFE_LM_MAX_KEYFRAMES ORBFE_COV_MAX_KEYFRAMES
+#define ORBFE_LM_MAX_POINTS ORBFE_COV_MAX_POINTS
+#define ORBFE_LM_MAX_TOTAL_SLOTS ORBFE_COV_MAX_TOTAL_SLOTS
+#define ORBFE_LM_MAX_TOTAL_CHILDREN ORBFE_COV_MAX_KEYFRAMES
+#define ORBFE_LM_MAX_TOTAL_SEEN 16777216
+#define ORBFE_LM_MAX_KF_CAP (ORBFE_COV_MAX_CONN + 3)
+#define ORBFE_LM_MAX_P_CAP ORBFE_COV_MAX_POINTS
+#define ORBFE_LM_MAX_TOTAL_RECORDS 4194304
+#define ORBFE_LM_BEST 10                  /* GetBestCovisibilityKeyFrames(10), Tracking.cc:1172 */
+#define ORBFE_LM_SIZE 80                  /* `mvpLocalKeyFrames.size() > 80`, :1167 */
+enum { ORBFE_LM_OK = 0, ORBFE_LM_EMPTY = 1, ORBFE_LM_OVERFLOW = 2, ORBFE_LM_REFUSED = 3 };             /* orbfe_lm_header.status */
+enum { ORBFE_LM_STOP_EXHAUSTED = 0, ORBFE_LM_STOP_SIZE = 1, ORBFE_LM_STOP_PARENT = 2 };                /* orbfe_lm_header.stop */
+typedef struct orbfe_lm_graph {           /* one per keyframe row; 56 bytes */
+  int32_t parent;                         /* GetParent(): its row, or -1 */
+  int32_t child_offset, n_children;       /* GetChilds(): its slice of the children array, rows in ascending kf_order */
+  int32_t n_best;                         /* 0 .. 10 */
+  int32_t best[ORBFE_LM_BEST];            /* GetBestCovisibilityKeyFrames(10), in its order */
+} orbfe_lm_graph;
+typedef struct orbfe_lm_frame {           /* 8 bytes */
+  int32_t seen_offset, n_seen;            /* its slice of the also-seen array (point indices) */
+} orbfe_lm_frame;
+typedef struct orbfe_lm_header {          /* 32 bytes, always written */
+  int32_t n_voted;                        /* entries of the vote */
+  int32_t n_local_kf, n_local_points;     /* exact, even beyond kf_cap / p_cap */
+  int32_t ref_kf;                         /* the vote's kf_max */
+  int32_t stop;                           /* ORBFE_LM_STOP_*: the rule that ended the expansion */
+  int32_t status;                         /* ORBFE_LM_OK .. ORBFE_LM_REFUSED */
+  int32_t reserved[2];                    /* 0 */
+} orbfe_lm_header;
+/* S frames, DEVICE pointers (the keyframe table holds device addresses), asynchronous on `stream` (NULL: the NULL stream), one
+ * launch.  d_headers [S] / d_entries [S][conn_cap]: the vote's output.  d_subjects [S]: the frames' slices of d_slots.  d_frames
+ * [S] and d_seen: the also-seen slices; d_frames NULL: no frame has one.  Outputs: d_lm_headers [S]; d_local_kf [S][kf_cap] rows;
+ * d_local_points [S][p_cap] point indices; d_n_points [S] = min(n_local_points, p_cap); and, when d_point_records (a resident
+ * orbfe_map_point[n_points], indexed by point) is not NULL, d_map_points [S][p_cap]: each record copied from the resident one with
+ * `skip` replaced.  d_map_points, d_n_points and p_cap feed orbfe_search_local_points_batch_device unchanged.
+ * Limits (ORBFE_ERR_INVALID): the ORBFE_LM_MAX_* above, every count >= 0, 1 <= conn_cap <= ORBFE_COV_MAX_CONN, null arrays with a
+ * count > 0, d_map_points null with d_point_records, records not 4-byte (the keyframe table: 8-byte) aligned.  S == 0: nothing is
+ * launched. */
+int orbfe_local_map_batch_device(int S, const orbfe_cov_header* d_headers, const orbfe_cov_entry* d_entries, int conn_cap,
+                                 const orbfe_lm_graph* d_graph, const int32_t* d_children, int n_children_total,
+                                 const orbfe_cov_keyframe* d_keyframes, const uint8_t* d_kf_bad, int n_kf, const uint8_t* d_point_bad,
+                                 int n_points, const int32_t* d_slots, int n_slots_total, const orbfe_cov_subject* d_subjects,
+                                 const orbfe_lm_frame* d_frames, const int32_t* d_seen, int n_seen_total,
+                                 const orbfe_map_point* d_point_records, int kf_cap, int p_cap, orbfe_lm_header* d_lm_headers,
+                                 int32_t* d_local_kf, int32_t* d_local_points, int32_t* d_n_points, orbfe_map_point* d_map_points,
+                                 void* stream);
+/* The same from HOST arrays (the table's `slots` are host addresses and are staged with it), synchronous, on the calling thread's
+ * current device: one upload, one launch, one download.  Of each frame the header, n_points and the written head of each list come
+ * back; what lies behind stays the caller's.  Limits: as above, and the host-form limits of the list. */
+int orbfe_local_map(const orbfe_cov_header* headers, const orbfe_cov_entry* entries, int conn_cap, const orbfe_lm_graph* graph,
+                    const int32_t* children, int n_children_total, const orbfe_cov_keyframe* keyframes, const uint8_t* kf_bad, int n_kf,
+                    const uint8_t* point_bad, int n_points, const int32_t* slots, int n_slots_total, const orbfe_cov_subject* subjects,
+                    const orbfe_lm_frame* frames, const int32_t* seen, int n_seen_total, const orbfe_map_point* point_records, int S,
+                    int kf_cap, int p_cap, orbfe_lm_header* lm_headers, int32_t* local_kf, int32_t* local_points, int32_t* n_points_out,
+                    orbfe_map_point* map_points);
 
 /* SearchForInitialization (L/src/ORBmatcher.cc:388-492), the monocular map-initialisation matcher: level-0
  * keypoints of F1 are searched in a window of `window_size` pixels around prev_matched_xy[2*i..2*i+1] in F2; a

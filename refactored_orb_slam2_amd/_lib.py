@@ -243,6 +243,17 @@ COV_CONNECTIONS, COV_VOTES = 0, 1
 COV_OK, COV_EMPTY, COV_OVERFLOW, COV_REFUSED = 0, 1, 2, 3
 COV_KEPT, COV_CULLED, COV_MARKED, COV_SKIPPED_ID0, COV_ROW_REFUSED = 0, 1, 2, 3, 4
 COV_IS_ID0, COV_NOT_ERASE = 1, 2
+# orbfe_lm_graph / orbfe_lm_frame / orbfe_lm_header and the ORBFE_LM_* constants (include/orbfe.h)
+LM_GRAPH_DTYPE = np.dtype([("parent", "<i4"), ("child_offset", "<i4"), ("n_children", "<i4"), ("n_best", "<i4"), ("best", "<i4", (10,))])
+LM_FRAME_DTYPE = np.dtype([("seen_offset", "<i4"), ("n_seen", "<i4")])
+LM_HEADER_DTYPE = np.dtype([("n_voted", "<i4"), ("n_local_kf", "<i4"), ("n_local_points", "<i4"), ("ref_kf", "<i4"), ("stop", "<i4"),
+                            ("status", "<i4"), ("reserved", "<i4", (2,))])
+assert LM_GRAPH_DTYPE.itemsize == 56 and LM_FRAME_DTYPE.itemsize == 8 and LM_HEADER_DTYPE.itemsize == 32
+(LM_MAX_FRAMES, LM_MAX_KEYFRAMES, LM_MAX_POINTS, LM_MAX_TOTAL_SLOTS, LM_MAX_TOTAL_CHILDREN, LM_MAX_TOTAL_SEEN, LM_MAX_KF_CAP, LM_MAX_P_CAP,
+ LM_MAX_TOTAL_RECORDS) = 65535, 32768, 1048576, 16777216, 32768, 16777216, 2051, 1048576, 4194304
+LM_BEST, LM_SIZE = 10, 80
+LM_OK, LM_EMPTY, LM_OVERFLOW, LM_REFUSED = 0, 1, 2, 3
+LM_STOP_EXHAUSTED, LM_STOP_SIZE, LM_STOP_PARENT = 0, 1, 2
 # orbfe_eg_sim3 / orbfe_eg_vertex / orbfe_eg_edge / orbfe_eg_problem / orbfe_eg_result and the ORBFE_EG_* limits
 # (Optimizer::OptimizeEssentialGraph and the map correction behind it, include/orbfe.h)
 EG_SIM3_DTYPE = np.dtype([("q", "<f8", (4,)), ("t", "<f8", (3,)), ("s", "<f8")])
@@ -314,6 +325,7 @@ EXPORTS = [
     "orbfe_kfdb_detect_relocalization_device", "orbfe_kfdb_detect_loop_device", "orbfe_debug_kfdb_arrangement",
     "orbfe_refresh_map_points", "orbfe_refresh_map_points_batch_device",
     "orbfe_covis_count", "orbfe_covis_count_batch_device", "orbfe_covis_cull_keyframes", "orbfe_covis_cull_keyframes_batch_device",
+    "orbfe_local_map", "orbfe_local_map_batch_device",
     "orbfe_initializer_initialize", "orbfe_initializer_workspace_bytes", "orbfe_initializer_initialize_batch_device",
     "orbfe_create_initial_map", "orbfe_initial_map_workspace_bytes", "orbfe_create_initial_map_batch_device",
     "orbfe_essential_graph_envelope_blocks", "orbfe_essential_graph", "orbfe_essential_graph_workspace_bytes",
@@ -478,6 +490,9 @@ def lib():
     L.orbfe_covis_count_batch_device.argtypes = [ci, vp, ci, vp, vp, ci, vp, vp, ci, vp, ci, vp, ci, vp, vp, vp]
     L.orbfe_covis_cull_keyframes.argtypes = [vp, ci, vp, vp, vp, ci, vp, ci, vp, ci, vp, ci, vp]
     L.orbfe_covis_cull_keyframes_batch_device.argtypes = [ci, vp, ci, vp, vp, vp, ci, vp, ci, vp, ci, vp, vp, vp]
+    L.orbfe_local_map_batch_device.argtypes = [ci, vp, vp, ci, vp, vp, ci, vp, vp, ci, vp, ci, vp, ci, vp, vp, vp, ci, vp, ci, ci, vp, vp, vp, vp,
+                                               vp, vp]
+    L.orbfe_local_map.argtypes = [vp, vp, ci, vp, vp, ci, vp, vp, ci, vp, ci, vp, ci, vp, vp, vp, ci, vp, ci, ci, ci, vp, vp, vp, vp, vp]
     L.orbfe_initializer_initialize.argtypes = [vp, vp, ci, vp, ci, vp, vp, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.orbfe_initializer_workspace_bytes.argtypes = [ci, ci, C.POINTER(sz)]
     L.orbfe_initializer_initialize_batch_device.argtypes = [ci, vp, vp, vp, vp, vp, ci, vp, vp, vp, ci, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]
