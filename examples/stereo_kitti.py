@@ -21,6 +21,10 @@ optimisation, local mapping and loop closing are out of scope.
                         relative motions on the host and write the camera trajectory as System::SaveTrajectoryKITTI does
                         (L/src/System.cc:452-505): one line of 12 numbers per frame, the rows of Twc.  A frame with fewer than 10
                         inliers keeps the identity motion and is counted.  Stereo visual odometry, no map: not with --shard.
+  --close-points        the points a frame hands to the next one are the temporal points of Tracking::UpdateLastFrame
+                        (L/src/Tracking.cc:732-777) instead of every keypoint with depth: those closer than mThDepth = bf * ThDepth / fx,
+                        or the 100 closest plus one (tracking.keyframe_insertion_device, whose depth_selected replaces the depth
+                        array).  --th-depth is ThDepth of the settings file (35 for KITTI 00-02).  Off by default.
 
 usage: stereo_kitti.py <sequence_dir> [--features 2000] [--batch 64] [--max-frames N] [--bf 386.1448 --fx 718.856 ...]
 """
@@ -75,6 +79,8 @@ def main():
     ap.add_argument("--shard", action="store_true")
     ap.add_argument("--dump", default="")
     ap.add_argument("--trajectory", default="")
+    ap.add_argument("--close-points", action="store_true")
+    ap.add_argument("--th-depth", type=float, default=35.0)  # ThDepth of the settings file: mThDepth = bf * ThDepth / fx (L/src/Tracking.cc:125-129)
     args = ap.parse_args()
     if args.trajectory and args.shard:
         ap.error("--trajectory composes every frame's motion with its predecessor's pose: a rank's first frame has no predecessor "
@@ -128,6 +134,11 @@ def main():
     t_cams = torch.from_numpy(cams.view(np.uint8).reshape(F, -1)).to(dev)
     t_poses = torch.from_numpy(poses.view(np.uint8).reshape(F, -1)).to(dev)
     stream = torch.cuda.Stream(dev)
+    if args.close_points:
+        from refactored_orb_slam2_amd import tracking
+        kf_scales = tracking.pack_scales(sf, np.float32(args.bf) * np.float32(args.th_depth) / np.float32(args.fx))
+        kf_head, kf_new, kf_idx, kf_n = z(F, 64), z(F, cap, 72), z(F, cap, dt=torch.int32), z(F, dt=torch.int32)
+        depth_sel = z(F, cap, dt=torch.float32)
     if args.trajectory:
         from refactored_orb_slam2_amd import optimizer
         from refactored_orb_slam2_amd._lib import POSE_RESULT_DTYPE
@@ -156,7 +167,14 @@ def main():
                 mt.stereo_match(exL, exR, kl[:B], dl[:B], nl[:B], kr[:B], dr[:B], nr[:B], args.bf, args.bf / args.fx, ur[:B], depth[:B],
                                 nst[:B], stream=stream)
                 # the stereo points of every frame of the batch (slot j + 1), then frame j is searched with the points of slot j
-                unproject_stereo_batch(kl[:B], dl[:B], nl[:B], depth[:B], t_cams[:B], 1, pts[1:B + 1], stream)
+                src_depth = depth
+                if args.close_points:   # the temporal-point rule of Tracking::UpdateLastFrame: the close points, or the 100 closest
+                    tracking.keyframe_insertion_device(kf_scales, tracking.KF_CREATE, tracking.KF_MODE_LAST_FRAME, S=B, cap=cap, new_cap=cap,
+                                                       depth=depth[:B], n=nl[:B], headers=kf_head[:B], keys_un=kl[:B], desc=dl[:B],
+                                                       cam=t_cams[:B], new_points=kf_new[:B], new_index=kf_idx[:B], n_new=kf_n[:B],
+                                                       depth_selected=depth_sel[:B], stream=stream)
+                    src_depth = depth_sel
+                unproject_stereo_batch(kl[:B], dl[:B], nl[:B], src_depth[:B], t_cams[:B], 1, pts[1:B + 1], stream)
                 npts[1:B + 1].copy_(nl[:B])
                 track_queries_batch(t_poses[:B], pts[:B], npts[:B], 0, q[:B], nq[:B], stream)
                 blocked[:B].zero_(); assigned[:B].fill_(-1)

@@ -1745,6 +1745,152 @@ int orbfe_local_map(const orbfe_cov_header* headers, const orbfe_cov_entry* entr
                     int kf_cap, int p_cap, orbfe_lm_header* lm_headers, int32_t* local_kf, int32_t* local_points, int32_t* n_points_out,
                     orbfe_map_point* map_points);
 
+/* ---- Keyframe decision and close stereo points: the statistics tail of Tracking::TrackLocalMap (L/src/Tracking.cc:851-877),
+ * Tracking::NeedNewKeyFrame (:880-962), the depth-ordered point creation of Tracking::CreateNewKeyFrame (:973-1024), the temporal
+ * points of Tracking::UpdateLastFrame (:732-777) and the points of Tracking::StereoInitialization (:455-479) ------------------------------
+ * One frame is one workgroup; csrc/keyframe_internal.h states every rule once, for the kernel and for host code.  The arrays are
+ * those of orbfe_pose_optimization_batch_device, so a frame goes from orbfe_local_map_batch_device over
+ * orbfe_search_local_points_batch_device and orbfe_pose_optimization_batch_device to this call on one stream, and its new points are
+ * orbfe_map_point records that the search, fuse and refresh stages take unchanged.  Which parts run is `flags`:
+ *   ORBFE_KF_STATISTICS   n_matches_inliers = the slots i < n that are occupied (assigned[i] >= 0) and not outlier and, when
+ *     only_tracking == 0, hold an observed point (:854-866); track_ok = !(recent && n_matches_inliers < 50) && n_matches_inliers >= 30
+ *     with recent = frame_id < last_reloc_frame_id + max_frames (:870-877).  IncreaseFound and the stereo sensor's clearing of outlier
+ *     slots (:857, :863-864) stay with the caller: ORBFE_POSE_DISCARD of the pose stage does the latter, and it has to be done
+ *     before this call where the creation is to see those slots empty.
+ *   ORBFE_KF_DECISION     (requires STATISTICS, whose count it reads) n_tracked_close / n_non_tracked_close over the keypoints with
+ *     depth > 0 && depth < th_depth -- strict, an entry exactly at th_depth is in neither -- tracked = occupied and not outlier, both 0
+ *     for a monocular sensor (:906-917); n_ref_matches = KeyFrame::TrackedMapPoints(n_kfs <= 2 ? 2 : 3) of table row ref_kf (0 for
+ *     ref_kf == -1): its slots p >= 0 with !point_bad[p] && point_observations[p] >= nMinObs (L/src/KeyFrame.cc:237-256); then
+ *     :881-961 with every comparison in the source's types: the frame id unsigned 64-bit against a 32-bit unsigned sum that wraps,
+ *     `n_matches_inliers < n_ref_matches * 0.25` in double, `n_matches_inliers < n_ref_matches * thRefRatio` in float.  early: the
+ *     return before the conditions that was taken (ORBFE_KF_EARLY_*: only_tracking :881, mapper stopped :885, recent relocalisation
+ *     with n_kfs > max_frames :892); the counts are written all the same.  conditions: c1a | c1b << 1 | c1c << 2 | c2 << 3;
+ *     need: the return value; interrupt_ba: :951 was reached -- InterruptBA() and SetNotStop stay with the caller.
+ *   ORBFE_KF_CREATE       the selection and the new points, by `mode`.  With DECISION it runs only for frames whose need is 1; the
+ *     others get M = c = L = n_created = n_cleared = 0, d_n_new = 0 and d_depth_selected = -1.
+ *     The sensor is not asked (:973, :728): a monocular frame has no positive depth, and a caller whose arrays hold some tests it.
+ * Selection (:979-1022, identical at :734-777).  Candidates: i < n with depth[i] > 0 (NaN and non-positive out, +inf in), M of them,
+ * ordered as std::sort orders pair<float, int>: ascending depth, ties by ascending index -- for positive floats the ascending order of
+ * the 64-bit key (bits(depth) << 32) | i, which has no equal keys.  The loop counts nPoints in both branches and breaks after an entry
+ * with depth > th_depth && nPoints > 100, so the selected prefix has L = min(M, max(100, c) + 1) entries, c = the candidates with
+ * depth <= th_depth (note <=: an entry exactly at th_depth does not stop the loop).  An entry of the prefix is CREATED when its slot is
+ * empty or holds a point that is not observed (a temporal point; ORBFE_KF_MODE_KEYFRAME clears that slot first and counts it in
+ * n_cleared, :1002; ORBFE_KF_MODE_LAST_FRAME does not); an entry whose slot holds an observed point is kept: nothing is written for it,
+ * but it counts.  ORBFE_KF_MODE_STEREO_INIT (:455-479): only when n > 500, every candidate in INDEX order, whatever its slot holds; no
+ * sort, L = M, c as above.
+ * New point records, in creation order (the order of mnId, of mlpTemporalPoints and of Map::AddMapPoint): d_new_points [S][new_cap],
+ * d_new_index [S][new_cap] the keypoint index of each, d_n_new [S] = min(n_created, new_cap).  pos = Frame::UnprojectStereo(i)
+ * (L/src/Frame.cc:668-679) in the arithmetic of orbfe_unproject_stereo_device, byte-equal to its row i.  KEYFRAME and STEREO_INIT
+ * (MapPoint(x3D, pKF, pMap), AddObservation, ComputeDistinctiveDescriptors, UpdateNormalAndDepth): one observation, so desc = row i,
+ * normal = (0.0f + unit) * (float)(1.0 / 1), max_distance = dist * scale_factors[octave], min_distance = max_distance /
+ * scale_factors[n_levels - 1] -- byte-equal to orbfe_refresh_map_points of the same one-observation point; observed = 1.  LAST_FRAME
+ * (MapPoint(x3D, pMap, &mLastFrame, i), L/src/MapPoint.cc:49-77): the same expressions without the sum and the division by the count,
+ * which changes one thing: a normal component of -0.0f stays -0.0f here and is +0.0f in the keyframe form; observed = 0.  skip = 0.
+ * d_depth_selected [S][cap] (nullable): depth[i] for every entry of the prefix, created or kept, -1 elsewhere (rows at and behind n
+ * included); orbfe_track_queries_stereo_device takes it in place of d_depth and so gets the reference's point set.
+ * d_assigned (nullable: every slot is empty) is written in KEYFRAME and STEREO_INIT mode only: a cleared slot becomes -1, a created
+ * slot whose record was written becomes d_n_points_base[f] (NULL: 0) + its position in the created list.  No other input is modified.
+ * Arrays: frame f owns rows [f * cap, f * cap + d_n[f]) of d_keys_un / d_desc / d_depth / d_assigned / d_outlier (nullable: no
+ * outliers); d_n[f] is clamped to [0, cap].  Assigned values index the records of frame (f - frame_shift) mod S at d_points + that
+ * frame * p_cap * point_stride, of which d_n_points[that frame] (clamped to [0, p_cap]) exist; observed_offset is the byte offset of
+ * the record's int32 `observed` field (orbfe_map_point: 36, orbfe_last_point: 16), -1: every occupied slot counts as observed.
+ * d_ref_kf: an int32 per frame, ref_kf_stride bytes apart (the ref_kf field of an orbfe_lm_header array: the address of the first
+ * one and 32).  Of the orbfe_cov_keyframe table `slots` and `n_keys` are read, of rows some frame names.
+ * Status of a frame: OK; OVERFLOW -- more than new_cap created: the counts are exact, the first new_cap records are written and
+ * nothing behind them is touched; REFUSED -- decided before anything else of the frame is written, every count 0, d_n_new = 0: an
+ * assigned value >= the record count; an octave outside [0, n_levels) on a created entry; ref_kf outside [-1, n_kf); a reference row
+ * with n_keys < 0, or n_keys > 0 and a null or misaligned slot address, or a slot < -1 or >= n_map_points.
+ * Deterministic: ballots and integer sums only; a frame's bytes do not depend on S, on its position in the batch or on the run.
+ * No CPU fallback.  Limits, each refused with ORBFE_ERR_INVALID one step past it, before any device call (tests/test_keyframe_cpu.py):
+ *   ORBFE_KF_MAX_FRAMES   65 535 frames per launch: one workgroup each, the grid limit the other batch forms use
+ *   ORBFE_KF_MAX_CAP      1 <= cap <= 9 500: the frame limit of the projection searches and the pose stage; the keys of a frame, 8
+ *                         bytes each, are sorted in LDS (padded to a power of two: 16 384 keys, 128 KiB of the 160)
+ *   1 <= new_cap <= cap; p_cap >= 1; frame_shift >= 0; point_stride >= 12 and a multiple of 4; observed_offset -1, or a multiple of 4
+ *   in [0, point_stride - 4]; ref_kf_stride >= 4 and a multiple of 4; n_kf 0 .. ORBFE_COV_MAX_KEYFRAMES; n_map_points 0 ..
+ *   ORBFE_COV_MAX_POINTS; n_levels 1 .. ORBFE_MAX_LEVELS; mode 0 .. 2; flags a non-empty subset of the three, DECISION only with
+ *   STATISTICS; null arrays that the flags need with S > 0 (the tables with a count > 0); records not 4-byte (the decision records and
+ *   the keyframe table: 8-byte) aligned.  S == 0: nothing is launched and nothing behind a pointer is read. */
+#define ORBFE_KF_MAX_FRAMES 65535
+#define ORBFE_KF_MAX_CAP 9500
+#define ORBFE_KF_MAX_TOTAL_ROWS 4194304   /* host form: S x cap keypoint rows (272 MiB staged), S x p_cap point records */
+#define ORBFE_KF_STATISTICS 1
+#define ORBFE_KF_DECISION 2
+#define ORBFE_KF_CREATE 4
+enum { ORBFE_KF_MODE_KEYFRAME = 0, ORBFE_KF_MODE_LAST_FRAME = 1, ORBFE_KF_MODE_STEREO_INIT = 2 };
+enum { ORBFE_KF_SENSOR_MONOCULAR = 0, ORBFE_KF_SENSOR_STEREO = 1, ORBFE_KF_SENSOR_RGBD = 2 };          /* System::eSensor */
+enum { ORBFE_KF_OK = 0, ORBFE_KF_OVERFLOW = 2, ORBFE_KF_REFUSED = 3 };                                 /* orbfe_kf_header.status */
+enum { ORBFE_KF_EARLY_NONE = 0, ORBFE_KF_EARLY_ONLY_TRACKING = 1, ORBFE_KF_EARLY_STOPPED = 2, ORBFE_KF_EARLY_RELOCALISED = 3 };
+#define ORBFE_KF_C1A 1
+#define ORBFE_KF_C1B 2
+#define ORBFE_KF_C1C 4
+#define ORBFE_KF_C2 8
+#define ORBFE_KF_CLOSE_POINTS 100         /* `nPoints > 100`, :1020 and :775; `nTrackedClose < 100`, :919 */
+#define ORBFE_KF_INIT_MIN_KEYS 500        /* `mCurrentFrame.N > 500`, :455 */
+typedef struct orbfe_kf_decision_in {     /* what :851-961 read beside the frame; 56 bytes, 8-byte aligned */
+  uint64_t frame_id;                      /* mCurrentFrame.mnId (long unsigned int) */
+  uint32_t last_reloc_frame_id;           /* mnLastRelocFrameId (unsigned int) */
+  uint32_t last_keyframe_id;              /* mnLastKeyFrameId (unsigned int) */
+  int32_t max_frames, min_frames;         /* mMaxFrames, mMinFrames */
+  int32_t sensor;                         /* ORBFE_KF_SENSOR_* */
+  int32_t only_tracking;                  /* mbOnlyTracking */
+  int32_t mapper_stopped;                 /* mpLocalMapper->isStopped() || mpLocalMapper->stopRequested() */
+  int32_t accept_keyframes;               /* mpLocalMapper->AcceptKeyFrames() */
+  int32_t keyframes_in_queue;             /* mpLocalMapper->KeyframesInQueue() */
+  int32_t n_kfs;                          /* mpMap->KeyFramesInMap() */
+  int32_t reserved[2];
+} orbfe_kf_decision_in;
+typedef struct orbfe_kf_scales {          /* 72 bytes; read on the host before the call returns */
+  int32_t n_levels;                       /* mnScaleLevels, 1 .. ORBFE_MAX_LEVELS */
+  float th_depth;                         /* mThDepth */
+  float scale_factors[ORBFE_MAX_LEVELS];  /* mvScaleFactors */
+} orbfe_kf_scales;
+typedef struct orbfe_kf_header {          /* 64 bytes, always written */
+  int32_t n_matches_inliers;              /* mnMatchesInliers */
+  int32_t track_ok;                       /* the return value of TrackLocalMap */
+  int32_t n_tracked_close, n_non_tracked_close, n_ref_matches;
+  int32_t early;                          /* ORBFE_KF_EARLY_* */
+  int32_t conditions;                     /* ORBFE_KF_C1A | C1B | C1C | C2 */
+  int32_t need;                           /* the return value of NeedNewKeyFrame */
+  int32_t interrupt_ba;                   /* :951 was reached */
+  int32_t M, c, L;                        /* candidates, those with depth <= th_depth, length of the selected prefix */
+  int32_t n_created, n_cleared;           /* exact, even beyond new_cap */
+  int32_t status;                         /* ORBFE_KF_OK .. ORBFE_KF_REFUSED */
+  int32_t reserved;                       /* 0 */
+} orbfe_kf_header;
+typedef struct orbfe_kf_call {            /* the arrays and counts of one call; 8-byte aligned */
+  const orbfe_keypoint* keys_un;          /* [S][cap] mvKeysUn (x, y, octave are read) */
+  const uint8_t* desc;                    /* [S][cap][32] mDescriptors */
+  const float* depth;                     /* [S][cap] mvDepth */
+  const int32_t* n;                       /* [S] N */
+  const orbfe_unproject_cam* cam;         /* [S] */
+  int32_t* assigned;                      /* [S][cap] in/out, nullable */
+  const void* points;                     /* the records the assigned values index */
+  const int32_t* n_points;                /* [S] */
+  const uint8_t* outlier;                 /* [S][cap] mvbOutlier, nullable */
+  const orbfe_kf_decision_in* decision;   /* [S]; STATISTICS and DECISION */
+  const void* ref_kf;                     /* DECISION: see above */
+  const orbfe_cov_keyframe* keyframes;    /* [n_kf]; DECISION */
+  const uint8_t* point_bad;               /* [n_map_points] MapPoint::isBad(); DECISION */
+  const int32_t* point_observations;      /* [n_map_points] MapPoint::Observations(): nObs, a stereo observation counts 2; DECISION */
+  const int32_t* n_points_base;           /* [S], nullable; CREATE */
+  orbfe_kf_header* headers;               /* [S] out */
+  orbfe_map_point* new_points;            /* [S][new_cap] out; CREATE */
+  int32_t* new_index;                     /* [S][new_cap] out; CREATE */
+  int32_t* n_new;                         /* [S] out; CREATE */
+  float* depth_selected;                  /* [S][cap] out, nullable; CREATE */
+  int32_t S, cap, new_cap, p_cap, frame_shift, point_stride, observed_offset, ref_kf_stride, n_kf, n_map_points, mode, flags;
+} orbfe_kf_call;
+/* S frames in one launch.  Every pointer of `call` is a DEVICE pointer (the keyframe table holds device addresses); `call` and
+ * `camera` themselves are HOST records, read before the call returns.  Asynchronous on `stream` (NULL: the NULL stream). */
+int orbfe_keyframe_insertion_batch_device(const orbfe_kf_call* call, const orbfe_kf_scales* camera, void* stream);
+/* The same from HOST arrays (the table's `slots` are host addresses; the slot arrays of the rows some frame names are staged with
+ * it), synchronous, on the calling thread's current device: one upload, one launch, one download.  Of each frame the header, n_new,
+ * the written head of the two lists, its row of depth_selected and (KEYFRAME and STEREO_INIT mode) its rows of assigned come back;
+ * a REFUSED frame brings back its header and n_new alone.  Host-form limits (ORBFE_ERR_INVALID): S x cap and, with assigned, S x p_cap
+ * at most ORBFE_KF_MAX_TOTAL_ROWS; a named reference row with n_keys > ORBFE_COV_MAX_KEYS; the named rows' n_keys summing to more than
+ * ORBFE_COV_MAX_TOTAL_KEYS.  ref_kf is read on the host to find those rows; a value outside [-1, n_kf) is refused by the device. */
+int orbfe_keyframe_insertion(const orbfe_kf_call* call, const orbfe_kf_scales* camera);
+
 /* SearchForInitialization (L/src/ORBmatcher.cc:388-492), the monocular map-initialisation matcher: level-0
  * keypoints of F1 are searched in a window of `window_size` pixels around prev_matched_xy[2*i..2*i+1] in F2; a
  * closer later keypoint steals an earlier match (vMatchedDistance / vnMatches21).  matches12[i] = F2 index or -1;

@@ -254,6 +254,37 @@ assert LM_GRAPH_DTYPE.itemsize == 56 and LM_FRAME_DTYPE.itemsize == 8 and LM_HEA
 LM_BEST, LM_SIZE = 10, 80
 LM_OK, LM_EMPTY, LM_OVERFLOW, LM_REFUSED = 0, 1, 2, 3
 LM_STOP_EXHAUSTED, LM_STOP_SIZE, LM_STOP_PARENT = 0, 1, 2
+# orbfe_kf_decision_in / orbfe_kf_scales / orbfe_kf_header / orbfe_kf_call and the ORBFE_KF_* constants of the keyframe decision and the
+# close stereo points (Tracking::NeedNewKeyFrame, CreateNewKeyFrame, UpdateLastFrame, StereoInitialization, include/orbfe.h)
+KF_DECISION_DTYPE = np.dtype([("frame_id", "<u8"), ("last_reloc_frame_id", "<u4"), ("last_keyframe_id", "<u4"), ("max_frames", "<i4"),
+                              ("min_frames", "<i4"), ("sensor", "<i4"), ("only_tracking", "<i4"), ("mapper_stopped", "<i4"),
+                              ("accept_keyframes", "<i4"), ("keyframes_in_queue", "<i4"), ("n_kfs", "<i4"), ("reserved", "<i4", (2,))])
+KF_SCALES_DTYPE = np.dtype([("n_levels", "<i4"), ("th_depth", "<f4"), ("scale_factors", "<f4", (16,))])
+KF_HEADER_DTYPE = np.dtype([("n_matches_inliers", "<i4"), ("track_ok", "<i4"), ("n_tracked_close", "<i4"), ("n_non_tracked_close", "<i4"),
+                            ("n_ref_matches", "<i4"), ("early", "<i4"), ("conditions", "<i4"), ("need", "<i4"), ("interrupt_ba", "<i4"),
+                            ("M", "<i4"), ("c", "<i4"), ("L", "<i4"), ("n_created", "<i4"), ("n_cleared", "<i4"), ("status", "<i4"),
+                            ("reserved", "<i4")])
+assert KF_DECISION_DTYPE.itemsize == 56 and KF_SCALES_DTYPE.itemsize == 72 and KF_HEADER_DTYPE.itemsize == 64
+KF_MAX_FRAMES, KF_MAX_CAP, KF_MAX_TOTAL_ROWS = 65535, 9500, 4194304
+KF_STATISTICS, KF_DECISION, KF_CREATE = 1, 2, 4
+KF_MODE_KEYFRAME, KF_MODE_LAST_FRAME, KF_MODE_STEREO_INIT = 0, 1, 2
+KF_SENSOR_MONOCULAR, KF_SENSOR_STEREO, KF_SENSOR_RGBD = 0, 1, 2
+KF_OK, KF_OVERFLOW, KF_REFUSED = 0, 2, 3
+KF_EARLY_NONE, KF_EARLY_ONLY_TRACKING, KF_EARLY_STOPPED, KF_EARLY_RELOCALISED = 0, 1, 2, 3
+KF_C1A, KF_C1B, KF_C1C, KF_C2 = 1, 2, 4, 8
+KF_CLOSE_POINTS, KF_INIT_MIN_KEYS = 100, 500
+KF_CALL_POINTERS = ("keys_un", "desc", "depth", "n", "cam", "assigned", "points", "n_points", "outlier", "decision", "ref_kf", "keyframes",
+                    "point_bad", "point_observations", "n_points_base", "headers", "new_points", "new_index", "n_new", "depth_selected")
+KF_CALL_COUNTS = ("S", "cap", "new_cap", "p_cap", "frame_shift", "point_stride", "observed_offset", "ref_kf_stride", "n_kf", "n_map_points",
+                  "mode", "flags")
+
+
+class KfCall(C.Structure):
+    """orbfe_kf_call (include/orbfe.h): the arrays and counts of one orbfe_keyframe_insertion* call; 208 bytes"""
+    _fields_ = [(k, C.c_void_p) for k in KF_CALL_POINTERS] + [(k, C.c_int32) for k in KF_CALL_COUNTS]
+
+
+assert C.sizeof(KfCall) == 208
 # orbfe_eg_sim3 / orbfe_eg_vertex / orbfe_eg_edge / orbfe_eg_problem / orbfe_eg_result and the ORBFE_EG_* limits
 # (Optimizer::OptimizeEssentialGraph and the map correction behind it, include/orbfe.h)
 EG_SIM3_DTYPE = np.dtype([("q", "<f8", (4,)), ("t", "<f8", (3,)), ("s", "<f8")])
@@ -326,6 +357,7 @@ EXPORTS = [
     "orbfe_refresh_map_points", "orbfe_refresh_map_points_batch_device",
     "orbfe_covis_count", "orbfe_covis_count_batch_device", "orbfe_covis_cull_keyframes", "orbfe_covis_cull_keyframes_batch_device",
     "orbfe_local_map", "orbfe_local_map_batch_device",
+    "orbfe_keyframe_insertion", "orbfe_keyframe_insertion_batch_device",
     "orbfe_initializer_initialize", "orbfe_initializer_workspace_bytes", "orbfe_initializer_initialize_batch_device",
     "orbfe_create_initial_map", "orbfe_initial_map_workspace_bytes", "orbfe_create_initial_map_batch_device",
     "orbfe_essential_graph_envelope_blocks", "orbfe_essential_graph", "orbfe_essential_graph_workspace_bytes",
@@ -493,6 +525,8 @@ def lib():
     L.orbfe_local_map_batch_device.argtypes = [ci, vp, vp, ci, vp, vp, ci, vp, vp, ci, vp, ci, vp, ci, vp, vp, vp, ci, vp, ci, ci, vp, vp, vp, vp,
                                                vp, vp]
     L.orbfe_local_map.argtypes = [vp, vp, ci, vp, vp, ci, vp, vp, ci, vp, ci, vp, ci, vp, vp, vp, ci, vp, ci, ci, ci, vp, vp, vp, vp, vp]
+    L.orbfe_keyframe_insertion_batch_device.argtypes = [C.POINTER(KfCall), vp, vp]
+    L.orbfe_keyframe_insertion.argtypes = [C.POINTER(KfCall), vp]
     L.orbfe_initializer_initialize.argtypes = [vp, vp, ci, vp, ci, vp, vp, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.orbfe_initializer_workspace_bytes.argtypes = [ci, ci, C.POINTER(sz)]
     L.orbfe_initializer_initialize_batch_device.argtypes = [ci, vp, vp, vp, vp, vp, ci, vp, vp, vp, ci, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]
