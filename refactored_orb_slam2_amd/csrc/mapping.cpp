@@ -1,5 +1,5 @@
 // mapping.cpp -- C ABI of LocalMapping::CreateNewMapPoints (include/orbfe.h: orbfe_triangulate_matches*, orbfe_create_new_map_points).
-// The entry points validate, stage and launch mapping_kernels.hip (and, for the chain, the search of match_kernels.hip through the
+// The entry points validate, stage and launch mapping_kernels.hip (and, for the chain, the search of bow_kernels.hip through the
 // helpers orbfe_search_for_triangulation itself uses).  No CPU fallback: without a device all three are an error.
 #include <string.h>
 
@@ -10,7 +10,7 @@
 #include "mapping_internal.h"
 #include "match_internal.h"
 
-#define TRI_MAX_ROWS 65535   // the descriptor limit of SearchForTriangulation (match_kernels.hip packs a position into 16 bits)
+#define TRI_MAX_ROWS 65535   // the descriptor limit of SearchForTriangulation (triangulation_match, bow_kernels.hip, packs a position into 16 bits)
 
 static bool view_ok(const orbfe_tri_view* v, const char* what) {
   if (v->n_levels < 1 || v->n_levels > ORBFE_MAX_LEVELS) {

@@ -1,10 +1,23 @@
-// match_internal.h -- structs shared by matcher.cpp and match_kernels.hip
+// match_internal.h -- structs and launchers shared by matcher.cpp, mapping.cpp and the kernel units hamming_, grid_, projection_, bow_, stereo_, frustum_ and fuse_kernels.hip
 #pragma once
+#include <atomic>
 #include <vector>
 
 #include "orbfe_internal.h"
 
 #define GRID_CELLS (ORBFE_GRID_COLS * ORBFE_GRID_ROWS)
+
+// hipFuncSetAttribute applies to the device that is current when it is called: a process with matchers on several devices
+// (orbfe_matcher_create takes a device) must raise a kernel's dynamic-LDS limit once on EACH of them.  One bit per device
+// ordinal, in a flag that each launcher keeps for its kernel; two threads racing on the same device both set the same value.
+inline void raise_dynamic_lds(const void* kernel, int bytes, std::atomic<unsigned long long>& done) {
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) dev = 0;
+  const unsigned long long bit = 1ull << (dev & 63);
+  if (done.load(std::memory_order_acquire) & bit) return;
+  (void)hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+  done.fetch_or(bit, std::memory_order_release);
+}
 
 // A batch of frames with identical capacity: frame f uses rows [f*cap, f*cap + n[f])
 struct FrameBatch {

@@ -1,5 +1,5 @@
 // matcher.cpp -- host side of liborbfe's ORBmatcher path: work-space handle, kernel sequencing, C ABI.
-// No CPU fallback: everything that computes runs in match_kernels.hip.
+// No CPU fallback: everything that computes runs in the kernel units hamming_, grid_, projection_, bow_ and stereo_kernels.hip.
 //
 // Reference behaviour (L/ = Source/Libraries/ORB_SLAM2/):
 //   DescriptorDistance                         L/src/ORBmatcher.cc:1542-1556

@@ -1,6 +1,9 @@
-// search_device.h -- device code that more than one kernel unit of the projection searches states: the library is built with
-// -fno-gpu-rdc, so what two units share lives here, once.
-//   wave helpers, hamming256, enumerate_window   match_kernels.hip (proj_best, proj_resolve), fuse_kernels.hip
+// search_device.h -- device code that more than one kernel unit of the searches states: the library is built with -fno-gpu-rdc, so
+// what two units share lives here, once.
+//   wave helpers, hamming256, load_desc           hamming_, grid_, projection_, bow_, stereo_kernels.hip, fuse_kernels.hip
+//   cell_rec_pack / cell_rec_unpack               grid_kernels.hip writes the records; enumerate_window and proj_candidates read them
+//   enumerate_window                              projection_kernels.hip (proj_best, proj_resolve, init_resolve), fuse_kernels.hip
+//   rot_bin, three_maxima                         projection_kernels.hip, bow_kernels.hip
 //   predict_scale, kf_project                     frustum_kernels.hip (frustum / kf queries), fuse_kernels.hip
 // Compiled with -ffp-contract=off: every float expression is evaluated un-fused, as the reference does.
 #pragma once
@@ -47,6 +50,39 @@ __device__ __forceinline__ int wave_incl_scan_i(int v) {
   return v;
 }
 __device__ __forceinline__ int wave_sum_i32(int v) { return __builtin_amdgcn_readlane(wave_incl_scan_i(v), 63); }
+
+// Rotation-histogram bin of a match: `rot = angle1 - angle2; if (rot < 0) rot += 360; bin = round(rot * factor)` with the
+// reference's factor (sic) 1 / HISTO_LENGTH (L/src/ORBmatcher.cc:174,232-237; again at :456, :574, :719, :1352, :1475)
+__device__ __forceinline__ int rot_bin(float angle1, float angle2) {
+  float rot = angle1 - angle2;
+  if (rot < 0.0f) rot += 360.0f;
+  const int bin = (int)roundf(rot * (1.0f / ORBFE_HISTO_LENGTH));
+  return bin == ORBFE_HISTO_LENGTH ? 0 : bin;
+}
+// ComputeThreeMaxima (L/src/ORBmatcher.cc:1506-1538)
+__device__ inline void three_maxima(const int* hs, int L, int& ind1, int& ind2, int& ind3) {
+  int max1 = 0, max2 = 0, max3 = 0;
+  ind1 = ind2 = ind3 = -1;
+  for (int i = 0; i < L; i++) {
+    const int s = hs[i];
+    if (s > max1) { max3 = max2; max2 = max1; max1 = s; ind3 = ind2; ind2 = ind1; ind1 = i; }
+    else if (s > max2) { max3 = max2; max2 = s; ind3 = ind2; ind2 = i; }
+    else if (s > max3) { max3 = s; ind3 = i; }
+  }
+  if (max2 < 0.1f * (float)max1) { ind2 = -1; ind3 = -1; }
+  else if (max3 < 0.1f * (float)max1) { ind3 = -1; }
+}
+
+// The 16-byte record of FrameBatch::cell_rec, one per grid entry in CSR order: everything a window walk tests per entry
+// (L/src/Frame.cc:379-393 and the matcher's mvuRight gate) instead of the index -> keypoint -> mvuRight chain.  A second writer
+// states this layout by hand: the record loop of grid_build_global_kernel (grid_kernels.hip) -- change both together.
+__device__ __forceinline__ uint4 cell_rec_pack(int i, int octave, float x, float y, float ur) {
+  return make_uint4((uint32_t)i | ((uint32_t)octave << 24), (uint32_t)__float_as_int(x), (uint32_t)__float_as_int(y), (uint32_t)__float_as_int(ur));
+}
+struct CellRec { int idx, oct; float x, y, ur; };
+__device__ __forceinline__ CellRec cell_rec_unpack(const uint4 rec) {
+  return {(int)(rec.x & 0xFFFFFFu), (int)(rec.x >> 24), __int_as_float((int)rec.y), __int_as_float((int)rec.z), __int_as_float((int)rec.w)};
+}
 
 // Enumerates, in the reference's order, the keypoints GetFeaturesInArea returns for query q that also pass the
 // matcher's stereo gate, and calls fn(rank, idx, dist) for each, wave-cooperatively: a chunk of up to 64
@@ -95,10 +131,10 @@ __device__ __forceinline__ int enumerate_window(const FrameBatch& F, int f, cons
     bool ok = false;
     int idx = 0, oct = 0;
     if (ent >= 0) {
-      const uint4 rec = cr[ent];
-      idx = (int)(rec.x & 0xFFFFFFu);
-      oct = (int)(rec.x >> 24);
-      const float kx = __int_as_float((int)rec.y), ky = __int_as_float((int)rec.z), kur = __int_as_float((int)rec.w);
+      const CellRec k = cell_rec_unpack(cr[ent]);
+      idx = k.idx;
+      oct = k.oct;
+      const float kx = k.x, ky = k.y, kur = k.ur;
       ok = true;
       if (bCheckLevels) {
         if (oct < q.min_level) ok = false;

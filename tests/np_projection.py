@@ -77,10 +77,10 @@ _CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), os.pardir, "ref
 
 @functools.lru_cache(maxsize=None)
 def kernel_constants():
-    """RC_THREADS, RC_REG, RC_LIST_CAP, ORBFE_CAND_LANES (match_kernels.hip) and ORBFE_MAX_CAND (matcher.cpp), from their #define lines:
+    """RC_THREADS, RC_REG, RC_LIST_CAP, ORBFE_CAND_LANES (projection_kernels.hip) and ORBFE_MAX_CAND (matcher.cpp), from their #define lines:
     the census follows the kernel when one of them moves, and fails when one is no longer found"""
     out = {}
-    for fn, names in (("match_kernels.hip", ("RC_THREADS", "RC_REG", "RC_LIST_CAP", "ORBFE_CAND_LANES")), ("matcher.cpp", ("ORBFE_MAX_CAND",))):
+    for fn, names in (("projection_kernels.hip", ("RC_THREADS", "RC_REG", "RC_LIST_CAP", "ORBFE_CAND_LANES")), ("matcher.cpp", ("ORBFE_MAX_CAND",))):
         with open(os.path.join(_CSRC, fn)) as f:
             text = f.read()
         for name in names:

@@ -43,7 +43,7 @@ if True:
         fn = L.orbfe_debug_rs_profile
     except AttributeError:
         fn = None
-    if fn is not None:   # library built with -DFC_TIMING=1 (tools/ab_build.sh rs "-DFC_TIMING=1" match_kernels.hip)
+    if fn is not None:   # library built with -DFC_TIMING=1 (tools/ab_build.sh rs "-DFC_TIMING=1" projection_kernels.hip)
         out = (C.c_ulonglong * 16)()
         fn(out, 1)
         for _ in range(100):
