@@ -14,8 +14,9 @@
 __global__ __launch_bounds__(64) void bow_match_kernel(BowParams P) {
   extern __shared__ __attribute__((aligned(16))) uint8_t taken[];  // per frame feature of this node
   const int lane = threadIdx.x;
-  // sequential mode (a frame feature listed under several nodes -- never produced by DBoW2, but legal input): one
-  // wave walks all node pairs in NodeId order and reads the match table from memory, as the reference does
+  // sequential mode (a frame feature listed under several nodes or, in the KF-KF form, a first-keyframe feature under several
+  // common nodes -- never produced by DBoW2, but legal input; search_plan.h decides): one wave walks all node pairs in NodeId
+  // order and reads the match table from memory, as the reference does
   const int first = P.sequential ? 0 : blockIdx.x, last = P.sequential ? P.n_pairs : blockIdx.x + 1;
   for (int pi = first; pi < last; pi++) {
   const BowPair pr = P.pairs[pi];

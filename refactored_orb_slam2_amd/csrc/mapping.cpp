@@ -175,7 +175,8 @@ extern "C" int orbfe_create_new_map_points(const orbfe_keypoint* keysA, const ui
     active[k] = !plans[k].pairs.empty();
   }
 
-  const size_t push_n = (size_t)std::max(totA, nA);
+  size_t push_n = (size_t)nA;   // one scratch for all neighbours, which run one after the other: the largest plan's visits
+  for (int k = 0; k < K; k++) push_n = std::max(push_n, (size_t)plans[k].push_cap);
   HostCall c("create new map points");
   const size_t o_vw1 = c.in(sizeof(orbfe_tri_view)), o_kA = c.in((size_t)nA * sizeof(orbfe_keypoint)), o_dA = c.in((size_t)nA * 32),
                o_uA = c.in((size_t)nA * 4), o_zA = c.in((size_t)nA * 4), o_iA = c.in((size_t)totA * 4), o_vA = c.in((size_t)nA),

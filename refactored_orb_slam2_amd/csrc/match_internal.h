@@ -4,6 +4,7 @@
 #include <vector>
 
 #include "orbfe_internal.h"
+#include "search_plan.h"   // BowPair, TriSearchPlan / BowSearchPlan and the plan functions (host only, no device needed)
 
 #define GRID_CELLS (ORBFE_GRID_COLS * ORBFE_GRID_ROWS)
 
@@ -76,13 +77,12 @@ struct StereoParams {
 #define STEREO_MAX_KEYS 8192        // (row bucket, octave) keys: 512 x 16; the bucket kernel's LDS holds two ints per key
 #define STEREO_BUCKET_SPAN 8        // a band [y-r, y+r], r = 2*scale <= ~25 rows, overlaps at most this many buckets
 
-struct BowPair { int32_t startA, countA, startB, countB; };
 struct BowParams {
   const BowPair* pairs;
   const uint8_t* descA; const float* angleA; const uint8_t* validA; const int32_t* idxA;
   const uint8_t* descB; const float* angleB; const int32_t* idxB;
   float nnratio; int check_ori;
-  int sequential, n_pairs;  // sequential != 0: a frame feature occurs under more than one node
+  int sequential, n_pairs;  // sequential != 0: the nodes are coupled through a feature listed twice (search_plan.h)
   int kf_mode;              // SearchByBoW(KF,KF): validB mask, strict TH_LOW, result per A feature
   const uint8_t* validB;
   int32_t* matchA;          // [nA], pre-set to -1 (kf_mode)
@@ -113,12 +113,8 @@ struct TriParams {
   orbfe_epipolar ep;
 };
 void orbfe_launch_triangulation(const TriParams& p, int n_pairs, hipStream_t s);
-// matcher.cpp: the halves of orbfe_search_for_triangulation around its upload, shared with orbfe_create_new_map_points (mapping.cpp)
-struct TriSearchPlan {
-  std::vector<BowPair> pairs;   // the common vocabulary nodes
-  int totA = 0, totB = 0;       // entries of the two index arrays
-  int sequential = 0;           // a pKF1 feature is listed under two nodes
-};
+// the halves of orbfe_search_for_triangulation around its upload, shared with orbfe_create_new_map_points (mapping.cpp): the plan is
+// search_plan.h's orbfe_tri_search_plan, the enqueue half is in matcher.cpp
 struct TriSearchBuffers {       // device pointers of one search
   const BowPair* pairs; int n_pairs;
   const uint8_t* descA; const uint8_t* descB;
@@ -128,10 +124,8 @@ struct TriSearchBuffers {       // device pointers of one search
   const uint8_t* stereoA; const uint8_t* stereoB;   // mvuRight >= 0
   int32_t* matchA;              // [nA], pre-set to -1
   int32_t* counters;            // 64 ints, pre-set to 0; [1] = nmatches afterwards
-  int32_t* push_idx; uint8_t* push_bin;   // scratch, max(totA, nA) entries each
+  int32_t* push_idx; uint8_t* push_bin;   // scratch, TriSearchPlan::push_cap entries each
 };
-int orbfe_tri_search_plan(int nA, const orbfe_featvec_node* nodesA, int n_nodesA, const int32_t* idxA, int nB,
-                          const orbfe_featvec_node* nodesB, int n_nodesB, const int32_t* idxB, TriSearchPlan& plan);
 int orbfe_tri_search_enqueue(const TriSearchBuffers& b, const orbfe_epipolar* ep, int check_orientation, int sequential, hipStream_t s);
 void orbfe_launch_proj_best(const FrameBatch& f, const QueryBatch& q, int gate, const float* inv_sigma2, int32_t* best_idx,
                             int32_t* best_dist, int n_frames, hipStream_t s);

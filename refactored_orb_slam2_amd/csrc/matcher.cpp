@@ -528,40 +528,15 @@ static int bow_impl(const uint8_t* descA, const float* angleA, const uint8_t* va
     for (int i = 0; i < nA; i++) matchA_out[i] = -1;
   if (nA == 0 || nB == 0 || n_nodesA == 0 || n_nodesB == 0) return ORBFE_OK;
   if (!descA || !angleA || !validA || !nodesA || !idxA || !descB || !angleB || !nodesB || !idxB) return ORBFE_ERR_INVALID;
-  // merge-join of the two FeatureVectors on NodeId (:183-253; lower_bound jumps == plain two-pointer walk on sorted ids)
-  std::vector<BowPair> pairs;
-  int ia = 0, ib = 0, totA = 0, totB = 0, maxB = 0;
-  while (ia < n_nodesA && ib < n_nodesB) {
-    if (nodesA[ia].node_id == nodesB[ib].node_id) {
-      pairs.push_back(BowPair{nodesA[ia].start, nodesA[ia].count, nodesB[ib].start, nodesB[ib].count});
-      maxB = std::max(maxB, nodesB[ib].count);
-      ia++; ib++;
-    } else if (nodesA[ia].node_id < nodesB[ib].node_id) ia++;
-    else ib++;
+  // the merge-join of the two FeatureVectors on NodeId, the bounds checks, the replay decision and the scratch size (search_plan.h)
+  BowSearchPlan plan;
+  if (int prc = orbfe_bow_search_plan(nA, nodesA, n_nodesA, idxA, nB, nodesB, n_nodesB, idxB, kf_mode, plan)) {
+    if (plan.maxB > ORBFE_NODE_MAX_B) orbfe_set_error("a vocabulary node lists %d frame features (at most %d)", plan.maxB, ORBFE_NODE_MAX_B);
+    return prc;
   }
-  for (int i = 0; i < n_nodesA; i++) totA = std::max(totA, nodesA[i].start + nodesA[i].count);
-  for (int i = 0; i < n_nodesB; i++) totB = std::max(totB, nodesB[i].start + nodesB[i].count);
+  const std::vector<BowPair>& pairs = plan.pairs;
+  const int totA = plan.totA, totB = plan.totB, maxB = plan.maxB, sequential = plan.sequential;
   if (pairs.empty()) return ORBFE_OK;
-  if (maxB > 60000) {
-    orbfe_set_error("a vocabulary node lists %d frame features (at most 60000)", maxB);
-    return ORBFE_ERR_INVALID;
-  }
-  // nodes are independent only if no frame feature is listed under two of them (always true for DBoW2 output)
-  int sequential = 0;
-  {
-    std::vector<uint8_t> seen((size_t)nB, 0);
-    for (const BowPair& pr : pairs) {   // a malformed FeatureVector must not index past the descriptor arrays on the device
-      if (pr.startA < 0 || pr.countA < 0 || pr.startB < 0 || pr.countB < 0) return ORBFE_ERR_INVALID;
-      for (int t = 0; t < pr.countA; t++)
-        if (idxA[pr.startA + t] < 0 || idxA[pr.startA + t] >= nA) return ORBFE_ERR_INVALID;
-      for (int t = 0; t < pr.countB; t++) {
-        const int j = idxB[pr.startB + t];
-        if (j < 0 || j >= nB) return ORBFE_ERR_INVALID;
-        if (seen[j]) sequential = 1;
-        seen[j] = 1;
-      }
-    }
-  }
   // one packed upload [pairs | descA | descB | angleA | angleB | idxA | idxB | validA | validB | scratch | counters | matchB | matchA]
   // (the match tables go up filled with -1, the counters zero), one packed download of the tail from the counters on
   const size_t b_pairs = pairs.size() * sizeof(BowPair);
@@ -569,7 +544,7 @@ static int bow_impl(const uint8_t* descA, const float* angleA, const uint8_t* va
   const size_t o_pairs = c.in(b_pairs), o_dA = c.in((size_t)nA * 32), o_dB = c.in((size_t)nB * 32), o_aA = c.in((size_t)nA * 4),
                o_aB = c.in((size_t)nB * 4), o_iA = c.in((size_t)totA * 4), o_iB = c.in((size_t)totB * 4), o_vA = c.in((size_t)nA),
                o_vB = c.in(kf_mode ? (size_t)nB : 0);
-  const size_t o_pi = c.scratch((size_t)nA * 4), o_pb = c.scratch((size_t)nA);
+  const size_t o_pi = c.scratch((size_t)plan.push_cap * 4), o_pb = c.scratch((size_t)plan.push_cap);   // one entry per visit of an A feature
   const size_t o_cnt = c.out(256), o_mB = c.out((size_t)nB * 4), o_mA = c.out(kf_mode ? (size_t)nA * 4 : 0);
   int rc;
   if ((rc = c.open())) return rc;
@@ -738,40 +713,6 @@ extern "C" int orbfe_kf_search(const orbfe_frame_view* f, const float* inv_level
   return ORBFE_OK;
 }
 
-// The host half of SearchForTriangulation in front of the upload: the merge-join of the two FeatureVectors on NodeId and the
-// checks that keep a malformed one from indexing past the arrays on the device.  ORBFE_OK with no pairs: nothing to search.
-int orbfe_tri_search_plan(int nA, const orbfe_featvec_node* nodesA, int n_nodesA, const int32_t* idxA, int nB,
-                          const orbfe_featvec_node* nodesB, int n_nodesB, const int32_t* idxB, TriSearchPlan& plan) {
-  plan.pairs.clear();
-  plan.totA = plan.totB = plan.sequential = 0;
-  int ia = 0, ib = 0;
-  while (ia < n_nodesA && ib < n_nodesB) {
-    if (nodesA[ia].node_id == nodesB[ib].node_id) {
-      plan.pairs.push_back(BowPair{nodesA[ia].start, nodesA[ia].count, nodesB[ib].start, nodesB[ib].count});
-      if (nodesB[ib].count > 60000) return ORBFE_ERR_INVALID;
-      ia++; ib++;
-    } else if (nodesA[ia].node_id < nodesB[ib].node_id) ia++;
-    else ib++;
-  }
-  for (int i = 0; i < n_nodesA; i++) plan.totA = std::max(plan.totA, nodesA[i].start + nodesA[i].count);
-  for (int i = 0; i < n_nodesB; i++) plan.totB = std::max(plan.totB, nodesB[i].start + nodesB[i].count);
-  if (plan.pairs.empty()) return ORBFE_OK;
-  // a pKF1 feature listed under two nodes (never produced by DBoW2) is visited twice by the reference: replay in order
-  std::vector<uint8_t> seen((size_t)nA, 0);
-  for (const BowPair& pr : plan.pairs) {
-    if (pr.startA < 0 || pr.countA < 0 || pr.startB < 0 || pr.countB < 0) return ORBFE_ERR_INVALID;
-    for (int t = 0; t < pr.countA; t++) {
-      const int j = idxA[pr.startA + t];
-      if (j < 0 || j >= nA) return ORBFE_ERR_INVALID;
-      if (seen[j]) plan.sequential = 1;
-      seen[j] = 1;
-    }
-    for (int t = 0; t < pr.countB; t++)
-      if (idxB[pr.startB + t] < 0 || idxB[pr.startB + t] >= nB) return ORBFE_ERR_INVALID;
-  }
-  return ORBFE_OK;
-}
-
 // The enqueue half: the search and its rotation-histogram pass on stream s, every pointer a device pointer
 int orbfe_tri_search_enqueue(const TriSearchBuffers& b, const orbfe_epipolar* ep, int check_orientation, int sequential, hipStream_t s) {
   TriParams t;
@@ -811,7 +752,7 @@ extern "C" int orbfe_search_for_triangulation(const orbfe_keypoint* keysA, const
   if (pairs.empty()) return ORBFE_OK;
   // one packed upload [pairs | descA | descB | keysA | keysB | idxA | idxB | validA | validB | stereoA | stereoB | scratch | matchA | counters]
   // (matchA goes up filled with -1, the counters zero), one packed download of [matchA | counters]
-  const size_t b_pairs = pairs.size() * sizeof(BowPair), push_n = (size_t)std::max(totA, nA);
+  const size_t b_pairs = pairs.size() * sizeof(BowPair), push_n = (size_t)plan.push_cap;
   HostCall c("orbfe_search_for_triangulation");
   const size_t o_pairs = c.in(b_pairs), o_dA = c.in((size_t)nA * 32), o_dB = c.in((size_t)nB * 32), o_kA = c.in((size_t)nA * sizeof(orbfe_keypoint)),
                o_kB = c.in((size_t)nB * sizeof(orbfe_keypoint)), o_iA = c.in((size_t)totA * 4), o_iB = c.in((size_t)totB * 4),

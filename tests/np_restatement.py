@@ -464,23 +464,26 @@ class RefFrame:
         return vIndices
 
 
-def compute_three_maxima(sizes, lt=operator.lt):
-    """ORBmatcher::ComputeThreeMaxima (:1506-1538) on the bin sizes.  `lt` stands in for the `<` of the 0.1 rule (proj_walk's rules)."""
+def compute_three_maxima(sizes, lt=operator.lt, gt1=operator.gt, gt2=operator.gt, gt3=operator.gt, lt3=None):
+    """ORBmatcher::ComputeThreeMaxima (:1506-1538) on the bin sizes.  `lt` stands in for the `<` of the 0.1 rule (proj_walk's rules);
+    node_walk's rules swap each of the five comparisons on its own: gt1 / gt2 / gt3 the three `s > max`, lt the tenth test of max2,
+    lt3 the tenth test of max3 (None: the same as lt)."""
+    lt3 = lt if lt3 is None else lt3
     max1 = max2 = max3 = 0
     ind1 = ind2 = ind3 = -1
     for i, s in enumerate(sizes):
-        if s > max1:
+        if gt1(s, max1):
             max3, max2, max1 = max2, max1, s
             ind3, ind2, ind1 = ind2, ind1, i
-        elif s > max2:
+        elif gt2(s, max2):
             max3, max2 = max2, s
             ind3, ind2 = ind2, i
-        elif s > max3:
+        elif gt3(s, max3):
             max3 = s
             ind3 = i
     if lt(_f32(max2), _f32(0.1) * _f32(max1)):
         ind2 = ind3 = -1
-    elif lt(_f32(max3), _f32(0.1) * _f32(max1)):
+    elif lt3(_f32(max3), _f32(0.1) * _f32(max1)):
         ind3 = -1
     return ind1, ind2, ind3
 
@@ -683,112 +686,203 @@ def ref_search_by_projection_keyframe(F, points, orb_dist, check_orientation, ha
     return proj_walk(F, _last_as_queries(points, True), 1, 0.0, check_orientation, has_point, th_high=orb_dist, stereo_gate=False)[:3]
 
 
-def ref_search_by_bow(descKF, angleKF, validKF, featvecKF, descF, angleF, featvecF, nnratio, check_orientation):
-    """SearchByBoW(KeyFrame*, Frame&, vpMapPointMatches) (:161-273).  featvec*: {node id: [feature indices]} (DBoW2::FeatureVector
-    is a std::map: ascending ids); validKF[i]: the keyframe's map point i exists and is not bad.  Returns (nmatches,
-    keyframe feature index per frame feature or -1)."""
-    matches = [-1] * len(descF)
-    rotHist = [[] for _ in range(HISTO_LENGTH)]
-    nmatches = 0
-    idsKF, idsF = sorted(featvecKF), sorted(featvecF)
-    a = b = 0
-    while a < len(idsKF) and b < len(idsF):
-        if idsKF[a] == idsF[b]:
-            for realIdxKF in featvecKF[idsKF[a]]:
-                if not validKF[realIdxKF]:
-                    continue
-                bestDist1, bestIdxF, bestDist2 = 256, -1, 256
-                for realIdxF in featvecF[idsF[b]]:
-                    if matches[realIdxF] >= 0:
-                        continue
-                    dist = descriptor_distance(descKF[realIdxKF], descF[realIdxF])
-                    if dist < bestDist1:
-                        bestDist2, bestDist1, bestIdxF = bestDist1, dist, realIdxF
-                    elif dist < bestDist2:
-                        bestDist2 = dist
-                if bestDist1 <= TH_LOW and _f32(bestDist1) < _f32(nnratio) * _f32(bestDist2):
-                    matches[bestIdxF] = realIdxKF
-                    if check_orientation:
-                        rotHist[_rot_bin(angleKF[realIdxKF], angleF[bestIdxF])].append(bestIdxF)
-                    nmatches += 1
-            a += 1
-            b += 1
-        elif idsKF[a] < idsF[b]:
-            while a < len(idsKF) and idsKF[a] < idsF[b]:      # lower_bound
-                a += 1
-        else:
-            while b < len(idsF) and idsF[b] < idsKF[a]:
-                b += 1
-    if check_orientation:
-        ind = compute_three_maxima([len(h) for h in rotHist])
-        for i in range(HISTO_LENGTH):
-            if i in ind:
-                continue
-            for j in rotHist[i]:
-                matches[j] = -1
-                nmatches -= 1
-    return nmatches, matches
+# ------------------------------------------------------------------------------------------------------------------------------
+# The searches over common vocabulary nodes -- SearchByBoW(KeyFrame*, Frame&) (:161-273), SearchByBoW(KeyFrame*, KeyFrame*) (:494-612),
+# SearchForTriangulation (:614-764) -- and SearchForInitialization (:388-492): one instrumented body each (bow_walk serves both
+# SearchByBoW forms).  The ref_search_* functions below are thin readings of them, as the ref_search_by_projection_* are of proj_walk.
+# Exits, one per VISIT of a first-side feature (a feature listed under several common nodes is visited once per node) and, in
+# `exits`, the one of the last visit per first-side feature:
+(NX_UNVISITED, NX_INVALID, NX_EMPTY, NX_ALL_GONE, NX_TOO_FAR, NX_RATIO, NX_MATCHED, NX_STOLEN, NX_ROTATION) = range(-1, 8)
+# what removed a candidate of SearchForTriangulation, in the order the reference asks
+(TG_INVALID, TG_FAR, TG_WORSE, TG_EPIPOLE, TG_DEN, TG_EPIPOLAR, TG_PASSED) = range(7)
+
+# The reference's comparisons; a test swaps exactly one of them.  Swapping best_lt or second_lt changes no result where a ratio test
+# follows (equal best candidates make best == second-best, which it rejects): see test_nodesearch_cpu.EQUIVALENT.
+NODE_RULES = dict(
+    best_lt=operator.lt,             # dist < bestDist1: of equal best candidates the first is named
+    second_lt=operator.lt,           # dist < bestDist2
+    accept_frame=operator.le,        # SearchByBoW(KF, F): bestDist1 <= TH_LOW
+    accept_kf=operator.lt,           # SearchByBoW(KF, KF): bestDist1 < TH_LOW
+    accept_init=operator.le,         # SearchForInitialization: bestDist <= TH_LOW
+    ratio_lt=operator.lt,            # (float)bestDist1 < mfNNratio * (float)bestDist2
+    ratio_float=True,                # ... a float product (False: the same in double)
+    tri_far=operator.gt,             # dist > TH_LOW
+    tri_worse=operator.gt,           # dist > bestDist: of equal candidates the LAST one wins
+    has_right=lambda ur: ur >= 0,    # mvuRight[idx] >= 0
+    disc_lt=operator.lt,             # distex * distex + distey * distey < 100 * mvScaleFactors[octave]
+    disc_float=True,                 # ... in float (False: in double)
+    epi_lt=operator.lt,              # dsqr < 3.84 * sigma2
+    epi_double=True,                 # ... in double, 3.84 being a double constant (False: in float)
+    den_zero=lambda den: den == 0,   # CheckDistEpipolarLine refuses a degenerate line
+    kept_le=operator.le,             # vMatchedDistance[i2] <= dist: an equal distance cannot steal
+    stolen_stay_in_hist=True,        # SearchForInitialization leaves the rotHist entry of a match that was stolen later
+    max_gt1=operator.gt, max_gt2=operator.gt, max_gt3=operator.gt,    # ComputeThreeMaxima: s > max1 / max2 / max3
+    max_lt2=operator.lt, max_lt3=operator.lt,                         # max2 < 0.1f * max1, max3 < 0.1f * max1
+    round=c_round,                   # round(): halves away from zero
+)
 
 
-def _featvec_walk(fvA, fvB):
-    """The lock-step walk over two DBoW2::FeatureVector maps (ascending node ids, lower_bound on a mismatch): yields the lists of
-    feature indices of every node both hold."""
+def _node_maxima(hist, R):
+    return compute_three_maxima(hist, R["max_lt2"], R["max_gt1"], R["max_gt2"], R["max_gt3"], R["max_lt3"])
+
+
+def _ratio_ok(R, best, second, nnratio):
+    if R["ratio_float"]:
+        return R["ratio_lt"](_f32(best), _f32(nnratio) * _f32(second))
+    return R["ratio_lt"](float(best), float(_f32(nnratio)) * float(second))
+
+
+def _featvec_pairs(fvA, fvB):
+    """The lock-step walk over two DBoW2::FeatureVector maps (ascending node ids, lower_bound on a mismatch): yields
+    (node id, list of A, list of B) for every node both hold."""
     idsA, idsB = sorted(fvA), sorted(fvB)
     a = b = 0
     while a < len(idsA) and b < len(idsB):
         if idsA[a] == idsB[b]:
-            yield fvA[idsA[a]], fvB[idsB[b]]
+            yield idsA[a], fvA[idsA[a]], fvB[idsB[b]]
             a += 1
             b += 1
         elif idsA[a] < idsB[b]:
-            while a < len(idsA) and idsA[a] < idsB[b]:
+            while a < len(idsA) and idsA[a] < idsB[b]:      # lower_bound
                 a += 1
         else:
             while b < len(idsB) and idsB[b] < idsA[a]:
                 b += 1
 
 
+def _best_two(free, R):
+    """free: [(position in the node's list, distance)] in list order.  Returns the walk's (bestDist1, position, bestDist2) and
+    the facts of the pick: position of the first candidate at the second-best distance (-1), the positions tied at the best."""
+    best, bpos, second = 256, -1, 256
+    for pos, d in free:
+        if R["best_lt"](d, best):
+            second, best, bpos = best, d, pos
+        elif R["second_lt"](d, second):
+            second = d
+    spos = next((p for p, d in free if d == second and p != bpos), -1)
+    return best, bpos, second, spos, [p for p, d in free if d == best]
+
+
+def _visit_facts(v, n_list, free, best, bpos, second, spos, ties):
+    v.update(n_list=n_list, n_free=len(free), best=best, second=second, best_pos=bpos, second_pos=spos, tie_pos=ties,
+             second_same_lane=spos >= 0 and spos % 64 == bpos % 64)
+
+
+def _close_rotation(R, rotHist, visits, clear):
+    """the rotation check behind a walk: rotHist[bin] = [visit index]; clear(visit) removes its match and tells whether the reference
+    decrements nmatches for it.  Returns (hist, maxima, decrements)."""
+    hist = [len(h) for h in rotHist]
+    ind = _node_maxima(hist, R)
+    dec = 0
+    for b in range(HISTO_LENGTH):
+        if b in ind:
+            continue
+        for k in rotHist[b]:
+            if clear(visits[k]):
+                dec += 1
+    return hist, ind, dec
+
+
+def _node_result(n_first, visits, **facts):
+    exits = np.full(n_first, NX_UNVISITED, np.int32)
+    pushes = np.zeros(n_first, np.int32)
+    for v in visits:
+        exits[v["a"]] = v["exit"]
+        pushes[v["a"]] += v["bin"] >= 0
+    facts.update(visits=visits, pushes=pushes)
+    return exits, facts
+
+
+def bow_walk(descA, angleA, validA, fvA, descB, angleB, validB, fvB, nnratio, check_orientation, kf_mode, rules=None):
+    """Both SearchByBoW forms read literally.  kf_mode False: SearchByBoW(KeyFrame*, Frame&) -- validB is not read, the result is the
+    keyframe feature per frame feature; True: SearchByBoW(pKF1, pKF2) -- the result is the index in keyframe 2 per feature of keyframe 1.
+    Returns (nmatches, result, exits, facts).  facts["visits"]: one dict per visit -- a, node, exit, n_list, n_free, best, second
+    (256: none), best_pos / second_pos (places in the node's second-side list, the lane being place % 64), second_same_lane, tie_pos,
+    match (the second-side feature, -1), bin (-1: no entry pushed); facts["pushes"] per first-side feature; hist, maxima, n_pairs,
+    dup_a / dup_b (a feature met under two visits / listed twice among the common nodes)."""
+    R = NODE_RULES if rules is None else rules
+    nA, nB = len(descA), len(descB)
+    matchesB = [-1] * nB                 # KF-F: vpMapPointMatches;  KF-KF: vbMatched2 as "the visit that took it"
+    matches12 = [-1] * nA
+    owner12 = [-1] * nA                  # the visit whose match vpMatches12[idx1] holds
+    rotHist = [[] for _ in range(HISTO_LENGTH)]
+    visits = []
+    nmatches = n_pairs = 0
+    seenA, seenB, dup_a, dup_b = set(), set(), False, False
+    accept = R["accept_kf"] if kf_mode else R["accept_frame"]
+    for nid, listA, listB in _featvec_pairs(fvA, fvB):
+        n_pairs += 1
+        dup_b = dup_b or len(set(listB)) < len(listB) or bool(seenB & set(listB))
+        seenB |= set(listB)
+        for idxA in listA:
+            dup_a = dup_a or idxA in seenA
+            seenA.add(idxA)
+            v = dict(a=idxA, node=nid, exit=NX_INVALID, match=-1, bin=-1)
+            visits.append(v)
+            if not validA[idxA]:
+                continue
+            free = [(pos, descriptor_distance(descA[idxA], descB[j])) for pos, j in enumerate(listB)
+                    if matchesB[j] < 0 and not (kf_mode and not validB[j])]
+            best, bpos, second, spos, ties = _best_two(free, R)
+            _visit_facts(v, len(listB), free, best, bpos, second, spos, ties)
+            if bpos < 0:
+                v["exit"] = NX_EMPTY if not listB else NX_ALL_GONE
+            elif not accept(best, TH_LOW):
+                v["exit"] = NX_TOO_FAR
+            elif not _ratio_ok(R, best, second, nnratio):
+                v["exit"] = NX_RATIO
+            else:
+                j = listB[bpos]
+                v["exit"], v["match"] = NX_MATCHED, j
+                matchesB[j] = idxA
+                if kf_mode:
+                    if owner12[idxA] >= 0:
+                        visits[owner12[idxA]]["exit"] = NX_STOLEN      # overwritten: both stay counted
+                    matches12[idxA], owner12[idxA] = j, len(visits) - 1
+                nmatches += 1
+                if check_orientation:
+                    v["bin"] = _rot_bin(angleA[idxA], angleB[j], R["round"])
+                    rotHist[v["bin"]].append(len(visits) - 1)
+    hist, ind = [0] * HISTO_LENGTH, (-1, -1, -1)
+    if check_orientation:
+        def clear(v):
+            v["exit"] = NX_ROTATION
+            if kf_mode:
+                matches12[v["a"]] = -1          # vpMatches12[rotHist[i][j]] = NULL, whichever visit wrote it last
+            else:
+                matchesB[v["match"]] = -1
+            return True
+        hist, ind, dec = _close_rotation(R, rotHist, visits, clear)
+        nmatches -= dec
+    result = np.array(matches12 if kf_mode else matchesB, np.int32).reshape(-1)
+    exits, facts = _node_result(nA, visits, hist=hist, maxima=ind, n_pairs=n_pairs, dup_a=dup_a, dup_b=dup_b)
+    return nmatches, result, exits, facts
+
+
+def ref_search_by_bow(descKF, angleKF, validKF, featvecKF, descF, angleF, featvecF, nnratio, check_orientation):
+    """SearchByBoW(KeyFrame*, Frame&, vpMapPointMatches) (:161-273).  featvec*: {node id: [feature indices]} (DBoW2::FeatureVector
+    is a std::map: ascending ids); validKF[i]: the keyframe's map point i exists and is not bad.  Returns (nmatches,
+    keyframe feature index per frame feature or -1)."""
+    nm, matches = bow_walk(descKF, angleKF, validKF, featvecKF, descF, angleF, None, featvecF, nnratio, check_orientation, False)[:2]
+    return nm, matches.tolist()
+
+
 def ref_search_by_bow_kf(desc1, angle1, valid1, featvec1, desc2, angle2, valid2, featvec2, nnratio, check_orientation):
     """SearchByBoW(KeyFrame* pKF1, KeyFrame* pKF2, vpMatches12) (:494-612).  valid*[i]: the keyframe's map point i exists and is not
     bad.  Returns (nmatches, index in keyframe 2 per feature of keyframe 1 or -1)."""
-    vpMatches12 = [-1] * len(desc1)
-    vbMatched2 = [False] * len(desc2)
-    rotHist = [[] for _ in range(HISTO_LENGTH)]
-    nmatches = 0
-    for node1, node2 in _featvec_walk(featvec1, featvec2):
-        for idx1 in node1:
-            if not valid1[idx1]:
-                continue
-            bestDist1, bestIdx2, bestDist2 = 256, -1, 256
-            for idx2 in node2:
-                if vbMatched2[idx2] or not valid2[idx2]:
-                    continue
-                dist = descriptor_distance(desc1[idx1], desc2[idx2])
-                if dist < bestDist1:
-                    bestDist2, bestDist1, bestIdx2 = bestDist1, dist, idx2
-                elif dist < bestDist2:
-                    bestDist2 = dist
-            if bestDist1 < TH_LOW:
-                if _f32(bestDist1) < _f32(nnratio) * _f32(bestDist2):
-                    vpMatches12[idx1] = bestIdx2
-                    vbMatched2[bestIdx2] = True
-                    if check_orientation:
-                        rotHist[_rot_bin(angle1[idx1], angle2[bestIdx2])].append(idx1)
-                    nmatches += 1
-    if check_orientation:
-        ind = compute_three_maxima([len(h) for h in rotHist])
-        for i in range(HISTO_LENGTH):
-            if i in ind:
-                continue
-            for j in rotHist[i]:
-                vpMatches12[j] = -1
-                nmatches -= 1
-    return nmatches, vpMatches12
+    nm, m12 = bow_walk(desc1, angle1, valid1, featvec1, desc2, angle2, valid2, featvec2, nnratio, check_orientation, True)[:2]
+    return nm, m12.tolist()
 
 
 def check_dist_epipolar_line(x1, y1, x2, y2, octave2, F12, level_sigma2):
-    """ORBmatcher::CheckDistEpipolarLine (:137-159): float products and sums left to right, the last comparison in double (3.84
-    is a double constant)."""
+    """ORBmatcher::CheckDistEpipolarLine (:137-159)"""
+    return _epipolar_gate(x1, y1, x2, y2, octave2, F12, level_sigma2) == TG_PASSED
+
+
+def _epipolar_gate(x1, y1, x2, y2, octave2, F12, level_sigma2, rules=None):
+    """CheckDistEpipolarLine: float products and sums left to right, the last comparison in double (3.84 is a double constant).
+    Returns the gate that refused (TG_DEN, TG_EPIPOLAR) or TG_PASSED."""
+    R = NODE_RULES if rules is None else rules
     F = [[_f32(F12[r][c]) for c in range(3)] for r in range(3)]
     x1, y1, x2, y2 = _f32(x1), _f32(y1), _f32(x2), _f32(y2)
     a = x1 * F[0][0] + y1 * F[1][0] + F[2][0]
@@ -796,10 +890,100 @@ def check_dist_epipolar_line(x1, y1, x2, y2, octave2, F12, level_sigma2):
     c = x1 * F[0][2] + y1 * F[1][2] + F[2][2]
     num = a * x2 + b * y2 + c
     den = a * a + b * b
-    if den == 0:
-        return False
+    if R["den_zero"](den):
+        return TG_DEN
     dsqr = num * num / den
-    return float(dsqr) < 3.84 * float(_f32(level_sigma2[octave2]))
+    if R["epi_double"]:
+        ok = R["epi_lt"](float(dsqr), 3.84 * float(_f32(level_sigma2[octave2])))
+    else:
+        ok = R["epi_lt"](dsqr, _f32(3.84) * _f32(level_sigma2[octave2]))
+    return TG_PASSED if ok else TG_EPIPOLAR
+
+
+def tri_walk(keys1, desc1, u_right1, has_mp1, featvec1, keys2, desc2, u_right2, has_mp2, featvec2, F12, ex, ey, scale_factors,
+             level_sigma2, only_stereo, check_orientation, rules=None):
+    """SearchForTriangulation read literally.  Returns (nmatches, vMatches12, exits, facts); a visit carries, beside the fields of
+    bow_walk's, gates: one TG_* per entry of the node's second-side list (which gate removed the candidate), and best_pos / tie_pos
+    over the candidates that passed every gate at the winning distance."""
+    R = NODE_RULES if rules is None else rules
+    n1, n2 = len(keys1), len(keys2)
+    ur1 = [_f32(-1)] * n1 if u_right1 is None else [_f32(v) for v in u_right1]
+    ur2 = [_f32(-1)] * n2 if u_right2 is None else [_f32(v) for v in u_right2]
+    ex, ey = _f32(ex), _f32(ey)
+    vbMatched2 = [False] * n2           # read, never set (:677) -- kept so
+    vMatches12 = [-1] * n1
+    owner12 = [-1] * n1
+    rotHist = [[] for _ in range(HISTO_LENGTH)]
+    visits = []
+    nmatches = n_pairs = 0
+    seenA, dup_a = set(), False
+    for nid, node1, node2 in _featvec_pairs(featvec1, featvec2):
+        n_pairs += 1
+        for idx1 in node1:
+            dup_a = dup_a or idx1 in seenA
+            seenA.add(idx1)
+            v = dict(a=idx1, node=nid, exit=NX_INVALID, match=-1, bin=-1, gates=[])
+            visits.append(v)
+            if has_mp1[idx1]:
+                continue
+            bStereo1 = bool(R["has_right"](ur1[idx1]))
+            if only_stereo and not bStereo1:
+                continue
+            bestDist, bestIdx2, bpos = TH_LOW, -1, -1
+            passed = []
+            for pos, idx2 in enumerate(node2):
+                bStereo2 = bool(R["has_right"](ur2[idx2]))
+                if vbMatched2[idx2] or has_mp2[idx2] or (only_stereo and not bStereo2):
+                    v["gates"].append(TG_INVALID)
+                    continue
+                dist = descriptor_distance(desc1[idx1], desc2[idx2])
+                if R["tri_far"](dist, TH_LOW):
+                    v["gates"].append(TG_FAR)
+                    continue
+                if R["tri_worse"](dist, bestDist):
+                    v["gates"].append(TG_WORSE)
+                    continue
+                x2, y2, o2 = _f32(keys2["x"][idx2]), _f32(keys2["y"][idx2]), int(keys2["octave"][idx2])
+                if not bStereo1 and not bStereo2:
+                    distex = ex - x2
+                    distey = ey - y2
+                    if R["disc_float"]:
+                        inside = R["disc_lt"](distex * distex + distey * distey, _f32(100) * _f32(scale_factors[o2]))
+                    else:
+                        inside = R["disc_lt"](float(distex) * float(distex) + float(distey) * float(distey), 100.0 * float(_f32(scale_factors[o2])))
+                    if inside:
+                        v["gates"].append(TG_EPIPOLE)
+                        continue
+                g = _epipolar_gate(keys1["x"][idx1], keys1["y"][idx1], x2, y2, o2, F12, level_sigma2, R)
+                v["gates"].append(g)
+                if g == TG_PASSED:
+                    bestIdx2, bestDist, bpos = idx2, dist, pos
+                    passed.append((pos, dist))
+            g = v["gates"]
+            v.update(n_list=len(node2), n_free=len(passed), best=bestDist if bpos >= 0 else 256, second=256, best_pos=bpos, second_pos=-1,
+                     tie_pos=[p for p, d in passed if d == bestDist], second_same_lane=False)
+            if bestIdx2 < 0:
+                v["exit"] = (NX_EMPTY if not node2 else NX_ALL_GONE if any(t in (TG_EPIPOLE, TG_DEN, TG_EPIPOLAR) for t in g) or TG_FAR not in g
+                             else NX_TOO_FAR)
+                continue
+            v["exit"], v["match"] = NX_MATCHED, bestIdx2
+            if owner12[idx1] >= 0:
+                visits[owner12[idx1]]["exit"] = NX_STOLEN
+            vMatches12[idx1], owner12[idx1] = bestIdx2, len(visits) - 1
+            nmatches += 1
+            if check_orientation:
+                v["bin"] = _rot_bin(keys1["angle"][idx1], keys2["angle"][bestIdx2], R["round"])
+                rotHist[v["bin"]].append(len(visits) - 1)
+    hist, ind = [0] * HISTO_LENGTH, (-1, -1, -1)
+    if check_orientation:
+        def clear(v):
+            v["exit"] = NX_ROTATION
+            vMatches12[v["a"]] = -1
+            return True
+        hist, ind, dec = _close_rotation(R, rotHist, visits, clear)
+        nmatches -= dec
+    exits, facts = _node_result(n1, visits, hist=hist, maxima=ind, n_pairs=n_pairs, dup_a=dup_a, dup_b=False)
+    return nmatches, np.array(vMatches12, np.int32).reshape(-1), exits, facts
 
 
 def ref_search_for_triangulation(keys1, desc1, u_right1, has_mp1, featvec1, keys2, desc2, u_right2, has_mp2, featvec2, F12, ex, ey,
@@ -807,58 +991,18 @@ def ref_search_for_triangulation(keys1, desc1, u_right1, has_mp1, featvec1, keys
     """SearchForTriangulation(pKF1, pKF2, F12, vMatchedPairs, bOnlyStereo) (:614-764) after the epipole (ex, ey) has been formed.
     u_right*: mvuRight or None (monocular: every value -1).  vbMatched2 is read but never set by the reference -- kept so.  Returns
     (nmatches, vMatches12)."""
-    n1, n2 = len(keys1), len(keys2)
-    ur1 = [_f32(-1)] * n1 if u_right1 is None else [_f32(v) for v in u_right1]
-    ur2 = [_f32(-1)] * n2 if u_right2 is None else [_f32(v) for v in u_right2]
-    ex, ey = _f32(ex), _f32(ey)
-    vbMatched2 = [False] * n2
-    vMatches12 = [-1] * n1
-    rotHist = [[] for _ in range(HISTO_LENGTH)]
-    nmatches = 0
-    for node1, node2 in _featvec_walk(featvec1, featvec2):
-        for idx1 in node1:
-            if has_mp1[idx1]:
-                continue
-            bStereo1 = ur1[idx1] >= 0
-            if only_stereo and not bStereo1:
-                continue
-            bestDist, bestIdx2 = TH_LOW, -1
-            for idx2 in node2:
-                if vbMatched2[idx2] or has_mp2[idx2]:
-                    continue
-                bStereo2 = ur2[idx2] >= 0
-                if only_stereo and not bStereo2:
-                    continue
-                dist = descriptor_distance(desc1[idx1], desc2[idx2])
-                if dist > TH_LOW or dist > bestDist:
-                    continue
-                x2, y2, o2 = _f32(keys2["x"][idx2]), _f32(keys2["y"][idx2]), int(keys2["octave"][idx2])
-                if not bStereo1 and not bStereo2:
-                    distex = ex - x2
-                    distey = ey - y2
-                    if distex * distex + distey * distey < _f32(100) * _f32(scale_factors[o2]):
-                        continue
-                if check_dist_epipolar_line(keys1["x"][idx1], keys1["y"][idx1], x2, y2, o2, F12, level_sigma2):
-                    bestIdx2, bestDist = idx2, dist
-            if bestIdx2 >= 0:
-                vMatches12[idx1] = bestIdx2
-                nmatches += 1
-                if check_orientation:
-                    rotHist[_rot_bin(keys1["angle"][idx1], keys2["angle"][bestIdx2])].append(idx1)
-    if check_orientation:
-        ind = compute_three_maxima([len(h) for h in rotHist])
-        for i in range(HISTO_LENGTH):
-            if i in ind:
-                continue
-            for j in rotHist[i]:
-                vMatches12[j] = -1
-                nmatches -= 1
-    return nmatches, vMatches12
+    nm, m12 = tri_walk(keys1, desc1, u_right1, has_mp1, featvec1, keys2, desc2, u_right2, has_mp2, featvec2, F12, ex, ey, scale_factors,
+                       level_sigma2, only_stereo, check_orientation)[:2]
+    return nm, m12.tolist()
 
 
-def ref_search_for_initialization(keys1, desc1, F2, prev_matched, window, nnratio, check_orientation):
-    """SearchForInitialization(F1, F2, vbPrevMatched, vnMatches12, windowSize) (:388-492).  Returns (nmatches, vnMatches12,
-    updated vbPrevMatched)."""
+def init_walk(keys1, desc1, F2, prev_matched, window, nnratio, check_orientation, rules=None):
+    """SearchForInitialization read literally.  Returns (nmatches, vnMatches12, updated vbPrevMatched, exits, facts): one visit per
+    keypoint of F1 (facts["visits"][i1]) with, beside bow_walk's fields, outside (the window missed the grid), n_kept (candidates
+    an earlier, closer or equal match keeps), n_kept_equal (... at exactly the distance), victim (the F1 keypoint the match was
+    stolen from, -1), depth (1 + the victim's depth), bin; facts["hist_stolen"]: histogram entries whose match was stolen before
+    the rotation check ran."""
+    R = NODE_RULES if rules is None else rules
     INT_MAX = 2 ** 31 - 1
     n1 = len(keys1)
     prev = [(_f32(p[0]), _f32(p[1])) for p in prev_matched]
@@ -866,46 +1010,79 @@ def ref_search_for_initialization(keys1, desc1, F2, prev_matched, window, nnrati
     rotHist = [[] for _ in range(HISTO_LENGTH)]
     vMatchedDistance = [INT_MAX] * F2.N
     vnMatches21 = [-1] * F2.N
+    visits = []
     nmatches = 0
     for i1 in range(n1):
+        v = dict(a=i1, node=0, exit=NX_INVALID, match=-1, bin=-1, victim=-1, depth=0, outside=False, n_kept=0, n_kept_equal=0)
+        visits.append(v)
         level1 = int(keys1["octave"][i1])
         if level1 > 0:
             continue
-        vIndices2 = F2.GetFeaturesInArea(prev[i1][0], prev[i1][1], window, level1, level1)
+        info = {}
+        vIndices2 = F2.GetFeaturesInArea(prev[i1][0], prev[i1][1], window, level1, level1, info=info)
+        v["outside"] = info["outside"]
         if not vIndices2:
+            v["exit"] = NX_EMPTY
+            _visit_facts(v, 0, [], 256, -1, 256, -1, [])
             continue
-        bestDist, bestDist2, bestIdx2 = INT_MAX, INT_MAX, -1
-        for i2 in vIndices2:
+        free = []
+        for pos, i2 in enumerate(vIndices2):
             dist = descriptor_distance(desc1[i1], F2.desc[i2])
-            if vMatchedDistance[i2] <= dist:
+            if R["kept_le"](vMatchedDistance[i2], dist):
+                v["n_kept"] += 1
+                v["n_kept_equal"] += vMatchedDistance[i2] == dist
                 continue
-            if dist < bestDist:
-                bestDist2, bestDist, bestIdx2 = bestDist, dist, i2
-            elif dist < bestDist2:
-                bestDist2 = dist
-        if bestDist <= TH_LOW and _f32(bestDist) < _f32(bestDist2) * _f32(nnratio):
+            free.append((pos, dist))
+        best, bpos, second, spos, ties = _best_two(free, R)
+        _visit_facts(v, len(vIndices2), free, best, bpos, second, spos, ties)
+        if bpos < 0:
+            v["exit"] = NX_ALL_GONE
+        elif not R["accept_init"](best, TH_LOW):
+            v["exit"] = NX_TOO_FAR
+        elif not _ratio_ok(R, best, INT_MAX if second == 256 else second, nnratio):
+            v["exit"] = NX_RATIO
+        else:
+            bestIdx2 = vIndices2[bpos]
             if vnMatches21[bestIdx2] >= 0:
-                vnMatches12[vnMatches21[bestIdx2]] = -1
+                w = vnMatches21[bestIdx2]
+                vnMatches12[w] = -1
                 nmatches -= 1
+                visits[w]["exit"] = NX_STOLEN
+                v["victim"], v["depth"] = w, 1 + visits[w]["depth"]
+                if not R["stolen_stay_in_hist"] and visits[w]["bin"] >= 0:
+                    rotHist[visits[w]["bin"]].remove(w)
             vnMatches12[i1] = bestIdx2
             vnMatches21[bestIdx2] = i1
-            vMatchedDistance[bestIdx2] = bestDist
+            vMatchedDistance[bestIdx2] = best
             nmatches += 1
+            v["exit"], v["match"] = NX_MATCHED, bestIdx2
             if check_orientation:
-                rotHist[_rot_bin(keys1["angle"][i1], F2.angle[bestIdx2])].append(i1)
+                v["bin"] = _rot_bin(keys1["angle"][i1], F2.angle[bestIdx2], R["round"])
+                rotHist[v["bin"]].append(i1)
+    hist, ind, hist_stolen = [0] * HISTO_LENGTH, (-1, -1, -1), 0
     if check_orientation:
-        ind = compute_three_maxima([len(h) for h in rotHist])
-        for i in range(HISTO_LENGTH):
-            if i in ind:
-                continue
-            for idx1 in rotHist[i]:
-                if vnMatches12[idx1] >= 0:
-                    vnMatches12[idx1] = -1
-                    nmatches -= 1
+        hist_stolen = sum(vnMatches12[i] < 0 for h in rotHist for i in h)
+
+        def clear(v):
+            if vnMatches12[v["a"]] >= 0:
+                vnMatches12[v["a"]] = -1
+                v["exit"] = NX_ROTATION
+                return True
+            return False
+        hist, ind, dec = _close_rotation(R, rotHist, visits, clear)
+        nmatches -= dec
     for i1 in range(n1):
         if vnMatches12[i1] >= 0:
             prev[i1] = (F2.x[vnMatches12[i1]], F2.y[vnMatches12[i1]])
-    return nmatches, vnMatches12, prev
+    exits, facts = _node_result(n1, visits, hist=hist, maxima=ind, hist_stolen=hist_stolen)
+    return nmatches, np.array(vnMatches12, np.int32).reshape(-1), prev, exits, facts
+
+
+def ref_search_for_initialization(keys1, desc1, F2, prev_matched, window, nnratio, check_orientation):
+    """SearchForInitialization(F1, F2, vbPrevMatched, vnMatches12, windowSize) (:388-492).  Returns (nmatches, vnMatches12,
+    updated vbPrevMatched)."""
+    nm, m12, prev = init_walk(keys1, desc1, F2, prev_matched, window, nnratio, check_orientation)[:3]
+    return nm, m12.tolist(), prev
 
 
 # the ways a left keypoint leaves Frame::ComputeStereoMatches, in the order the walk below meets them

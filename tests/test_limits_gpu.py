@@ -519,7 +519,47 @@ def test_ordered_resolvers_at_9500(big, n):
     m.close()
 
 
-# ------------------------------------------------------------------------------------------------------------- 6. carry frame
+# ------------------------------------------------------------------------------------------------------------- 6. initialisation tables in LDS
+def test_search_for_initialization_at_the_lds_limit():
+    """SearchForInitialization keeps vMatchedDistance and vnMatches21 of the second frame in LDS, 8 bytes per keypoint and 60 KiB at
+    the most: 7680 keypoints equal the oracle (the last index matched, so both tables are written at their last entry), 7681 are
+    refused on the host before any kernel, and the handle goes on working"""
+    n2 = 7680
+    rng = np.random.default_rng(n2)
+    w, h, n1 = 1241, 376, 600
+    k = np.zeros(n2 + 1, ol.KP_DTYPE)
+    k["x"] = rng.uniform(0, w, n2 + 1).astype(np.float32); k["y"] = rng.uniform(0, h, n2 + 1).astype(np.float32)
+    k["octave"] = rng.integers(0, 3, n2 + 1); k["angle"] = rng.uniform(0, 360, n2 + 1).astype(np.float32); k["size"] = 31
+    k["octave"][n2 - 1] = 0
+    d = rng.integers(0, 256, (n2 + 1, 32), dtype=np.uint8)
+    sf = np.array([np.float32(1.2) ** i for i in range(8)], np.float32)
+    # first frame: copies of level-0 keypoints of the second, the last index among them and a third of them twice (the nearer copy
+    # comes later and steals), moved by a few pixels and with a few bits turned
+    lvl0 = np.flatnonzero(k["octave"][:n2] == 0)
+    src = np.concatenate([[n2 - 1], rng.choice(lvl0, n1 - 201, replace=False)])
+    src = np.concatenate([src, src[:200]])
+    k1 = k[src].copy()
+    k1["angle"] = (k1["angle"] + rng.normal(0, 3, n1)).astype(np.float32) % np.float32(360)
+    k1["octave"][rng.random(n1) < 0.1] = 1
+    d1 = d[src].copy()
+    d1[:n1 - 200, :3] ^= 0x15
+    d1[n1 - 200:, :1] ^= 0x01
+    prev = np.stack([k1["x"] + rng.uniform(-4, 4, n1).astype(np.float32), k1["y"] + rng.uniform(-4, 4, n1).astype(np.float32)], 1)
+    prev = prev.astype(np.float32)
+    m = ORBmatcher(0.9, True)
+    f1 = FrameView(k1, d1, 0, w, 0, h)
+    nm, m12, p2 = m.SearchForInitialization(f1, FrameView(k[:n2], d[:n2], 0, w, 0, h), prev, 10)
+    onm, om12, op2 = ol.search_for_initialization(k1, d1, ol.OracleFrame(k[:n2], d[:n2], sf, 0, w, 0, h), prev, 10, np.float32(0.9), True)
+    assert nm == onm and nm > 200
+    np.testing.assert_array_equal(m12, om12)
+    assert p2.tobytes() == op2.tobytes()
+    assert (m12 == n2 - 1).any() and (m12[:200] == -1).sum() > 100       # the last table entry is used; matches were stolen
+    _refused(m.SearchForInitialization, f1, FrameView(k, d, 0, w, 0, h), prev, 10, match="exceeds the LDS-resident tables")
+    nm2, m12b, p2b = m.SearchForInitialization(f1, FrameView(k[:n2], d[:n2], 0, w, 0, h), prev, 10)
+    assert nm2 == onm and np.array_equal(m12b, om12) and p2b.tobytes() == op2.tobytes()
+
+
+# ------------------------------------------------------------------------------------------------------------- 7. carry frame
 def test_carry_frame_feeds_frame_zero_and_refuses_shift_2():
     """orbfe_track_queries_stereo_device: a carry that differs from the batch's tail changes frame 0's queries (they come from the
     carry, as the oracle computes them); frame_shift 2 without a carry wraps mod F; frame_shift 2 with a carry is refused (the
